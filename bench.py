@@ -1,7 +1,7 @@
 """Headline benchmark: forecast-steps/sec of one Aurora forward step (+6 h) on the 0.25-degree
 ERA5 grid (721 x 1440, 13 pressure levels, 2 history states), bf16 backbone (autocast=True).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 A "step" is one `Aurora.forward` of the 1.3 B-parameter AuroraPretrained configuration
@@ -17,9 +17,19 @@ distributed between steps (`gather_output=False`), `value` = steps of that one f
 `AURORA_BENCH_MODE=replicas` instead lets every rank advance its own forecast (ensemble members, no
 collective on the data path, "weak" scaling, `value` = steps of all ranks per second).
 
-One JSON line on stdout (rank 0), with two extra objects:
+A plain run sets up, warms up, times K steps and prints one JSON line on stdout (rank 0): `value`, `ms_per_step` (the
+mean time of one timed step) and what they measured.
+
+--dump-outputs DIR  after the timed steps, what the last one returned (`pred.surf_vars` / `pred.atmos_vars`) as
+                DIR/surf_<var>.npy and DIR/atmos_<var>.npy, float32 (with N > 1 ranks: DIR/rank<R>_...npy, each rank's
+                own rows).  At most 64 MB in all: every array gets an equal share; one larger than its share is written
+                as a fixed seeded sample of that many of its elements (flattened, in index order), the same on every run.
+
+--full adds the measurements and checks that take runs of their own, to the same line:
+  kernel_ms_per_step  one more step with HIP events around every launch, per kernel.
+  per_rank      (N > 1, bands) K more steps per rank with the halo waits timed.
   roofline      the dominant kernel (bf16 MFMA GEMM): algorithmic FLOPs / mean launch time measured
-                with HIP events on the launch stream during the timed steps, vs the 2.5 PF dense peak;
+                with HIP events on the launch stream during K more steps, vs the 2.5 PF dense peak;
                 `attention` holds the same for the HBM-bound window-attention kernel (bytes / time
                 vs 8 TB/s).
   cpu_baseline  the CPU oracle (a port of the reference's algorithm, oracle/aurora_oracle.py) timed on this box's host
@@ -92,6 +102,26 @@ def synthetic_batch(cfg, H, W, seed, device, levels=LEVELS):
     md = Metadata(lat=torch.linspace(90, -90, H), lon=torch.linspace(0, 360, W + 1)[:-1],
                   time=(datetime(2020, 6, 1, 12, 0, tzinfo=timezone.utc),), atmos_levels=levels)
     return Batch(surf, static, atmos, md).to(device)
+
+
+DUMP_BYTES = 64_000_000
+
+
+def dump_outputs(pred, out_dir: Path, prefix: str = "", budget_bytes: int = DUMP_BYTES) -> None:
+    """`pred`'s arrays as float32 .npy files under `out_dir` (see the module docstring): an equal share of the budget
+    each; an array larger than its share is written as a seeded sample of its flattened elements, in index order."""
+    import numpy as np
+
+    arrays = [(f"surf_{k}", v) for k, v in pred.surf_vars.items()] + [(f"atmos_{k}", v) for k, v in pred.atmos_vars.items()]
+    share = (budget_bytes - 256 * len(arrays)) // (4 * len(arrays))   # 256 B covers an .npy header
+    g = torch.Generator().manual_seed(0)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    for name, v in arrays:
+        v = v.detach()
+        if v.numel() > share:
+            idx = torch.randperm(v.numel(), generator=g)[:share].sort().values
+            v = v.reshape(-1)[idx.to(v.device)]
+        np.save(out_dir / f"{prefix}{name}.npy", v.float().cpu().numpy())
 
 
 _T0 = time.perf_counter()
@@ -183,7 +213,8 @@ def cpu_baseline(model, H: int, W: int, budget_s: float, cls_name: str = "Aurora
     torch ops).  Returns (cpu_baseline object, oracle outputs of the full grid or None)."""
     import subprocess
 
-    threads = min(os.cpu_count() or 1, 64)
+    # the cores this process may use (OMP_NUM_THREADS where the host sets it): more threads than cores slows the oracle down
+    threads = int(os.environ.get("OMP_NUM_THREADS") or 0) or min(len(os.sched_getaffinity(0)), 64)
     tmp = _tmp_dir()
     wpath, opath = tmp / f"aurora_bench_weights_{os.getpid()}.pt", tmp / f"aurora_bench_oracle_{os.getpid()}.pt"
     outputs = None
@@ -267,9 +298,13 @@ def main() -> None:
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--cpu-budget", type=float, default=900.0,
-                    help="seconds the CPU oracle leg may take (full grid: ~5 min on 64 cores)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned to DIR/<name>.npy (float32, at most 64 MB in all)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, per-kernel and per-rank figures, the CPU oracle and full-grid parity")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave out the CPU oracle leg")
+    ap.add_argument("--cpu-budget", type=float, default=450.0,
+                    help="seconds the CPU oracle leg may take (full grid: ~5 min on 64 cores); keeps --full within 10 minutes")
     ap.add_argument("--grid", default="721x1440", help=argparse.SUPPRESS)   # tests run the same script on a small grid
     ap.add_argument("--cpu-worker", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-threads", type=int, default=8, help=argparse.SUPPRESS)
@@ -277,6 +312,8 @@ def main() -> None:
     ap.add_argument("--cpu-out", default="", help=argparse.SUPPRESS)
     ap.add_argument("--cpu-model", default="AuroraPretrained", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     GH, GW = map(int, args.grid.split("x"))
     if args.cpu_worker:
         cpu_worker(args.cpu_budget, args.cpu_threads, args.cpu_weights, args.cpu_out, GH, GW, args.cpu_model)
@@ -405,38 +442,42 @@ def main() -> None:
         barrier()
         elapsed = time.perf_counter() - t0
         log(f"timed region done: {elapsed / args.steps * 1e3:.1f} ms/step")
-        # (2) the same K steps again with HIP events (on the launch stream, inside the C-ABI handle) around every launch
-        # of the roofline kernels -> `roofline`.  Kept out of (1): an event pair keeps a launch from overlapping
-        # its neighbours, ~250 pairs per step cost about 1 % of it.
-        eng = model.engine()
-        eng.profile_start({"linear_bf16", "linear_layernorm_bf16", "window_attention_bf16"})
-        for _ in range(args.steps):
-            model.forward(batch)
-        barrier()
-        prof = eng.profile_stop()
-        eng.profile_start()          # (3) one more step with events around everything, for the per-kernel breakdown
-        model.forward(batch)
-        breakdown = eng.profile_stop()
-        # (4) sharded runs: K more steps per rank with an event pair around every halo `wait` on the launch stream -- how
-        # long a rank's stream stood still for messages (what the exchange did NOT hide) -- next to the rank's own step time
-        # measured WITHOUT a barrier between ranks; the first scaling record then says whether a rank is slow or waiting
+        if args.dump_outputs:
+            dump_outputs(pred, Path(args.dump_outputs), f"rank{rank}_" if distributed else "", DUMP_BYTES // world)
+            log(f"outputs of the last timed step written to {args.dump_outputs}")
         per_rank = None
-        if mode == "bands":
-            tr = eng.native.transport
-            tr.time_waits = True
-            tr.wait_ms()
-            barrier()
-            t1 = time.perf_counter()
+        if args.full:
+            # (2) the same K steps again with HIP events (on the launch stream, inside the C-ABI handle) around every launch
+            # of the roofline kernels -> `roofline`.  Kept out of (1): an event pair keeps a launch from overlapping
+            # its neighbours, ~250 pairs per step cost about 1 % of it.
+            eng = model.engine()
+            eng.profile_start({"linear_bf16", "linear_layernorm_bf16", "window_attention_bf16"})
             for _ in range(args.steps):
                 model.forward(batch)
-            torch.cuda.synchronize()
-            mine = [(time.perf_counter() - t1) / args.steps * 1e3, tr.wait_ms() / args.steps, float(tr.exchanges)]
-            tr.time_waits = False
-            every = [None] * world
-            dist.all_gather_object(every, mine)
-            per_rank = {"step_ms": [round(v[0], 3) for v in every], "halo_wait_ms": [round(v[1], 3) for v in every],
-                        "compute_ms": [round(v[0] - v[1], 3) for v in every],
-                        "max_rank_compute_ms": round(max(v[0] - v[1] for v in every), 3)}
+            barrier()
+            prof = eng.profile_stop()
+            eng.profile_start()          # (3) one more step with events around everything, for the per-kernel breakdown
+            model.forward(batch)
+            breakdown = eng.profile_stop()
+            # (4) sharded runs: K more steps per rank with an event pair around every halo `wait` on the launch stream -- how
+            # long a rank's stream stood still for messages (what the exchange did NOT hide) -- next to the rank's own step
+            # time measured WITHOUT a barrier between ranks; the first scaling record then says whether a rank is slow or waiting
+            if mode == "bands":
+                tr = eng.native.transport
+                tr.time_waits = True
+                tr.wait_ms()
+                barrier()
+                t1 = time.perf_counter()
+                for _ in range(args.steps):
+                    model.forward(batch)
+                torch.cuda.synchronize()
+                mine = [(time.perf_counter() - t1) / args.steps * 1e3, tr.wait_ms() / args.steps, float(tr.exchanges)]
+                tr.time_waits = False
+                every = [None] * world
+                dist.all_gather_object(every, mine)
+                per_rank = {"step_ms": [round(v[0], 3) for v in every], "halo_wait_ms": [round(v[1], 3) for v in every],
+                            "compute_ms": [round(v[0] - v[1], 3) for v in every],
+                            "max_rank_compute_ms": round(max(v[0] - v[1] for v in every), 3)}
     assert torch.isfinite(pred.surf_vars["2t"]).all()
 
     if distributed:
@@ -449,36 +490,6 @@ def main() -> None:
     if rank == 0:
         ms_per_step = elapsed / args.steps * 1e3
         value = (1 if mode == "bands" else world) * args.steps / elapsed
-        zero = {"launches": 0, "ms": 0.0, "work": 0.0}
-        g = prof.get("linear_bf16", zero)
-        f = prof.get("linear_layernorm_bf16", zero)
-        a = prof.get("window_attention_bf16", zero)
-        gemm_tf = g["work"] / (g["ms"] * 1e-3) / 1e12 if g["ms"] else 0.0
-        all_tf = (g["work"] + f["work"]) / ((g["ms"] + f["ms"]) * 1e-3) / 1e12 if g["ms"] + f["ms"] else 0.0
-        attn_gbs = a["work"] / (a["ms"] * 1e-3) / 1e9 if a["ms"] else 0.0
-        # HBM-side bytes per launch of the dominant kernel come from hardware counters, which only rocprofv3 can collect:
-        # the tracked PMC summary of THIS command (tools/profile_round.sh -> tools/pmc_rollup.py), not a live value --
-        # `traffic_build` names the commit whose library those passes profiled.
-        traffic, traffic_build = None, None
-        pmc = sorted((ROOT / "profiles").glob("r*_pmc_summary.json"))
-        traffic_stale, stale_sources = None, None
-        if pmc:
-            import hashlib
-
-            pj = json.loads(pmc[-1].read_text())
-            traffic, traffic_build = pj.get("linear_bf16_hbm_bytes_per_launch"), pj.get("build_commit")
-            # counters are static evidence of the build they profiled: if the GEMM source has changed since (its SHA-256 is
-            # recorded by tools/pmc_rollup.py), the figure is withheld instead of going stale silently
-            sha = hashlib.sha256((ROOT / "aurora_amd" / "csrc" / "gemm.hip").read_bytes()).hexdigest()
-            traffic_stale = pj.get("gemm_source_sha256") != sha
-            if traffic_stale:
-                traffic = None
-            # every kernel source, not only the GEMM's: which of the profiled files differ from the tree (their rows in the
-            # committed rNN_kernel_stats.txt / rNN_pmc_summary.json describe an earlier build)
-            stale_sources = sorted(n for n, d in (pj.get("source_sha256") or {}).items()
-                                   if n != "libaurora_hip.so" and (not (ROOT / "aurora_amd" / "csrc" / n).exists() or
-                                   hashlib.sha256((ROOT / "aurora_amd" / "csrc" / n).read_bytes()).hexdigest() != d))
-        per = max(args.steps, 1)
         out = {
             "metric": "forecast-steps/sec (6h step) 0.25deg ERA5 721x1440x13",
             "value": value, "unit": "forecast-steps/s", "n_gpus": world, "steps": args.steps,
@@ -492,7 +503,40 @@ def main() -> None:
                                                 "(3 rows per shifted block and side), state kept distributed",
                                        "replicas": f"replica x{world} (independent forecasts, no data-path "
                                                    "collective)"}[mode]},
-            "roofline": {
+            "step_tflops": FLOP_PER_STEP / (ms_per_step * 1e-3) / 1e12 if (GH, GW) == (721, 1440) else None,
+        }
+        if args.full:
+            zero = {"launches": 0, "ms": 0.0, "work": 0.0}
+            g = prof.get("linear_bf16", zero)
+            f = prof.get("linear_layernorm_bf16", zero)
+            a = prof.get("window_attention_bf16", zero)
+            gemm_tf = g["work"] / (g["ms"] * 1e-3) / 1e12 if g["ms"] else 0.0
+            all_tf = (g["work"] + f["work"]) / ((g["ms"] + f["ms"]) * 1e-3) / 1e12 if g["ms"] + f["ms"] else 0.0
+            attn_gbs = a["work"] / (a["ms"] * 1e-3) / 1e9 if a["ms"] else 0.0
+            # HBM-side bytes per launch of the dominant kernel come from hardware counters, which only rocprofv3 can collect:
+            # the tracked PMC summary of THIS command (tools/profile_round.sh -> tools/pmc_rollup.py), not a live value --
+            # `traffic_build` names the commit whose library those passes profiled.
+            traffic, traffic_build = None, None
+            pmc = sorted((ROOT / "profiles").glob("r*_pmc_summary.json"))
+            traffic_stale, stale_sources = None, None
+            if pmc:
+                import hashlib
+
+                pj = json.loads(pmc[-1].read_text())
+                traffic, traffic_build = pj.get("linear_bf16_hbm_bytes_per_launch"), pj.get("build_commit")
+                # counters are static evidence of the build they profiled: if the GEMM source has changed since (its SHA-256 is
+                # recorded by tools/pmc_rollup.py), the figure is withheld instead of going stale silently
+                sha = hashlib.sha256((ROOT / "aurora_amd" / "csrc" / "gemm.hip").read_bytes()).hexdigest()
+                traffic_stale = pj.get("gemm_source_sha256") != sha
+                if traffic_stale:
+                    traffic = None
+                # every kernel source, not only the GEMM's: which of the profiled files differ from the tree (their rows in the
+                # committed rNN_kernel_stats.txt / rNN_pmc_summary.json describe an earlier build)
+                stale_sources = sorted(n for n, d in (pj.get("source_sha256") or {}).items()
+                                       if n != "libaurora_hip.so" and (not (ROOT / "aurora_amd" / "csrc" / n).exists() or
+                                       hashlib.sha256((ROOT / "aurora_amd" / "csrc" / n).read_bytes()).hexdigest() != d))
+            per = max(args.steps, 1)
+            out["roofline"] = {
                 "kernel": "linear_kernel_256pp (bf16 MFMA GEMM, ping-pong LDS ring): the plain backbone linears of a step; "
                           "`frac_all_matrix_launches` adds the stage-0 proj / fc2 launches that run fused with their "
                           "AdaLN + residual (linear_layernorm_bf16)", "bound": "mfma",
@@ -512,10 +556,8 @@ def main() -> None:
                               "frac_moved_bytes": attn_gbs / PEAK_HBM_GBS * attention_moved_fraction(
                                   model.config, (GH - GH % model.patch_size) // model.patch_size, GW // model.patch_size),
                               "launches_per_step": a["launches"] / per, "ms_per_step": a["ms"] / per},
-            },
-            "step_tflops": FLOP_PER_STEP / (ms_per_step * 1e-3) / 1e12 if (GH, GW) == (721, 1440) else None,
-            "kernel_ms_per_step": {k: v["ms"] for k, v in sorted(breakdown.items())},   # (the extra, un-timed step)
-        }
+            }
+            out["kernel_ms_per_step"] = {k: v["ms"] for k, v in sorted(breakdown.items())}   # (the extra, un-timed step)
         if per_rank is not None:
             out["per_rank"] = per_rank
         if bands_error is not None:   # asked for a sharded forecast, measured replicas: the record says why
@@ -523,7 +565,7 @@ def main() -> None:
         # the GPU measurement is safe in the log before the (long) CPU leg starts: a driver that gives up on the CPU oracle
         # still finds it on stderr; stdout carries exactly one line, at the end
         log("GPU-only result: " + json.dumps(out))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             log("running the CPU oracle on the same weights and Batch (full grid)")
             out["cpu_baseline"], oracle_out = cpu_baseline(model, GH, GW, args.cpu_budget)
             if oracle_out is not None:

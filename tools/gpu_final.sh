@@ -1,7 +1,7 @@
 #!/bin/bash
 # The round's record runs on ONE box (so that the numbers belong together):  tools/gpu_final.sh <tag> [part ...]
 #   rocprof   tools/profile_round.sh: rocprofv3 kernel stats + three PMC passes of bench.py
-#   bench     bench.py with the driver's flags (full CPU oracle leg, full-grid parity)
+#   bench     bench.py --full (roofline, per-kernel times, full CPU oracle leg, full-grid parity)
 #   ranks     virtual ranks 2 4 8 of the headline config + the other sharded configs at 8
 #   configs   tools/bench_configs.py (roll-out eager / graph / to_host, AuroraHighRes, AuroraAirPollution)
 #   kinds     tools/rank_kinds.py 8 4 + tools/step_shapes.py
@@ -24,7 +24,7 @@ if has ranks; then
 fi
 if has configs; then timeout 900 python tools/bench_configs.py > $OUT/${TAG}_bench_configs.json 2>/dev/null; cat $OUT/${TAG}_bench_configs.json; fi
 if has bench; then
-  timeout 1500 python bench.py --steps 20 --warmup 3 2> $OUT/${TAG}_bench.err | grep '^{"metric"' | tail -1 > $OUT/${TAG}_bench.json
+  timeout 1500 python bench.py --steps 20 --warmup 3 --full 2> $OUT/${TAG}_bench.err | grep '^{"metric"' | tail -1 > $OUT/${TAG}_bench.json
   python - <<PY
 import json
 d = json.load(open("$OUT/${TAG}_bench.json"))

@@ -9,7 +9,7 @@ has() { [[ " $WHAT " == *" $1 "* || " $WHAT " == *" all "* ]]; }
 if has tests; then timeout 1500 python -m pytest tests -m gpu -x -q > $OUT/${TAG}_gpu_tests.log 2>&1; echo "tests rc=$?" | tee -a $OUT/${TAG}_gpu_tests.log; tail -3 $OUT/${TAG}_gpu_tests.log; fi
 if has optests; then timeout 900 python -m pytest tests/test_gpu_ops.py tests/test_gpu_sharded.py -m gpu -x -q > $OUT/${TAG}_gpu_optests.log 2>&1; echo "optests rc=$?" | tee -a $OUT/${TAG}_gpu_optests.log; tail -3 $OUT/${TAG}_gpu_optests.log; fi
 if has bench; then
-  timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline 2> $OUT/${TAG}_bench.err | grep '^{"metric"' | tail -1 > $OUT/${TAG}_bench_nocpu.json
+  timeout 600 python bench.py --steps 10 --warmup 3 --no-cpu-baseline --full 2> $OUT/${TAG}_bench.err | grep '^{"metric"' | tail -1 > $OUT/${TAG}_bench_nocpu.json
   python - <<PY
 import json
 d = json.load(open("$OUT/${TAG}_bench_nocpu.json"))

@@ -31,8 +31,8 @@ tot = sum(n.values())
 w = lambda key: sum(v[key] * n[k] for k, v in gemm.items()) / tot  # noqa: E731
 out = {
     "_about": "rocprofv3 --pmc passes (FETCH_SIZE+GRBM_GUI_ACTIVE, WRITE_SIZE, SQ counters: three separate runs, "
-              "tools/profile_round.sh) of `python bench.py --steps 3 --warmup 1 --no-cpu-baseline`, aggregated per kernel by "
-              "tools/pmc_summary.py and rolled up by tools/pmc_rollup.py; values are means per launch.",
+              "tools/profile_round.sh) of `python bench.py --steps 3 --warmup 1 --no-cpu-baseline --full`, aggregated per "
+              "kernel by tools/pmc_summary.py and rolled up by tools/pmc_rollup.py; values are means per launch.",
     "_calibration": "FETCH_SIZE reports 0.500 of the bytes actually read for all three access patterns probed "
                     "(profiles/r02_fetch_calibration.txt), so reads = 2 x FETCH_SIZE x 1024 B for every kernel here, the GEMM "
                     "included (round 1 took x1 for the GEMM: wrong).  FETCH_SIZE counts L2 misses on the fabric side: "
