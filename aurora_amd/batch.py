@@ -153,7 +153,59 @@ class Batch:
 
     # -- regridding and I/O (not on the per-step path) -----------------------------------
     def regrid(self, res: float) -> "Batch":
-        """Bilinear regrid to a `res`-degree grid (float32, CPU), periodic in longitude."""
+        """Bilinear regrid to a `res`-degree grid (float32), periodic in longitude.
+
+        A batch on the CPU goes through SciPy; a batch whose fields and (vector) coordinates all live on one GPU is
+        regridded there, in one HIP launch, with the same arithmetic, and stays there."""
+        md = self.metadata
+        tensors = [*self.surf_vars.values(), *self.static_vars.values(), *self.atmos_vars.values(), md.lat, md.lon]
+        devices = {t.device for t in tensors}
+        if all(d.type == "cpu" for d in devices):
+            return self._regrid_host(res)
+        if len(devices) != 1 or next(iter(devices)).type != "cuda":
+            raise ValueError(f"Batch.regrid: the fields and coordinates are on {sorted(map(str, devices))}; "
+                             "move the whole batch to the CPU or to one GPU first")
+        if md.lat.dim() != 1 or md.lon.dim() != 1:
+            raise ValueError("Batch.regrid on the GPU needs vector latitudes and longitudes, not matrices")
+        return self._regrid_device(res)
+
+    def _regrid_device(self, res: float) -> "Batch":
+        """The HIP path of `regrid`: tables from the library's host arithmetic, then one launch per source dtype (one for
+        an all-fp32 batch) over every plane.  bf16 / fp16 fields are widened to fp32 first (lossless)."""
+        from aurora_amd.engine import lib
+
+        md = self.metadata
+        dev = md.lat.device
+        n_lat, n_lon = round(180 / res) + 1, round(360 / res)
+        lat_new = np.linspace(90, -90, n_lat)
+        lon_new = np.linspace(0, 360, n_lon, endpoint=False)
+        tables = lib.regrid_plan(md.lat.double().cpu().numpy(), md.lon.double().cpu().numpy(), lat_new, lon_new)
+        rows, row_w, cols, col_w = (torch.from_numpy(t).to(dev) for t in tables)
+        shape = (md.lat.shape[0], md.lon.shape[0])
+        work: dict[torch.dtype, tuple[list, list]] = {}
+
+        def f(v: torch.Tensor) -> torch.Tensor:
+            if tuple(v.shape[-2:]) != shape:
+                raise ValueError(f"Batch.regrid: a field of shape {tuple(v.shape)} does not match the {shape} grid")
+            if v.dtype in (torch.bfloat16, torch.float16):
+                v = v.float()
+            elif v.dtype != torch.float32:
+                v = v.double()
+            out = torch.empty(*v.shape[:-2], n_lat, n_lon, dtype=torch.float32, device=dev)
+            pair = work.setdefault(v.dtype, ([], []))
+            pair[0].append(v.contiguous())
+            pair[1].append(out)
+            return out
+
+        surf = {k: f(v) for k, v in self.surf_vars.items()}
+        static = {k: f(v) for k, v in self.static_vars.items()}
+        atmos = {k: f(v) for k, v in self.atmos_vars.items()}
+        for src, dst in work.values():
+            lib.regrid(src, dst, rows, row_w, cols, col_w)
+        md = derive_metadata(md, lat=torch.from_numpy(lat_new).to(dev), lon=torch.from_numpy(lon_new).to(dev))
+        return Batch(surf, static, atmos, md)
+
+    def _regrid_host(self, res: float) -> "Batch":
         n_lat, n_lon = round(180 / res) + 1, round(360 / res)
         lat_new = torch.from_numpy(np.linspace(90, -90, n_lat))
         lon_new = torch.from_numpy(np.linspace(0, 360, n_lon, endpoint=False))
@@ -250,6 +302,9 @@ class BandBatch(Batch):
 
     def crop(self, patch_size: int) -> "BandBatch":
         return self  # a band is cut out of an already cropped grid
+
+    def regrid(self, res: float) -> "Batch":
+        return self._regrid_host(res)
 
     def to_netcdf(self, path: str | Path) -> None:
         """Sharded output: every rank writes ITS latitude band to its own file -- `path` is a

@@ -15,9 +15,10 @@ from ctypes import c_float, c_int, c_int32, c_int64, c_void_p
 from pathlib import Path
 from typing import Optional
 
+import numpy as np
 import torch
 
-F32, BF16 = 0, 1
+F32, BF16, F64 = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_SILU = 0, 1, 2
 
 _LIB_PATH = Path(__file__).resolve().parents[1] / "_lib" / "libaurora_hip.so"
@@ -118,6 +119,10 @@ _SIGNATURES = {
     "aurora_hip_copy2d": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_int,
                                   c_void_p]),
     "aurora_hip_convert": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p]),
+    "aurora_hip_regrid_plan": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p,
+                                       c_void_p, c_void_p, c_void_p]),
+    "aurora_hip_regrid": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
+                                  c_void_p, c_int, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -637,6 +642,51 @@ def convert(src: torch.Tensor, dst: torch.Tensor) -> torch.Tensor:
     with _Timed("convert", 0.0):
         _check(load().aurora_hip_convert(_ptr(src), _ptr(dst), src.numel(), dtype_code(src.dtype), _stream()))
     return dst
+
+
+def regrid_plan(lat, lon, lat_new, lon_new) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+    """Interpolation tables of `Batch.regrid` (aurora_hip_regrid_plan, host arithmetic): (rows (n_lat_new, 2) int32,
+    row_w (n_lat_new,) float64, cols (n_lon_new, 2) int32, col_w (n_lon_new,) float64) for vector coordinates."""
+    lat, lon, lat_new, lon_new = (np.ascontiguousarray(x, dtype=np.float64) for x in (lat, lon, lat_new, lon_new))
+    assert lat.ndim == lon.ndim == lat_new.ndim == lon_new.ndim == 1, "regrid_plan: coordinates must be vectors"
+    rows, cols = np.zeros((len(lat_new), 2), np.int32), np.zeros((len(lon_new), 2), np.int32)
+    row_w, col_w = np.zeros(len(lat_new)), np.zeros(len(lon_new))
+    _check(load().aurora_hip_regrid_plan(lat.ctypes.data, len(lat), lon.ctypes.data, len(lon), lat_new.ctypes.data,
+                                         len(lat_new), lon_new.ctypes.data, len(lon_new), rows.ctypes.data,
+                                         row_w.ctypes.data, cols.ctypes.data, col_w.ctypes.data))
+    return rows, row_w, cols, col_w
+
+
+def regrid(src: list[torch.Tensor], dst: list[torch.Tensor], rows: torch.Tensor, row_w: torch.Tensor,
+           cols: torch.Tensor, col_w: torch.Tensor) -> None:
+    """dst[i][..., r, c] = the bilinear regrid of src[i][..., :, :] for every plane of every pair, in ONE launch.
+
+    src: contiguous (..., n_lat, n_lon) tensors, all fp32 or all fp64; dst: contiguous fp32 (..., n_rows, n_cols) with
+    the same leading shape; the tables: device copies of `regrid_plan`'s (a slice rows[r0:r1], row_w[r0:r1] regrids
+    output rows r0..r1-1 only)."""
+    assert len(src) == len(dst) and src
+    dt = src[0].dtype
+    n_lat, n_lon = src[0].shape[-2:]
+    n_rows, n_cols = rows.shape[0], cols.shape[0]
+    assert dt in (torch.float32, torch.float64), f"regrid: sources must be fp32 or fp64, got {dt}"
+    assert rows.dtype == cols.dtype == torch.int32 and row_w.dtype == col_w.dtype == torch.float64
+    assert rows.shape == (n_rows, 2) and cols.shape == (n_cols, 2) and row_w.shape == (n_rows,) and col_w.shape == (n_cols,)
+    assert all(t.is_contiguous() for t in (rows, row_w, cols, col_w))
+    sp, dp = [], []
+    for s_, d_ in zip(src, dst):
+        assert s_.dtype == dt and s_.is_contiguous() and s_.shape[-2:] == (n_lat, n_lon), "regrid: bad source"
+        assert d_.dtype == torch.float32 and d_.is_contiguous() and d_.shape == (*s_.shape[:-2], n_rows, n_cols), "regrid: bad output"
+        assert s_.device == d_.device == rows.device, "regrid: every tensor must be on the same device"
+        n = s_.numel() // (n_lat * n_lon) if s_.numel() else 0
+        sp += [s_.data_ptr() + i * n_lat * n_lon * s_.element_size() for i in range(n)]
+        dp += [d_.data_ptr() + i * n_rows * n_cols * 4 for i in range(n)]
+    if not sp:
+        return
+    planes = torch.tensor([sp, dp], dtype=torch.int64).to(rows.device)
+    with _Timed("regrid", 0.0):
+        _check(load().aurora_hip_regrid(_ptr(planes[0]), F64 if dt == torch.float64 else F32, _ptr(planes[1]), len(sp),
+                                        n_lat, n_lon, _ptr(rows), _ptr(row_w), n_rows, _ptr(cols), _ptr(col_w), n_cols,
+                                        _stream()))
 
 
 # ---- model handle (one forecast step behind the C ABI) ------------------------------------------------------

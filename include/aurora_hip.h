@@ -10,7 +10,8 @@
  * Every function only enqueues work on `stream` and returns 0 on success or a negative
  * AURORA_E_* code; aurora_hip_last_error() describes the last failure of the calling thread.
  *
- * dtype codes: AURORA_F32 = 0 (float), AURORA_BF16 = 1 (bfloat16, raw uint16 storage).
+ * dtype codes: AURORA_F32 = 0 (float), AURORA_BF16 = 1 (bfloat16, raw uint16 storage), AURORA_F64 = 2 (double; regrid
+ * sources only).
  */
 #ifndef AURORA_HIP_H
 #define AURORA_HIP_H
@@ -23,6 +24,7 @@ extern "C" {
 
 #define AURORA_F32 0
 #define AURORA_BF16 1
+#define AURORA_F64 2
 
 #define AURORA_OK 0
 #define AURORA_E_ARG (-1)     /* invalid argument (shape / alignment / dtype) */
@@ -626,6 +628,31 @@ int aurora_hip_profile_end(aurora_hip_model* model, aurora_hip_profile_entry* ou
 /* The same, one entry per LAUNCH in launch order (launches = 1; `work` tells the shapes of a kind apart).  With capacity
  * smaller than the number of recorded launches only *n_out is set and the recording is kept: query first, then fetch. */
 int aurora_hip_profile_end_list(aurora_hip_model* model, aurora_hip_profile_entry* out, int capacity, int* n_out);
+
+/* ---- regridding a batch on the device (Batch.regrid of a GPU-resident batch; the reference's Batch.regrid / interpolate,
+ * batch.py:192-222, 299-362) ------------------------------------------------------------------------------------------------
+ * Bilinear interpolation from a (lat, lon) grid to another, periodic in longitude, exactly as the host path computes it
+ * (scipy.interpolate.RegularGridInterpolator(method="linear", bounds_error=False, fill_value=None) on the grid
+ * (lat, [lon[n-1] - 360, lon..., lon[0] + 360]) in fp64, rounded to fp32): on each axis, sorted ascending, a target takes
+ * the interval of the largest node <= it, clamped to the first / last interval (so a target on the last node takes the
+ * last interval and targets outside the axis extrapolate linearly), and the weight t = (x - x[i]) / (x[i+1] - x[i]); all
+ * four corners are summed even where a weight is zero, so a NaN there gives NaN.
+ * aurora_hip_regrid_plan: the interpolation tables, pure host arithmetic (no device work).  lat: n_lat >= 2 finite,
+ * strictly increasing or decreasing values; lon: n_lon >= 2 finite, strictly increasing values spanning less than 360
+ * degrees; targets finite.  Writes rows[2 k], rows[2 k + 1] (source rows) and row_w[k] (weight of the second) for every
+ * target latitude k, cols[2 k], cols[2 k + 1] (source columns, wrapped) and col_w[k] for every target longitude k.
+ * aurora_hip_regrid: dst[p][r][c] = the interpolation of src[p] (n_lat x n_lon, row-major, AURORA_F32 or AURORA_F64) for
+ * every plane p < n_planes, output row r < n_rows_out and column c < n_cols_out, in ONE launch.  src_planes / dst_planes
+ * are DEVICE arrays of n_planes plane pointers (4-byte aligned fp32 output planes of n_rows_out x n_cols_out; no other
+ * alignment needed); the four tables are device copies of the plan's.  Passing rows + 2 r0, row_w + r0 with
+ * n_rows_out = r1 - r0 regrids output rows [r0, r1) only.  Table indices are clamped into the source plane.  No host
+ * synchronisation, no workspace: capturable in a hipGraph. */
+int aurora_hip_regrid_plan(const double* lat, int n_lat, const double* lon, int n_lon, const double* lat_new, int n_lat_new,
+                           const double* lon_new, int n_lon_new, int32_t* rows, double* row_w, int32_t* cols,
+                           double* col_w);
+int aurora_hip_regrid(const void* const* src_planes, int src_dtype, float* const* dst_planes, int n_planes, int n_lat,
+                      int n_lon, const int32_t* rows, const double* row_w, int n_rows_out, const int32_t* cols,
+                      const double* col_w, int n_cols_out, void* stream);
 
 /* ---- debugging aid ------------------------------------------------------------------------------
  * The four-wave bf16 GEMM tile with the hand-scheduled main loop (csrc/gemm_a4.hip; plain bf16 linears on 256 x 256 tiles with
