@@ -1,7 +1,8 @@
 """aurora_amd: an MI355X-native forward / rollout engine for the Aurora model family.
 
 Public surface = the reference's (aurora/__init__.py:3-29).  The cyclone tracker (aurora/tracker.py) follows a roll-out
-without moving the predictions off the device: only its search windows travel (aurora_amd/tracker.py).
+without moving the predictions off the device: only its search windows travel (aurora_amd/tracker.py).  `scores` verifies a
+prediction against truth on the device (aurora_amd/scores.py); the reference has no counterpart.
 """
 
 from aurora_amd.batch import Batch, Metadata
@@ -16,6 +17,7 @@ from aurora_amd.model.aurora import (
     AuroraWave,
 )
 from aurora_amd.rollout import rollout, write_rollout
+from aurora_amd.scores import Scores, scores
 from aurora_amd.tracker import Tracker
 
 __all__ = [
@@ -31,5 +33,7 @@ __all__ = [
     "Metadata",
     "rollout",
     "write_rollout",
+    "scores",
+    "Scores",
     "Tracker",
 ]

@@ -1,0 +1,202 @@
+// Verification sums of a forecast against truth on the device (aurora_amd.scores: weighted RMSE / bias / MAE / ACC).
+//
+// For every plane (one variable, level and batch element; n_lat x n_lon fp32, row-major) the prediction p, the truth t
+// and, if given, the climatology c are read ONCE and reduced to eight fp64 sums over the points where every input
+// that is present is finite, with the row weight w[i] (include/aurora_hip.h has the table).  All differences and
+// products are formed in fp64 from the fp32 inputs; nothing is accumulated in fp32.
+//
+// The reduction tree is fixed, so a plane's sums are repeatable bit for bit and depend on nothing but its own values,
+// n_lat and n_lon -- not on the other planes of the call, and not on the alignment of the plane pointers:
+//   lane      columns 4 q .. 4 q + 3 of a row for q = lane, lane + 64, ... (one 16-byte load per input where the plane
+//             pointers are 16-byte aligned and n_lon % 4 == 0, four 4-byte loads otherwise: the same elements in the
+//             same order either way), over the rows wave, wave + 4, ... of the workgroup's row chunk;
+//   wave      xor butterfly over the 64 lanes;
+//   workgroup the four waves' sums through LDS, added in wave order: one partial per (plane, row chunk);
+//   plane     scores_finish_kernel adds the partials of a plane in chunk order.
+// No floating-point atomics, no tickets: the second launch is the hand-off.
+#include "common.h"
+
+namespace aurora {
+namespace {
+
+constexpr int kThreads = 256;
+constexpr int kWaves = kThreads / 64;
+constexpr int kSlots = 8;
+#ifndef AURORA_SCORES_CHUNK_ELEMS               // (a probe build may set it: AURORA_BUILD_FLAGS=-DAURORA_SCORES_CHUNK_ELEMS=...)
+#define AURORA_SCORES_CHUNK_ELEMS 40960
+#endif
+constexpr int kChunkElems = AURORA_SCORES_CHUNK_ELEMS;   // target size of a row chunk (elements of one input)
+
+template <typename T> using gptr = __attribute__((address_space(1))) T*;
+
+// Rows per chunk: a function of n_lon alone (and chunks per plane of n_lat, n_lon alone), never of n_planes.
+__host__ __device__ inline int chunk_rows(int n_lon) {
+  const int r = (kChunkElems + n_lon - 1) / n_lon;
+  return r < kWaves ? kWaves : r;
+}
+inline int64_t chunks_per_plane(int n_lat, int n_lon) {
+  const int r = chunk_rows(n_lon);
+  return ((int64_t)n_lat + r - 1) / r;
+}
+
+struct Acc {
+  double s2 = 0.0, s3 = 0.0, s4 = 0.0, s5 = 0.0, s6 = 0.0, s7 = 0.0;
+  int n = 0;                                    // valid points of the current row
+};
+
+// One point.  An invalid point is replaced by p = t = c = 0: every term is then exactly +0 and leaves the sums as
+// they are; only the count (and through it the weight sum) sees validity.
+template <bool kClim>
+__device__ __forceinline__ void point(Acc& a, double w, float pf, float tf, float cf, bool in_row) {
+  bool ok = in_row && __builtin_isfinite(pf) && __builtin_isfinite(tf);
+  if (kClim) ok = ok && __builtin_isfinite(cf);
+  const double p = (double)(ok ? pf : 0.f), t = (double)(ok ? tf : 0.f);
+  a.n += ok ? 1 : 0;
+  const double d = p - t;
+  const double wd = w * d;
+  a.s2 += wd;
+  a.s3 = __builtin_fma(wd, d, a.s3);
+  a.s4 += __builtin_fabs(wd);
+  if (kClim) {
+    const double c = (double)(ok ? cf : 0.f);
+    const double pp = p - c, tp = t - c;
+    const double wpp = w * pp;
+    a.s5 = __builtin_fma(wpp, tp, a.s5);
+    a.s6 = __builtin_fma(wpp, pp, a.s6);
+    a.s7 = __builtin_fma(w * tp, tp, a.s7);
+  }
+}
+
+__device__ __forceinline__ double wave_sum_f64(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+  return v;
+}
+
+// One workgroup = one row chunk of one plane; partial[(plane * n_chunks + chunk) * 8 + slot].
+template <bool kClim>
+__global__ __launch_bounds__(kThreads) void scores_kernel(const float* const* __restrict__ pred_planes,
+                                                          const float* const* __restrict__ truth_planes,
+                                                          const float* const* __restrict__ clim_planes, int n_lat,
+                                                          int n_lon, int n_chunks, const double* __restrict__ row_w,
+                                                          double* __restrict__ partial) {
+  __shared__ double s_wave[kWaves][kSlots];
+  const int plane = (int)(blockIdx.x / (unsigned)n_chunks), chunk = (int)(blockIdx.x % (unsigned)n_chunks);
+  const int lane = (int)threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
+  // (the plane pointers are global memory: said so, the loads are global_*, not flat_*)
+  const gptr<const float> P = (gptr<const float>)pred_planes[plane];
+  const gptr<const float> T = (gptr<const float>)truth_planes[plane];
+  const gptr<const float> C = kClim ? (gptr<const float>)clim_planes[plane] : P;
+  const bool vec = (n_lon & 3) == 0 && ((((uintptr_t)P | (uintptr_t)T | (uintptr_t)C) & 15) == 0);
+  const int n_quads = (n_lon + 3) >> 2;
+  const int rows = chunk_rows(n_lon);
+  const int r_begin = chunk * rows, r_end = min(r_begin + rows, n_lat);
+
+  Acc a;
+  double s1 = 0.0;
+  int count = 0;
+  for (int r = r_begin + wave; r < r_end; r += kWaves) {       // wave-uniform: w is one scalar load per row
+    const double w = row_w[r];
+    const int64_t row0 = (int64_t)r * n_lon;
+    a.n = 0;
+    if (vec) {
+      const gptr<const f32x4> p4 = (gptr<const f32x4>)(P + row0), t4 = (gptr<const f32x4>)(T + row0),
+                              c4 = (gptr<const f32x4>)(C + row0);
+#pragma unroll 2
+      for (int q = lane; q < n_quads; q += 64) {
+        const f32x4 p = p4[q], t = t4[q], c = kClim ? c4[q] : f32x4{0.f, 0.f, 0.f, 0.f};
+        point<kClim>(a, w, p.x, t.x, c.x, true);
+        point<kClim>(a, w, p.y, t.y, c.y, true);
+        point<kClim>(a, w, p.z, t.z, c.z, true);
+        point<kClim>(a, w, p.w, t.w, c.w, true);
+      }
+    } else {
+      for (int q = lane; q < n_quads; q += 64) {
+        float p[4], t[4], c[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          const int col = min(4 * q + k, n_lon - 1);           // clamped: the load is in the row, the guard is in_row
+          p[k] = P[row0 + col];
+          t[k] = T[row0 + col];
+          c[k] = kClim ? C[row0 + col] : 0.f;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) point<kClim>(a, w, p[k], t[k], c[k], 4 * q + k < n_lon);
+      }
+    }
+    count += a.n;
+    s1 = __builtin_fma(w, (double)a.n, s1);
+  }
+
+  const double sums[kSlots] = {(double)count, s1, a.s2, a.s3, a.s4, a.s5, a.s6, a.s7};
+#pragma unroll
+  for (int s = 0; s < kSlots; ++s) {
+    if (!kClim && s >= 5) break;
+    const double v = wave_sum_f64(sums[s]);
+    if (lane == 0) s_wave[wave][s] = v;
+  }
+  __syncthreads();
+  if (threadIdx.x < kSlots) {
+    const int s = (int)threadIdx.x;
+    double v = 0.0;
+    if (kClim || s < 5) {
+      v = s_wave[0][s];
+#pragma unroll
+      for (int k = 1; k < kWaves; ++k) v += s_wave[k][s];
+    }
+    partial[(int64_t)blockIdx.x * kSlots + s] = v;
+  }
+}
+
+// sums[plane][slot] = partial[plane][0][slot] + partial[plane][1][slot] + ... in chunk order; one lane per (plane, slot).
+__global__ __launch_bounds__(kThreads) void scores_finish_kernel(const double* __restrict__ partial, int n_planes,
+                                                                 int n_chunks, double* __restrict__ sums) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= (int64_t)n_planes * kSlots) return;
+  const int64_t plane = i / kSlots;
+  const int s = (int)(i % kSlots);
+  const double* p = partial + plane * n_chunks * kSlots + s;
+  double v = p[0];
+  for (int k = 1; k < n_chunks; ++k) v += p[(int64_t)k * kSlots];
+  sums[i] = v;
+}
+
+}  // namespace
+}  // namespace aurora
+
+using namespace aurora;
+
+extern "C" size_t aurora_hip_scores_workspace_bytes(int n_planes, int n_lat, int n_lon) {
+  if (n_planes < 1 || n_lat < 1 || n_lon < 1) return 0;
+  return (size_t)n_planes * (size_t)chunks_per_plane(n_lat, n_lon) * kSlots * sizeof(double);
+}
+
+extern "C" int aurora_hip_scores(const float* const* pred_planes, const float* const* truth_planes,
+                                 const float* const* clim_planes, int n_planes, int n_lat, int n_lon, const double* row_w,
+                                 double* sums, void* workspace, void* stream) {
+  AURORA_CHECK_ARG(n_planes >= 0 && n_lat >= 1 && n_lon >= 1, "scores: bad sizes (planes %d, grid %d x %d)", n_planes, n_lat,
+                   n_lon);
+  if (n_planes == 0) return AURORA_OK;
+  AURORA_CHECK_ARG(pred_planes && truth_planes && row_w && sums && workspace,
+                   "scores: null plane array, weight, output or workspace pointer");
+  AURORA_CHECK_ARG(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)sums & 7) == 0 && ((uintptr_t)row_w & 7) == 0,
+                   "scores: weights, output and workspace must be 8-byte aligned");
+  const int64_t n_chunks = chunks_per_plane(n_lat, n_lon);
+  const int64_t groups = n_chunks * n_planes;
+  AURORA_CHECK_ARG(groups <= 0x7fffffff, "scores: too many planes for one launch (%d planes x %lld row chunks)", n_planes,
+                   (long long)n_chunks);
+  double* const partial = (double*)workspace;
+  if (clim_planes)
+    hipLaunchKernelGGL(scores_kernel<true>, dim3((unsigned)groups), dim3(kThreads), 0, as_stream(stream), pred_planes,
+                       truth_planes, clim_planes, n_lat, n_lon, (int)n_chunks, row_w, partial);
+  else
+    hipLaunchKernelGGL(scores_kernel<false>, dim3((unsigned)groups), dim3(kThreads), 0, as_stream(stream), pred_planes,
+                       truth_planes, clim_planes, n_lat, n_lon, (int)n_chunks, row_w, partial);
+  const int code = check_launch("scores");
+  if (code != AURORA_OK) return code;
+  const unsigned fin = (unsigned)(((int64_t)n_planes * kSlots + kThreads - 1) / kThreads);
+  hipLaunchKernelGGL(scores_finish_kernel, dim3(fin), dim3(kThreads), 0, as_stream(stream), partial, n_planes, (int)n_chunks,
+                     sums);
+  return check_launch("scores (finish)");
+}

@@ -11,6 +11,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
+from collections import OrderedDict
 from ctypes import c_float, c_int, c_int32, c_int64, c_void_p
 from pathlib import Path
 from typing import Optional
@@ -123,6 +124,8 @@ _SIGNATURES = {
                                        c_void_p, c_void_p, c_void_p]),
     "aurora_hip_regrid": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                   c_void_p, c_int, c_void_p]),
+    "aurora_hip_scores_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int]),
+    "aurora_hip_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -687,6 +690,87 @@ def regrid(src: list[torch.Tensor], dst: list[torch.Tensor], rows: torch.Tensor,
         _check(load().aurora_hip_regrid(_ptr(planes[0]), F64 if dt == torch.float64 else F32, _ptr(planes[1]), len(sp),
                                         n_lat, n_lon, _ptr(rows), _ptr(row_w), n_rows, _ptr(cols), _ptr(col_w), n_cols,
                                         _stream()))
+
+
+# ---- verification sums (aurora_hip_scores) ----------------------------------------------------------------
+_PLANE_TABLES_MAX = 256
+_plane_tables: "OrderedDict[tuple, list]" = OrderedDict()   # plane addresses -> [device table, used in a captured graph]
+_plane_tables_lock = threading.Lock()
+
+
+def _plane_addresses(fields: list[torch.Tensor], n_lat: int, n_lon: int, what: str) -> list[int]:
+    """The address of every (n_lat, n_lon) plane of every tensor, in row-major order of the leading dimensions.  A plane
+    must be row-major contiguous; the leading dimensions may have any strides (history slices and other views)."""
+    out: list[int] = []
+    for v in fields:
+        assert v.dim() >= 2 and tuple(v.shape[-2:]) == (n_lat, n_lon), f"scores_sums: a {what} field is {tuple(v.shape)}, not (..., {n_lat}, {n_lon})"
+        assert v.dtype == torch.float32, f"scores_sums: {what} fields must be fp32, got {v.dtype}"
+        assert (n_lon == 1 or v.stride(-1) == 1) and (n_lat == 1 or v.stride(-2) == n_lon), \
+            f"scores_sums: the planes of a {what} field are not row-major contiguous (strides {v.stride()})"
+        base, lead, strides = v.data_ptr(), v.shape[:-2], v.stride()[:-2]
+        out += [base + 4 * sum(i * s for i, s in zip(idx, strides)) for idx in np.ndindex(*lead)]
+    return out
+
+
+def _plane_table(addresses: tuple, device: torch.device) -> torch.Tensor:
+    """Device copy of the plane-pointer arrays of a call, cached by the addresses (a roll-out scores the same buffers again
+    and again, and a captured graph must find its table alive and unchanged at every replay).  A miss uploads from pinned
+    memory without synchronising; during stream capture a miss is an error, and a table a graph uses is never evicted."""
+    key = (device.index, addresses)
+    capturing = torch.cuda.is_current_stream_capturing()
+    with _plane_tables_lock:
+        hit = _plane_tables.get(key)
+        if hit is not None:
+            _plane_tables.move_to_end(key)
+            hit[1] = hit[1] or capturing
+            return hit[0]
+    if capturing:
+        raise RuntimeError("scores_sums: call once on these tensors before capturing a graph (the plane-pointer table "
+                           "is uploaded on the first call, which a captured graph cannot replay)")
+    table = torch.tensor(addresses, dtype=torch.int64).pin_memory().to(device, non_blocking=True)
+    with _plane_tables_lock:
+        _plane_tables[key] = [table, False]
+        for old in [k for k, v in _plane_tables.items() if not v[1]][: max(0, len(_plane_tables) - _PLANE_TABLES_MAX)]:
+            del _plane_tables[old]
+    return table
+
+
+def scores_workspace_bytes(n_planes: int, n_lat: int, n_lon: int) -> int:
+    return int(load().aurora_hip_scores_workspace_bytes(n_planes, n_lat, n_lon))
+
+
+def scores_sums(pred: list[torch.Tensor], truth: list[torch.Tensor], clim: Optional[list[torch.Tensor]],
+                row_w: torch.Tensor) -> torch.Tensor:
+    """The eight verification sums (include/aurora_hip.h: count, w, w d, w d^2, w |d|, w p' t', w p'^2, w t'^2) of every
+    plane of `pred` against the same plane of `truth` (and of `clim`, or None), as an (n_planes, 8) fp64 tensor on the
+    device, in ONE aurora_hip_scores call.
+
+    pred / truth / clim: lists of fp32 (..., n_lat, n_lon) tensors on one device with row-major contiguous planes (any
+    leading strides, any 4-byte plane alignment), the same leading shapes in each list; row_w: (n_lat,) fp64 on that
+    device.  Nothing of plane size is allocated and the host does not wait for the device."""
+    assert row_w.is_cuda and row_w.dtype == torch.float64 and row_w.dim() == 1 and row_w.is_contiguous(), \
+        "scores_sums: row_w must be a contiguous fp64 vector on the device"
+    dev, n_lat = row_w.device, row_w.shape[0]
+    lists = [("prediction", pred), ("truth", truth)] + ([("climatology", clim)] if clim is not None else [])
+    assert all(len(fs) == len(pred) for _, fs in lists), "scores_sums: the lists differ in length"
+    for _, fs in lists:
+        for v, p in zip(fs, pred):
+            assert v.device == dev, "scores_sums: every tensor must be on the device of row_w"
+            assert v.shape == p.shape, f"scores_sums: shapes differ ({tuple(v.shape)} against {tuple(p.shape)})"
+    n_lon = pred[0].shape[-1] if pred else 1
+    addresses = [_plane_addresses(fs, n_lat, n_lon, what) for what, fs in lists]
+    n = len(addresses[0])
+    sums = torch.empty(n, 8, dtype=torch.float64, device=dev)
+    if n == 0:
+        return sums
+    with torch.cuda.device(dev):
+        table = _plane_table(tuple(a for row in addresses for a in row), dev)
+        workspace = torch.empty(scores_workspace_bytes(n, n_lat, n_lon), dtype=torch.uint8, device=dev)
+        base = table.data_ptr()
+        with _Timed("scores", 0.0):
+            _check(load().aurora_hip_scores(base, base + 8 * n, base + 16 * n if clim is not None else None, n, n_lat, n_lon,
+                                            _ptr(row_w), _ptr(sums), _ptr(workspace), _stream()))
+    return sums
 
 
 # ---- model handle (one forecast step behind the C ABI) ------------------------------------------------------

@@ -16,6 +16,7 @@
 #ifndef AURORA_HIP_H
 #define AURORA_HIP_H
 
+#include <stddef.h>
 #include <stdint.h>
 
 #ifdef __cplusplus
@@ -653,6 +654,35 @@ int aurora_hip_regrid_plan(const double* lat, int n_lat, const double* lon, int 
 int aurora_hip_regrid(const void* const* src_planes, int src_dtype, float* const* dst_planes, int n_planes, int n_lat,
                       int n_lon, const int32_t* rows, const double* row_w, int n_rows_out, const int32_t* cols,
                       const double* col_w, int n_cols_out, void* stream);
+
+/* ---- scoring a forecast against truth on the device (aurora_amd.scores: latitude-weighted RMSE / bias / MAE and the
+ * anomaly correlation; not in the reference) -------------------------------------------------------------------------------
+ * A plane is one variable, level and batch element: n_lat x n_lon fp32, row-major.  For every plane k < n_planes the
+ * prediction p, the truth t and, unless clim_planes is NULL, the climatology c are read once and reduced to eight fp64 sums
+ * sums[8 k + slot] over the VALID points of the plane, with the weight w = row_w[i] of the point's row i:
+ *   slot 0  1                          (the count of valid points, exact)
+ *   slot 1  w                          (the normaliser)
+ *   slot 2  w d,  d = p - t            (bias      = S2 / S1)
+ *   slot 3  w d^2                      (RMSE      = sqrt(S3 / S1))
+ *   slot 4  w |d|                      (MAE       = S4 / S1)
+ *   slot 5  w p' t',  p' = p - c, t' = t - c      (ACC = S5 / sqrt(S6 S7))
+ *   slot 6  w p'^2
+ *   slot 7  w t'^2
+ * Slots 5-7 are 0 without a climatology.  A point is valid where every input that is present (p, t and, if given, c) is
+ * finite; a plane without a valid point gives count 0 and all sums 0.  Differences and products are formed in fp64 from the
+ * fp32 inputs and accumulated in fp64.
+ * Determinism: the reduction tree is fixed (lane -> wavefront -> workgroup -> one partial per plane and row chunk in
+ * `workspace` -> partials added in chunk order by a second launch; no floating-point atomics), and the row chunks of a plane
+ * depend on n_lat and n_lon only.  The eight sums of a plane are therefore repeatable bit for bit and depend on the plane's
+ * own values, row_w, n_lat and n_lon alone: not on n_planes, on the other planes of the call, or on pointer alignment.
+ * pred_planes / truth_planes / clim_planes are DEVICE arrays of n_planes plane pointers (4-byte aligned; 16-byte loads are
+ * used where a plane's pointers and n_lon allow); row_w: n_lat device doubles; sums: n_planes x 8 device doubles; workspace:
+ * aurora_hip_scores_workspace_bytes(n_planes, n_lat, n_lon) device bytes, 8-byte aligned, no initialisation needed (0 bytes
+ * for a non-positive argument).  n_planes = 0 is a no-op.  The inputs are not modified.  Two launches, no host
+ * synchronisation, no allocation: capturable in a hipGraph. */
+size_t aurora_hip_scores_workspace_bytes(int n_planes, int n_lat, int n_lon);
+int aurora_hip_scores(const float* const* pred_planes, const float* const* truth_planes, const float* const* clim_planes,
+                      int n_planes, int n_lat, int n_lon, const double* row_w, double* sums, void* workspace, void* stream);
 
 /* ---- debugging aid ------------------------------------------------------------------------------
  * The four-wave bf16 GEMM tile with the hand-scheduled main loop (csrc/gemm_a4.hip; plain bf16 linears on 256 x 256 tiles with
