@@ -2,10 +2,12 @@
 
 Public surface = the reference's (aurora/__init__.py:3-29).  The cyclone tracker (aurora/tracker.py) follows a roll-out
 without moving the predictions off the device: only its search windows travel (aurora_amd/tracker.py).  `scores` verifies a
-prediction against truth on the device (aurora_amd/scores.py); the reference has no counterpart.
+prediction against truth on the device (aurora_amd/scores.py) and `ensemble_scores` an ensemble of them (CRPS, spread, rank
+histogram: aurora_amd/ensemble.py); the reference has no counterpart.
 """
 
 from aurora_amd.batch import Batch, Metadata
+from aurora_amd.ensemble import EnsembleScores, ensemble_scores
 from aurora_amd.model.aurora import (
     Aurora,
     Aurora12hPretrained,
@@ -35,5 +37,7 @@ __all__ = [
     "write_rollout",
     "scores",
     "Scores",
+    "ensemble_scores",
+    "EnsembleScores",
     "Tracker",
 ]

@@ -126,6 +126,9 @@ _SIGNATURES = {
                                   c_void_p, c_int, c_void_p]),
     "aurora_hip_scores_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int]),
     "aurora_hip_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "aurora_hip_ensemble_scores_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int]),
+    "aurora_hip_ensemble_scores": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -771,6 +774,52 @@ def scores_sums(pred: list[torch.Tensor], truth: list[torch.Tensor], clim: Optio
             _check(load().aurora_hip_scores(base, base + 8 * n, base + 16 * n if clim is not None else None, n, n_lat, n_lon,
                                             _ptr(row_w), _ptr(sums), _ptr(workspace), _stream()))
     return sums
+
+
+# ---- ensemble verification sums (aurora_hip_ensemble_scores) -------------------------------------------------------
+ENSEMBLE_MAX_MEMBERS = 64
+
+
+def ensemble_scores_workspace_bytes(n_members: int, n_planes: int, n_lat: int, n_lon: int) -> int:
+    return int(load().aurora_hip_ensemble_scores_workspace_bytes(n_members, n_planes, n_lat, n_lon))
+
+
+def ensemble_scores_sums(members: list[list[torch.Tensor]], truth: list[torch.Tensor],
+                         row_w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """The eight ensemble sums (include/aurora_hip.h: count, w, w e, w e^2, w |e|, w a, w g, w v) and the rank histogram of
+    every plane of M members against the same plane of `truth`, in ONE aurora_hip_ensemble_scores call: an (n_planes, 8)
+    fp64 tensor and an (n_planes, M + 2) int64 tensor (bins 0 .. M, then the ties) on the device.
+
+    members: M lists (2 <= M <= 64), each like `truth`: fp32 (..., n_lat, n_lon) tensors on one device with row-major
+    contiguous planes (any leading strides, any 4-byte plane alignment) and the leading shapes of `truth`; row_w: (n_lat,)
+    fp64 on that device.  The plane-pointer table is cached by address as in `scores_sums`.  Nothing of plane size is
+    allocated and the host does not wait for the device."""
+    assert row_w.is_cuda and row_w.dtype == torch.float64 and row_w.dim() == 1 and row_w.is_contiguous(), \
+        "ensemble_scores_sums: row_w must be a contiguous fp64 vector on the device"
+    M = len(members)
+    assert 2 <= M <= ENSEMBLE_MAX_MEMBERS, f"ensemble_scores_sums: members must hold 2..{ENSEMBLE_MAX_MEMBERS} lists, got {M}"
+    dev, n_lat = row_w.device, row_w.shape[0]
+    assert all(len(fs) == len(truth) for fs in members), "ensemble_scores_sums: the lists differ in length"
+    for fs in (truth, *members):
+        for v, t in zip(fs, truth):
+            assert v.device == dev, "ensemble_scores_sums: every tensor must be on the device of row_w"
+            assert v.shape == t.shape, f"ensemble_scores_sums: shapes differ ({tuple(v.shape)} against {tuple(t.shape)})"
+    n_lon = truth[0].shape[-1] if truth else 1
+    addresses = [_plane_addresses(fs, n_lat, n_lon, f"member {m}") for m, fs in enumerate(members)]
+    addresses.append(_plane_addresses(truth, n_lat, n_lon, "truth"))
+    n = len(addresses[-1])
+    sums = torch.empty(n, 8, dtype=torch.float64, device=dev)
+    hist = torch.empty(n, M + 2, dtype=torch.int64, device=dev)
+    if n == 0:
+        return sums, hist
+    with torch.cuda.device(dev):
+        table = _plane_table(tuple(a for row in addresses for a in row), dev)
+        workspace = torch.empty(ensemble_scores_workspace_bytes(M, n, n_lat, n_lon), dtype=torch.uint8, device=dev)
+        base = table.data_ptr()
+        with _Timed("ensemble_scores", 0.0):
+            _check(load().aurora_hip_ensemble_scores(base, base + 8 * M * n, M, n, n_lat, n_lon, _ptr(row_w), _ptr(sums),
+                                                     _ptr(hist), _ptr(workspace), _stream()))
+    return sums, hist
 
 
 # ---- model handle (one forecast step behind the C ABI) ------------------------------------------------------

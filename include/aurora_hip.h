@@ -684,6 +684,43 @@ size_t aurora_hip_scores_workspace_bytes(int n_planes, int n_lat, int n_lon);
 int aurora_hip_scores(const float* const* pred_planes, const float* const* truth_planes, const float* const* clim_planes,
                       int n_planes, int n_lat, int n_lon, const double* row_w, double* sums, void* workspace, void* stream);
 
+/* ---- scoring an ENSEMBLE against truth on the device (aurora_amd.ensemble_scores: CRPS, ensemble-mean RMSE / bias / MAE,
+ * spread, rank histogram; not in the reference) ----------------------------------------------------------------------------
+ * Planes as above.  For every plane k < n_planes the M = n_members member planes x_1 .. x_M and the truth plane y are read once.
+ * A point is VALID where y and all M members are finite.  Everything is formed in fp64 from the differences to truth,
+ * d_m = (double)x_m - (double)y (never from the raw values), per valid point, with the weight w = row_w[i] of the point's row:
+ *   per point                                                                    sums[8 k + slot] = sum over valid points of
+ *   slot 0                                                                       1   (the count, exact)
+ *   slot 1                                                                       w
+ *   slot 2  e = (sum_m d_m) / M, members added in member order                   w e     (bias = S2 / S1)
+ *   slot 3                                                                       w e^2   (RMSE of the ensemble mean = sqrt(S3 / S1))
+ *   slot 4                                                                       w |e|   (MAE of the ensemble mean = S4 / S1)
+ *   slot 5  a = (sum_m |d_m|) / M                                                w a
+ *   slot 6  g = (1 / M^2) sum_i sum_j |d_i - d_j|
+ *             = (2 / M^2) sum_k (2 k - M - 1) d_(k),  d_(1) <= ... <= d_(M)      w g
+ *   slot 7  v = sum_m (d_m - e)^2 / (M - 1)                                      w v
+ * so that CRPS = (S5 - S6 / 2) / S1, fair CRPS = (S5 - (S6 / 2) M / (M - 1)) / S1, spread = sqrt(S7 / S1) and
+ * spread / skill = sqrt((M + 1) / M) spread / RMSE.  (The kernel takes g in the sorted form and multiplies by 1 / M, 2 / M^2
+ * and 1 / (M - 1) rounded to fp64; a, g and the counts are formed from the sorted members and do not depend on their order.)
+ * hist[(M + 2) k + b] for b <= M is the rank histogram: the number of valid points with exactly b members BELOW the truth
+ * (x_m < y, compared as fp32, unweighted); hist[(M + 2) k + M + 1] is the number of valid points with some x_m == y (ties:
+ * where a bounded variable sits on its bound the low bins mean little).  All counts are exact; the bins add up to slot 0.
+ * A plane without a valid point gives zeros throughout.
+ * Determinism as above: a fixed tree (lane -> wavefront -> workgroup -> one partial per plane and row chunk in `workspace`
+ * -> partials added in chunk order by a second launch), no atomics; the row chunks of a plane depend on n_lat, n_lon and the
+ * member-count bucket (4, 8, 16, 32, 64: the smallest that holds M) only, so the results of a plane are repeatable bit for
+ * bit and depend on its own values, row_w, M, n_lat and n_lon alone.
+ * member_planes: DEVICE array of n_members x n_planes plane pointers, member-major (member m, plane k at [m n_planes + k]);
+ * truth_planes: n_planes pointers (all 4-byte aligned; 16-byte loads are used for M <= 16 where every pointer of a plane and
+ * n_lon allow).  2 <= n_members <= 64.  row_w: n_lat device doubles; sums: n_planes x 8 device doubles; hist: n_planes x
+ * (n_members + 2) device int64; workspace: what the _workspace_bytes function returns for the same sizes, 8-byte aligned, no
+ * initialisation needed (0 bytes for an argument out of range).  n_planes = 0 is a no-op.  The inputs are not modified.  Two
+ * launches, no host synchronisation, no allocation: capturable in a hipGraph. */
+size_t aurora_hip_ensemble_scores_workspace_bytes(int n_members, int n_planes, int n_lat, int n_lon);
+int aurora_hip_ensemble_scores(const float* const* member_planes, const float* const* truth_planes, int n_members, int n_planes,
+                               int n_lat, int n_lon, const double* row_w, double* sums, int64_t* hist, void* workspace,
+                               void* stream);
+
 /* ---- debugging aid ------------------------------------------------------------------------------
  * The four-wave bf16 GEMM tile with the hand-scheduled main loop (csrc/gemm_a4.hip; plain bf16 linears on 256 x 256 tiles with
  * K >= AURORA_GEMM_A4_MIN_K, a read-once process default) can leave s_memtime stamps of workgroups 0 and 255 in 8 x 8 device
