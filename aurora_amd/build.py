@@ -16,7 +16,7 @@ from pathlib import Path
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "_lib" / "libaurora_hip.so"
-SOURCES = ("runtime.hip", "gemm.hip", "gemm_a4.hip", "attention.hip", "norm.hip", "embed.hip", "perceiver_out.hip", "band.hip",
+SOURCES = ("runtime.hip", "gemm.hip", "gemm_f32.hip", "gemm_ln512.hip", "gemm_a4.hip", "attention.hip", "norm.hip", "embed.hip", "perceiver_out.hip", "band.hip",
            "model.hip", "step.hip", "regrid.hip", "scores.hip", "ensemble_scores.hip")
 ARCH = "gfx950"
 
@@ -32,8 +32,7 @@ def is_stale() -> bool:
     if not LIB.exists():
         return True
     built = LIB.stat().st_mtime
-    deps = [CSRC / s for s in SOURCES] + [CSRC / "common.h", CSRC / "band.h", CSRC / "model.h", CSRC / "gemm_a4_loop.inc",
-                                          PKG.parent / "include" / "aurora_hip.h"]
+    deps = [d for pat in ("*.hip", "*.h", "*.inc") for d in CSRC.glob(pat)] + [PKG.parent / "include" / "aurora_hip.h"]
     return any(d.stat().st_mtime > built for d in deps)
 
 
@@ -48,7 +47,8 @@ def build_library(force: bool = False, verbose: bool = True) -> Path:
         obj = LIB.parent / (src.replace(".hip", ".o"))
         # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in arch VGPRs (gfx950 has one unified file);
         # otherwise the softmax in the attention kernel pays a v_accvgpr_read per score.
-        # (AURORA_BUILD_FLAGS: extra compiler flags of a probe build, e.g. -DA4_EXPERIMENTS for tools/gemm_a4_stamps.py)
+        # (AURORA_BUILD_FLAGS: extra compiler flags of a probe build, e.g. -DA4_EXPERIMENTS for tools/gemm_a4_stamps.py --
+        #  after `python tools/gen_gemm_asm.py 1 2 3` has written the gemm_a4_loop_v<N>.inc that build includes)
         cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-mllvm",
                "-amdgpu-mfma-vgpr-form=1", *os.environ.get("AURORA_BUILD_FLAGS", "").split(), "-c", str(CSRC / src), "-o", str(obj)]
         if verbose:

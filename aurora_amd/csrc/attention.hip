@@ -463,12 +463,9 @@ extern "C" int aurora_hip_window_attention_planes(const void* qkv, int64_t plane
       hipLaunchKernelGGL((window_attention_bf16<true, 2>), dim3((unsigned)blocks), dim3(192), 0, as_stream(stream), p);
   } else {
     const size_t lds = 2 * MAXN * HD * 4 + MAXN * 4 + MAXN + 16;
-    static bool attr_done_dev[64] = {false};   // function attributes are per device
-    bool& attr_done = attr_done_dev[current_device() & 63];
-    if (!attr_done) {
+    once_per_device([&] {
       (void)hipFuncSetAttribute((const void*)window_attention_f32, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-      attr_done = true;
-    }
+    });
     hipLaunchKernelGGL(window_attention_f32, dim3((unsigned)blocks), dim3(192), lds, as_stream(stream), p);
   }
   return check_launch("window_attention");

@@ -27,6 +27,18 @@ int device_cus();
 // Index of the current device, for per-device one-time setup (function attributes).
 int current_device();
 
+// Runs `set` -- the hipFuncSetAttribute calls of one launch site -- the first time that site is reached on each device
+// (function attributes are per device; every lambda is its own type, so every site gets its own flags).
+template <typename F>
+inline void once_per_device(F&& set) {
+  static bool attr_done_dev[64] = {false};
+  bool& done = attr_done_dev[current_device() & 63];
+  if (!done) {
+    set();
+    done = true;
+  }
+}
+
 // ---- bf16 <-> fp32 (raw uint16 storage, round-to-nearest-even) ---------------------------------
 typedef uint16_t bf16_t;
 
@@ -63,7 +75,7 @@ typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
 typedef float f32x2_t __attribute__((ext_vector_type(2)));
 
-// Two-term fp16 split of a pair of fp32 values (gemm.hip, "second variant"): h = fp16(a), l = fp16(a - h), packed two to a
+// Two-term fp16 split of a pair of fp32 values (gemm_f32.hip, "second variant"): h = fp16(a), l = fp16(a - h), packed two to a
 // register.  Shared by every kernel that produces the fp16-pair layout, so that a split is the same wherever it happens.
 // (The remainder could come from one mixed-precision FMA per value -- v_fma_mixlo/hi_f16: widen, subtract and round in
 // one instruction, 3 operations per pair instead of 5.  Measured: no gain in the in-phase kernel, -15 % in the ping-pong

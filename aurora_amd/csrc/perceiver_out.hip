@@ -9,7 +9,7 @@
 // fp32-equivalent) and take the 13 x 48 convex combinations per column in registers.  Two kernels:
 //
 //   perceiver_probs_kernel   per (column, head): the 13 x 3 softmax weights p (fp32) -> P[col][head] (16 pairs, see there), and
-//                            the column's value rows re-written in the fp16-pair layout of the two-term GEMMs (gemm.hip,
+//                            the column's value rows re-written in the fp16-pair layout of the two-term GEMMs (gemm_f32.hip,
 //                            "The fp16-pair layout") -> Vp[col * 3 + j][inner].  HBM-bound: reads k | v once.
 //   perceiver_out_kernel     U_h = Vp_h . W_out_h^T on the matrix pipe (two fp16 terms, three MFMAs per product, weights
 //                            pre-split and scaled by 2^6 as everywhere), out[l] += p[l,h,j] U_h[j] on the VALU, 16 heads,
@@ -591,14 +591,11 @@ extern "C" int aurora_hip_perceiver_out(const void* Vp, const void* W_pairs, int
                 guard, guard_limit};
   p.n_blocks = ((n_cols + PO_COLS - 1) / PO_COLS) * p.tiles_n;
   AURORA_CHECK_ARG(p.n_blocks < (int64_t)1 << 31, "perceiver_out: too many tiles");
-  static bool attr_done_dev[64] = {false};
-  bool& attr_done = attr_done_dev[current_device() & 63];
-  if (!attr_done) {
+  once_per_device([] {
     (void)hipFuncSetAttribute((const void*)perceiver_out_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, PO_LDS_LAUNCH);
     (void)hipFuncSetAttribute((const void*)perceiver_out_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, PO_LDS_LAUNCH);
     (void)hipFuncSetAttribute((const void*)perceiver_out_kernel<13>, hipFuncAttributeMaxDynamicSharedMemorySize, PO_LDS_LAUNCH);
-    attr_done = true;
-  }
+  });
   const dim3 grid((unsigned)p.n_blocks), block(PO_THREADS);
   switch (Lq) {
     case 3: hipLaunchKernelGGL(perceiver_out_kernel<3>, grid, block, PO_LDS_LAUNCH, as_stream(stream), p); break;

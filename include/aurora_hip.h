@@ -721,12 +721,6 @@ int aurora_hip_ensemble_scores(const float* const* member_planes, const float* c
                                int n_lat, int n_lon, const double* row_w, double* sums, int64_t* hist, void* workspace,
                                void* stream);
 
-/* ---- debugging aid ------------------------------------------------------------------------------
- * The four-wave bf16 GEMM tile with the hand-scheduled main loop (csrc/gemm_a4.hip; plain bf16 linears on 256 x 256 tiles with
- * K >= AURORA_GEMM_A4_MIN_K, a read-once process default) can leave s_memtime stamps of workgroups 0 and 255 in 8 x 8 device
- * words -- per wave: kernel start, loop start, loop end, 64-wide K units, kernel end -- for tools/gemm_a4_stamps.py.  NULL switches it off. */
-void aurora_hip_debug_a4_stamps(void* device_words);
-
 #ifdef __cplusplus
 }
 #endif

@@ -4,6 +4,13 @@ fp32 kernels are held to fp32-roundoff tolerances against fp64 torch-CPU evaluat
 kernels are compared, on bf16-rounded inputs, against fp64 evaluations of the same rounded
 inputs (so only accumulation order and the output rounding differ).
 """
+import hashlib
+import json
+import os
+import subprocess
+import sys
+from pathlib import Path
+
 import numpy as np
 import pytest
 import torch
@@ -344,6 +351,54 @@ def test_linear_bf16(M, N, K, act):
     # fp32 copy: exact products, fp32 accumulation; the bf16 kernel's GELU uses a 4e-7-accurate erf
     assert relerr(out2, ref) < (5e-6 if act == 0 else 2e-5)
     assert relerr(out.float(), ref) < 5e-3    # bf16 copy: one rounding
+
+
+def four_wave_case_digests():
+    """SHA-256 of every result of a handful of bf16 linears that reach the four-wave kernel when AURORA_GEMM_A4_MIN_K allows it
+    (M >= 1024, N % 256 == 0, K % 64 == 0, K >= 256) and that the tile cost model keeps on 256 x 256 tiles on a 256-CU device:
+    256 tiles (one full round), K >= 512, and the 768 tiles of the stage-1 qkv shape.  M = 8100 and 16200 end in ragged tiles."""
+    L = lib()
+    digest = lambda t: hashlib.sha256(t.contiguous().view(torch.uint8).cpu().numpy().tobytes()).hexdigest()  # noqa: E731
+    out = {}
+    for M, N, K, act, general in [(8100, 2048, 512, 0, False), (8100, 2048, 1024, 1, False),     # whole-row epilogue
+                                  (8100, 2048, 1024, 1, True), (8192, 2048, 512, 0, True)]:      # general epilogue
+        a = rnd(M, K, seed=1).bfloat16().to(DEV)
+        w = rnd(N, K, seed=2, scale=K ** -0.5).bfloat16().to(DEV)
+        b = rnd(N, seed=3).float().to(DEV)
+        c = torch.zeros((M, N), dtype=torch.bfloat16, device=DEV)
+        c2 = torch.zeros((M, N), device=DEV) if general else None
+        r = rnd(M, N, seed=4).float().to(DEV) if general and act else None   # (second output + residual, second output alone)
+        L.linear(a, w, b, c, out2=c2, residual=r, act=act)
+        torch.cuda.synchronize()
+        out[f"linear {M}x{N}x{K} act={act} general={general}"] = digest(c)
+        if general:
+            out[f"linear {M}x{N}x{K} act={act} second output"] = digest(c2)
+    M, heads, K = 16200, 16, 1024
+    a = rnd(M, K, seed=5).bfloat16().to(DEV)
+    w = rnd(3 * 64 * heads, K, seed=6, scale=K ** -0.5).bfloat16().to(DEV)
+    b = rnd(3 * 64 * heads, seed=7).float().to(DEV)
+    planes = torch.zeros((heads, M, 3, 64), dtype=torch.bfloat16, device=DEV)
+    L.linear_planes(a, w, b, planes)
+    torch.cuda.synchronize()
+    out[f"linear_planes {M}x{heads} heads x{K}"] = digest(planes)
+    return out
+
+
+def test_linear_bf16_four_wave_kernel_equals_the_eight_wave_kernels():
+    """linear_kernel_256a4 (gemm_a4.hip) accumulates K in the same 32-wide steps and runs the same epilogues as the eight-wave
+    kernels: bit-identical results.  AURORA_GEMM_A4_MIN_K is read once per process, so the four-wave leg is ONE fresh child
+    process under a time limit; this process computes the same linears with the default (eight-wave) dispatch."""
+    root = Path(__file__).resolve().parents[1]
+    code = (f"import json, sys; sys.path.insert(0, {str(root)!r}); from tests import test_gpu_ops as t; "
+            "print('DIGESTS ' + json.dumps(t.four_wave_case_digests()))")
+    res = subprocess.run([sys.executable, *(["-s"] if sys.flags.no_user_site else []), "-c", code],
+                         env={**os.environ, "AURORA_GEMM_A4_MIN_K": "64"}, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, (res.returncode, res.stderr[-2000:])
+    four = json.loads(next(l for l in res.stdout.splitlines() if l.startswith("DIGESTS "))[8:])
+    eight = four_wave_case_digests()
+    assert len(four) == 7 and four.keys() == eight.keys()
+    for name in eight:
+        assert four[name] == eight[name], name
 
 
 @pytest.mark.parametrize("M,N,K,split", [(2160, 2048, 8192, 0), (2160, 2048, 8192, 2), (2160, 2048, 8192, 3), (2160, 2048, 8192, 5),

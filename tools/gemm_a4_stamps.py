@@ -1,6 +1,9 @@
 """Cycles per MFMA of the hand-scheduled loop of linear_kernel_256a4 (csrc/gemm_a4.hip) from its own s_memtime stamps, next to
 the launch's wall-clock rate and the eight-wave ping-pong kernel's on the same operands; results compared bit for bit.
-    AURORA_GEMM_A4_MIN_K is set by this script per leg (separate processes: the default is read once)."""
+    AURORA_GEMM_A4_MIN_K is set by this script per leg (separate processes: the default is read once).
+    Needs the probe build of the library (the stamps and the variants exist only there):
+        python tools/gen_gemm_asm.py 1 2 3 && AURORA_BUILD_FLAGS=-DA4_EXPERIMENTS python -m aurora_amd.build --force"""
+import ctypes
 import os
 import subprocess
 import sys
@@ -19,7 +22,12 @@ if len(sys.argv) > 1 and sys.argv[1] == "leg":
     a4 = int(os.environ["AURORA_GEMM_A4_MIN_K"]) > 0
     stamps = torch.zeros(64, dtype=torch.int64, device="cuda")
     if a4:
-        lib.load().aurora_hip_debug_a4_stamps(stamps.data_ptr())
+        try:
+            set_stamps = lib.load().aurora_hip_debug_a4_stamps   # not in include/aurora_hip.h: declared here
+        except AttributeError:
+            sys.exit("aurora_hip_debug_a4_stamps is missing: this library is not an A4_EXPERIMENTS build (see the docstring)")
+        set_stamps.restype, set_stamps.argtypes = None, [ctypes.c_void_p]
+        set_stamps(stamps.data_ptr())
     for name, M, N, K in SHAPES:
         g = torch.Generator(device="cuda").manual_seed(1)
         a = (torch.rand(M, K, device="cuda", generator=g) * 2 - 1).bfloat16()
