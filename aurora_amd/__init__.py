@@ -3,7 +3,8 @@
 Public surface = the reference's (aurora/__init__.py:3-29).  The cyclone tracker (aurora/tracker.py) follows a roll-out
 without moving the predictions off the device: only its search windows travel (aurora_amd/tracker.py).  `scores` verifies a
 prediction against truth on the device (aurora_amd/scores.py) and `ensemble_scores` an ensemble of them (CRPS, spread, rank
-histogram: aurora_amd/ensemble.py); the reference has no counterpart.
+histogram: aurora_amd/ensemble.py), and `spectra` gives the zonal power spectra of a prediction, of the truth and of the error
+(aurora_amd/spectra.py); the reference has no counterpart.
 """
 
 from aurora_amd.batch import Batch, Metadata
@@ -20,6 +21,7 @@ from aurora_amd.model.aurora import (
 )
 from aurora_amd.rollout import rollout, write_rollout
 from aurora_amd.scores import Scores, scores
+from aurora_amd.spectra import Spectra, spectra
 from aurora_amd.tracker import Tracker
 
 __all__ = [
@@ -39,5 +41,7 @@ __all__ = [
     "Scores",
     "ensemble_scores",
     "EnsembleScores",
+    "spectra",
+    "Spectra",
     "Tracker",
 ]

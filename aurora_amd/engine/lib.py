@@ -129,6 +129,9 @@ _SIGNATURES = {
     "aurora_hip_ensemble_scores_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int]),
     "aurora_hip_ensemble_scores": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p]),
+    "aurora_hip_spectra_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "aurora_hip_spectra": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                   c_void_p, ctypes.c_size_t, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -820,6 +823,76 @@ def ensemble_scores_sums(members: list[list[torch.Tensor]], truth: list[torch.Te
             _check(load().aurora_hip_ensemble_scores(base, base + 8 * M * n, M, n, n_lat, n_lon, _ptr(row_w), _ptr(sums),
                                                      _ptr(hist), _ptr(workspace), _stream()))
     return sums, hist
+
+
+# ---- zonal power spectra (aurora_hip_spectra) -------------------------------------------------------------------------
+SPECTRA_MAX_BANDS, SPECTRA_MAX_LON = 8, 4096
+_twiddles: dict[tuple, torch.Tensor] = {}     # (n_lon, device) -> (n_lon, 2) fp64 device table
+_twiddles_lock = threading.Lock()
+
+
+def spectra_twiddle(n_lon: int, device: torch.device) -> torch.Tensor:
+    """(n_lon, 2) fp64 on `device`: cos(2 pi m / n_lon), sin(2 pi m / n_lon), computed on the host in fp64 and kept per
+    (n_lon, device)."""
+    key = (int(n_lon), str(device))
+    with _twiddles_lock:
+        hit = _twiddles.get(key)
+    if hit is None:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("spectra_power: call once for this n_lon before capturing a graph (the twiddle table is "
+                               "uploaded on the first call, which a captured graph cannot replay)")
+        a = 2.0 * np.pi * np.arange(n_lon, dtype=np.float64) / n_lon
+        hit = torch.from_numpy(np.stack([np.cos(a), np.sin(a)], axis=1)).pin_memory().to(device, non_blocking=True)
+        with _twiddles_lock:
+            if len(_twiddles) >= 64:
+                _twiddles.clear()
+            _twiddles[key] = hit
+    return hit
+
+
+def spectra_workspace_bytes(n_planes: int, n_lat: int, n_lon: int, n_bands: int, has_truth: bool) -> int:
+    return int(load().aurora_hip_spectra_workspace_bytes(n_planes, n_lat, n_lon, n_bands, 1 if has_truth else 0))
+
+
+def spectra_power(pred: list[torch.Tensor], truth: Optional[list[torch.Tensor]],
+                  band_w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
+    """Band-mean zonal power spectra (include/aurora_hip.h) of every plane of `pred` (and of the same plane of `truth` and of
+    pred - truth, unless `truth` is None), in ONE aurora_hip_spectra call: an (n_planes, 1 or 3, n_bands, n_lon // 2 + 1)
+    fp64 tensor and the (n_planes, n_bands) int64 counts of valid rows, on the device.
+
+    pred / truth: lists of fp32 (..., n_lat, n_lon) tensors on one device with row-major contiguous planes (any leading
+    strides, any 4-byte plane alignment), the same leading shapes in each list; band_w: (n_bands, n_lat) fp64 on that
+    device, the row weight inside the band and 0 outside.  The plane-pointer table is cached by address as in `scores_sums`,
+    the twiddle table per n_lon; the only temporary is the workspace of partials.  The host does not wait for the device."""
+    assert band_w.is_cuda and band_w.dtype == torch.float64 and band_w.dim() == 2 and band_w.is_contiguous(), \
+        "spectra_power: band_w must be a contiguous (n_bands, n_lat) fp64 matrix on the device"
+    dev, (n_bands, n_lat) = band_w.device, band_w.shape
+    assert 1 <= n_bands <= SPECTRA_MAX_BANDS, f"spectra_power: 1..{SPECTRA_MAX_BANDS} bands, got {n_bands}"
+    lists = [("prediction", pred)] + ([("truth", truth)] if truth is not None else [])
+    assert all(len(fs) == len(pred) for _, fs in lists), "spectra_power: the lists differ in length"
+    for _, fs in lists:
+        for v, p in zip(fs, pred):
+            assert v.device == dev, "spectra_power: every tensor must be on the device of band_w"
+            assert v.shape == p.shape, f"spectra_power: shapes differ ({tuple(v.shape)} against {tuple(p.shape)})"
+    n_lon = pred[0].shape[-1] if pred else 2
+    assert 2 <= n_lon <= SPECTRA_MAX_LON, f"spectra_power: n_lon must be in 2..{SPECTRA_MAX_LON}, got {n_lon}"
+    addresses = [_plane_addresses(fs, n_lat, n_lon, what) for what, fs in lists]
+    n, F, K = len(addresses[0]), len(lists) * 2 - 1, n_lon // 2 + 1
+    power = torch.empty(n, F, n_bands, K, dtype=torch.float64, device=dev)
+    rows = torch.empty(n, n_bands, dtype=torch.int64, device=dev)
+    if n == 0:
+        return power, rows
+    with torch.cuda.device(dev):
+        table = _plane_table(tuple(a for row in addresses for a in row), dev)
+        twiddle = spectra_twiddle(n_lon, dev)
+        nbytes = spectra_workspace_bytes(n, n_lat, n_lon, n_bands, truth is not None)
+        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)   # (from torch's caching allocator: no hipMalloc warm)
+        base = table.data_ptr()
+        with _Timed("spectra", 2.0 * (len(lists) * n * n_lat) * K * (2 * K)):   # folded transform: K products per output
+            _check(load().aurora_hip_spectra(base, base + 8 * n if truth is not None else None, n, n_lat, n_lon, n_bands,
+                                             _ptr(band_w), _ptr(twiddle), _ptr(power), _ptr(rows), _ptr(workspace), nbytes,
+                                             _stream()))
+    return power, rows
 
 
 # ---- model handle (one forecast step behind the C ABI) ------------------------------------------------------

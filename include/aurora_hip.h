@@ -721,6 +721,35 @@ int aurora_hip_ensemble_scores(const float* const* member_planes, const float* c
                                int n_lat, int n_lon, const double* row_w, double* sums, int64_t* hist, void* workspace,
                                void* stream);
 
+/* ---- zonal power spectra of a forecast on the device (aurora_amd.spectra; not in the reference) ---------------------------
+ * Planes as above, N = n_lon, K = N / 2 + 1 wavenumbers.  For row i of a plane
+ *   X_i[k] = sum_n x_i[n] exp(-2 pi i k n / N),  k = 0 .. K-1,        P_i[k] = c_k |X_i[k]|^2 / N^2,
+ * with c_0 = 1, c_{N/2} = 1 for an even N and c_k = 2 otherwise, so that sum_k P_i[k] = mean_n x_i[n]^2.  A row is VALID when
+ * all N values of every input present (pred and, unless truth_planes is NULL, truth) are finite; validity is decided from the
+ * inputs.  band_w is n_bands x n_lat device doubles: the weight w_i of row i in band b, 0 where the row is outside the band
+ * (a row belongs to band b exactly where band_w[b n_lat + i] > 0).  For every plane, field and band
+ *   power[((plane F + f) n_bands + b) K + k] = sum_{i valid, i in b} w_i P_i[k] / sum_{i valid, i in b} w_i,
+ *   rows[plane n_bands + b]                  = the number of valid rows in band b;  a band without one gives NaN and 0.
+ * F = 1 without a truth (f = 0: pred); F = 3 with one (f = 0 pred, 1 truth, 2 the error pred - truth, formed in fp64 as
+ * X_pred - X_truth).  Everything is fp64: the fp32 values are converted exactly, folded (x[n] +- x[N - n], one rounding per
+ * pair) and multiplied on the fp64 matrix pipe (v_mfma_f64_16x16x4_f64) against cosines and sines taken from `twiddle`,
+ * accumulating over longitude in ascending order.  twiddle: 2 N device doubles, twiddle[2 m] = cos(2 pi m / N),
+ * twiddle[2 m + 1] = sin(2 pi m / N), m = 0 .. N-1, computed by the caller in fp64.
+ * Determinism: a fixed tree (MFMA accumulator over longitude -> the rows of a 16-row tile in a fixed order -> one partial per
+ * plane and chunk of 32 grid rows in `workspace`, filled tile by tile by the lane that owns the value -> partials added in
+ * chunk order by a second launch; no floating-point atomics).  A plane's spectrum is repeatable bit for bit and depends on its
+ * own values, band_w, n_lat, n_lon and the presence of a truth alone: not on n_planes, on the other planes of the call, or on
+ * pointer alignment (4-byte aligned plane pointers; every load of a plane is a 4-byte load).
+ * 2 <= n_lon <= 4096, 1 <= n_bands <= 8.  workspace: the only temporary,
+ *   n_planes x ceil(n_lat / 32) x (F n_bands K + 2 n_bands) doubles = aurora_hip_spectra_workspace_bytes(...) bytes
+ * (0 for an argument out of range), 8-byte aligned, no initialisation needed; workspace_bytes is what the caller lends and is
+ * checked.  n_planes = 0 is a no-op.  The inputs are not modified.  Two launches, no host synchronisation, no allocation, no
+ * environment variable: capturable in a hipGraph. */
+size_t aurora_hip_spectra_workspace_bytes(int n_planes, int n_lat, int n_lon, int n_bands, int has_truth);
+int aurora_hip_spectra(const float* const* pred_planes, const float* const* truth_planes, int n_planes, int n_lat, int n_lon,
+                       int n_bands, const double* band_w, const double* twiddle, double* power, int64_t* rows, void* workspace,
+                       size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
