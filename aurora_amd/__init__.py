@@ -4,11 +4,13 @@ Public surface = the reference's (aurora/__init__.py:3-29).  The cyclone tracker
 without moving the predictions off the device: only its search windows travel (aurora_amd/tracker.py).  `scores` verifies a
 prediction against truth on the device (aurora_amd/scores.py) and `ensemble_scores` an ensemble of them (CRPS, spread, rank
 histogram: aurora_amd/ensemble.py), and `spectra` gives the zonal power spectra of a prediction, of the truth and of the error
-(aurora_amd/spectra.py); the reference has no counterpart.
+(aurora_amd/spectra.py), and `event_scores` the contingency tables and the fractions skill score of threshold exceedances
+(aurora_amd/events.py); the reference has no counterpart.
 """
 
 from aurora_amd.batch import Batch, Metadata
 from aurora_amd.ensemble import EnsembleScores, ensemble_scores
+from aurora_amd.events import EventScores, event_scores
 from aurora_amd.model.aurora import (
     Aurora,
     Aurora12hPretrained,
@@ -43,5 +45,7 @@ __all__ = [
     "EnsembleScores",
     "spectra",
     "Spectra",
+    "event_scores",
+    "EventScores",
     "Tracker",
 ]

@@ -132,6 +132,9 @@ _SIGNATURES = {
     "aurora_hip_spectra_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "aurora_hip_spectra": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, ctypes.c_size_t, c_void_p]),
+    "aurora_hip_event_scores_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "aurora_hip_event_scores": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
+                                        c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -893,6 +896,55 @@ def spectra_power(pred: list[torch.Tensor], truth: Optional[list[torch.Tensor]],
                                              _ptr(band_w), _ptr(twiddle), _ptr(power), _ptr(rows), _ptr(workspace), nbytes,
                                              _stream()))
     return power, rows
+
+
+# ---- events: contingency tables and fractions skill score (aurora_hip_event_scores) -----------------------------------
+EVENT_MAX_THRESHOLDS, EVENT_MAX_SCALES, EVENT_MAX_SCALE, EVENT_MAX_LON = 8, 8, 63, 4096
+
+
+def event_scores_workspace_bytes(n_planes: int, n_lat: int, n_lon: int, n_thresholds: int, n_scales: int) -> int:
+    return int(load().aurora_hip_event_scores_workspace_bytes(n_planes, n_lat, n_lon, n_thresholds, n_scales))
+
+
+def event_rowsums(pred: list[torch.Tensor], truth: list[torch.Tensor], thresholds: torch.Tensor, scales,
+                  below: bool = False) -> tuple[torch.Tensor, torch.Tensor]:
+    """The integer row sums of include/aurora_hip.h (sum (cf - co)^2, sum cf^2, sum co^2 over the valid points of every row)
+    of every plane of `pred` against the same plane of `truth`, for every threshold and window size, in ONE
+    aurora_hip_event_scores call: an (n_planes, T, S, n_lat, 3) int64 tensor and the (n_planes, n_lat) int64 counts of valid
+    points, on the device.
+
+    pred / truth: lists of fp32 (..., n_lat, n_lon) tensors on one device with row-major contiguous planes (any leading
+    strides, any 4-byte plane alignment), the same leading shapes in each list; thresholds: contiguous (n_planes, T) fp32 on
+    that device (NaN: no event); scales: odd, ascending, distinct window sizes starting with 1, each <= 63 and <= n_lon.
+    The plane-pointer table is cached by address as in `scores_sums`.  Nothing of plane size is allocated and the host does
+    not wait for the device."""
+    assert thresholds.is_cuda and thresholds.dtype == torch.float32 and thresholds.dim() == 2 and thresholds.is_contiguous(), \
+        "event_rowsums: thresholds must be a contiguous (n_planes, T) fp32 matrix on the device"
+    dev, (n_thr_planes, T) = thresholds.device, thresholds.shape
+    scales = [int(n) for n in scales]
+    S = len(scales)
+    assert 1 <= T <= EVENT_MAX_THRESHOLDS, f"event_rowsums: 1..{EVENT_MAX_THRESHOLDS} thresholds, got {T}"
+    assert 1 <= S <= EVENT_MAX_SCALES, f"event_rowsums: 1..{EVENT_MAX_SCALES} scales, got {S}"
+    assert len(truth) == len(pred) and pred, "event_rowsums: the lists differ in length or are empty"
+    for v, p in zip(truth, pred):
+        assert v.device == dev and p.device == dev, "event_rowsums: every tensor must be on the device of thresholds"
+        assert v.shape == p.shape, f"event_rowsums: shapes differ ({tuple(v.shape)} against {tuple(p.shape)})"
+    n_lat, n_lon = pred[0].shape[-2:]
+    addresses = [_plane_addresses(fs, n_lat, n_lon, what) for what, fs in (("prediction", pred), ("truth", truth))]
+    n = len(addresses[0])
+    assert n == n_thr_planes, f"event_rowsums: {n} planes but thresholds for {n_thr_planes}"
+    rowsums = torch.empty(n, T, S, n_lat, 3, dtype=torch.int64, device=dev)
+    valid = torch.empty(n, n_lat, dtype=torch.int64, device=dev)
+    if n == 0:
+        return rowsums, valid
+    host_scales = (c_int32 * S)(*scales)
+    with torch.cuda.device(dev):
+        table = _plane_table(tuple(a for row in addresses for a in row), dev)
+        base = table.data_ptr()
+        with _Timed("event_scores", 0.0):
+            _check(load().aurora_hip_event_scores(base, base + 8 * n, n, n_lat, n_lon, _ptr(thresholds), T, host_scales, S,
+                                                  1 if below else 0, _ptr(rowsums), _ptr(valid), None, 0, _stream()))
+    return rowsums, valid
 
 
 # ---- model handle (one forecast step behind the C ABI) ------------------------------------------------------

@@ -750,6 +750,33 @@ int aurora_hip_spectra(const float* const* pred_planes, const float* const* trut
                        int n_bands, const double* band_w, const double* twiddle, double* power, int64_t* rows, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* ---- events: contingency tables and the Fractions Skill Score on the device (aurora_amd.event_scores; not in the reference)
+ * Planes as above.  A point (i, j) is VALID where pred and truth are both finite.  For plane k, threshold
+ * thr = thresholds[k T + t] (fp32, compared in fp32) and the odd window size n = scales[s] = 2 h + 1:
+ *   f(i,j) = valid && pred >= thr,   o(i,j) = valid && truth >= thr     (both <= with below != 0; a NaN threshold: no event)
+ *   cf(i,j) = sum_{|di| <= h, |dj| <= h} f(i + di, (j + dj) mod n_lon),  co likewise:
+ * periodic in longitude, rows outside [0, n_lat) and invalid points count 0.  Summed over the VALID centre columns j of row i:
+ *   rowsums[(((k T + t) S + s) n_lat + i) 3 + 0] = sum_j (cf - co)^2
+ *   rowsums[(((k T + t) S + s) n_lat + i) 3 + 1] = sum_j cf^2
+ *   rowsums[(((k T + t) S + s) n_lat + i) 3 + 2] = sum_j co^2
+ *   valid[k n_lat + i]                           = the number of valid points of row i.
+ * At n = 1 these are the contingency table of the row: hits = (Bf + Bo - A) / 2, false alarms = Bf - hits, misses = Bo - hits.
+ * Everything is an integer and exact (an entry < 4096 x 63^4 < 2^36): the result does not depend on the order of additions,
+ * is repeatable bit for bit, and a plane's numbers depend on its own values and thresholds alone -- not on n_planes, on the
+ * other planes, or on pointer alignment (4-byte aligned plane pointers; every load of a plane is a 4-byte load).
+ * thresholds: n_planes x T DEVICE floats; scales: S HOST int32, odd, ascending, distinct, scales[0] == 1, each <= 63 and
+ * <= n_lon.  1 <= T <= 8, 1 <= S <= 8, 1 <= n_lon <= 4096.  rowsums: n_planes x T x S x n_lat x 3 device int64; valid:
+ * n_planes x n_lat device int64; both 8-byte aligned, no initialisation needed.
+ * The call needs NO workspace: aurora_hip_event_scores_workspace_bytes returns 0 for every argument, `workspace` may be NULL
+ * and workspace_bytes 0 (the tables are cleared by a first small launch and filled by 64-bit integer vector atomics).  Arguments are
+ * checked before anything is enqueued (AURORA_E_ARG and aurora_hip_last_error()).  n_planes = 0 is a no-op.  The inputs are not
+ * modified.  Two launches, no host synchronisation, no allocation, no environment variable: capturable in a
+ * hipGraph. */
+size_t aurora_hip_event_scores_workspace_bytes(int n_planes, int n_lat, int n_lon, int n_thresholds, int n_scales);
+int aurora_hip_event_scores(const float* const* pred_planes, const float* const* truth_planes, int n_planes, int n_lat,
+                            int n_lon, const float* thresholds, int n_thresholds, const int32_t* scales, int n_scales, int below,
+                            int64_t* rowsums, int64_t* valid, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
