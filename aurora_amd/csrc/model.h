@@ -296,32 +296,62 @@ void timed(Model& m, void* stream, int kind, double work, F&& fn) {
 
 constexpr int SPLIT_TICKETS = 4096;
 
+// One linear launch: the eleven operands every call has, in the order of the operator ABI; whatever else a call uses it
+// sets by name.  Built on the stack at the call, read by Launcher::linear.
+struct LinearOp {
+  const void *A, *W;
+  const float* bias;
+  void* C;
+  int64_t lda, ldw, ldc, M;
+  int N, K, dtype, act = AURORA_ACT_NONE, f32_gemm = -1, batch = 1;
+  void* C2 = nullptr;
+  const float *res = nullptr, *guard = nullptr;
+  int64_t ldc2 = 0, ldr = 0, sa = 0, sw = 0, sbias = 0, sc = 0;
+  float limit = 0.f;
+  LinearOp(const void* A_, int64_t lda_, const void* W_, int64_t ldw_, const float* bias_, void* C_, int64_t ldc_, int64_t M_, int N_,
+           int K_, int dtype_)
+      : A(A_), W(W_), bias(bias_), C(C_), lda(lda_), ldw(ldw_), ldc(ldc_), M(M_), N(N_), K(K_), dtype(dtype_) {}
+  LinearOp& activation(int a) { act = a; return *this; }
+  LinearOp& second_output(void* c2, int64_t ld) { C2 = c2; ldc2 = ld; return *this; }
+  LinearOp& residual(const float* r, int64_t ld) { res = r; ldr = ld; return *this; }
+  LinearOp& f32_mode(int mode) { f32_gemm = mode; return *this; }   // AURORA_F32_GEMM mode | AURORA_F32_*_SPLIT bits
+  LinearOp& guarded_by(const float* word, float lim) { guard = word; limit = lim; return *this; }
+  // `n` strided problems in one launch (aurora_hip_linear_batched); strides in elements
+  LinearOp& batched(int n, int64_t a, int64_t w, int64_t b, int64_t c) { batch = n; sa = a; sw = w; sbias = b; sc = c; return *this; }
+};
+
 // launches (skipped in a dry run)
 struct Launcher {
   Model& m;
   void* stream;
-  // batch > 1: `batch` strided problems in one launch (aurora_hip_linear_batched); strides in elements
-  void linear(const void* A, int64_t lda, const void* Wt, int64_t ldw, const float* bias, void* C, int64_t ldc, int64_t M,
-              int N, int K, int dtype, int act = AURORA_ACT_NONE, void* C2 = nullptr, int64_t ldc2 = 0,
-              const float* res = nullptr, int64_t ldr = 0, int f32_gemm = -1, const float* guard = nullptr,
-              float limit = 0.f, int batch = 1, int64_t sa = 0, int64_t sw = 0, int64_t sbias = 0, int64_t sc = 0) {
+  void linear(const LinearOp& o) {
     // plain bf16 linears with few tiles and a long K borrow slab scratch from the arena and split along K (gemm.hip)
     void* ws = nullptr;
     int64_t ws_bytes = 0;
     const size_t mark = m.arena.top;
-    if (m.split_k && dtype == AURORA_BF16 && batch == 1 && f32_gemm == -1 && (ws_bytes = aurora_hip_linear_workspace(M, N, K, dtype)) > 0)
+    if (m.split_k && o.dtype == AURORA_BF16 && o.batch == 1 && o.f32_gemm == -1 &&
+        (ws_bytes = aurora_hip_linear_workspace(o.M, o.N, o.K, o.dtype)) > 0)
       ws = m.arena.take((size_t)ws_bytes);
-    timed(m, stream, dtype == AURORA_BF16 ? K_LINEAR_BF16 : K_LINEAR_F32, 2.0 * (double)M * N * K * batch, [&] {
+    timed(m, stream, o.dtype == AURORA_BF16 ? K_LINEAR_BF16 : K_LINEAR_F32, 2.0 * (double)o.M * o.N * o.K * o.batch, [&] {
       if (ws)
-        return aurora_hip_linear_ws(A, lda, Wt, ldw, bias, C, ldc, C2, ldc2, res, ldr, M, N, K, dtype, act, ws, ws_bytes,
-                                    (int32_t*)m.tickets.p, SPLIT_TICKETS, 0, stream);
-      if (batch > 1)
-        return aurora_hip_linear_batched(A, lda, Wt, ldw, bias, C, ldc, M, N, K, dtype, act, f32_gemm, guard, limit, batch, sa,
-                                         sw, sbias, sc, stream);
-      return aurora_hip_linear_ex(A, lda, Wt, ldw, bias, C, ldc, C2, ldc2, res, ldr, M, N, K, dtype, act, f32_gemm, guard,
-                                  limit, stream);
+        return aurora_hip_linear_ws(o.A, o.lda, o.W, o.ldw, o.bias, o.C, o.ldc, o.C2, o.ldc2, o.res, o.ldr, o.M, o.N, o.K, o.dtype,
+                                    o.act, ws, ws_bytes, (int32_t*)m.tickets.p, SPLIT_TICKETS, 0, stream);
+      if (o.batch > 1)
+        return aurora_hip_linear_batched(o.A, o.lda, o.W, o.ldw, o.bias, o.C, o.ldc, o.M, o.N, o.K, o.dtype, o.act, o.f32_gemm,
+                                         o.guard, o.limit, o.batch, o.sa, o.sw, o.sbias, o.sc, stream);
+      return aurora_hip_linear_ex(o.A, o.lda, o.W, o.ldw, o.bias, o.C, o.ldc, o.C2, o.ldc2, o.res, o.ldr, o.M, o.N, o.K, o.dtype,
+                                  o.act, o.f32_gemm, o.guard, o.limit, stream);
     });
     m.arena.top = mark;   // (stream order: the next launch that takes this memory runs after this one)
+  }
+  // A guarded pair: `op` names the fp32 weights; the two-term launch on the same weights pre-split (`Ws`, with `splits`: the
+  // AURORA_F32_*_SPLIT bits of the other operands) runs iff `word` < `limit`, the three-term launch on `op` itself iff not.
+  void guarded_pair(LinearOp op, const void* Ws, int splits, const float* word, float limit) {
+    const void* Wf = op.W;
+    op.W = Ws;
+    linear(op.f32_mode(2 | AURORA_F32_W_SPLIT | splits).guarded_by(word, limit));
+    op.W = Wf;
+    linear(op.f32_mode(1));
   }
   // the qkv linear of a block with its result in head planes (bf16)
   void linear_planes(const void* A, int64_t lda, const void* Wt, int64_t ldw, const float* bias, void* C, int64_t plane_stride,

@@ -880,10 +880,10 @@ extern "C" int aurora_hip_finalize(aurora_hip_model* mp, void* stream) {
     fourier(LEAD_TIME, &hours, 1, D, lead.data());
     DevBuf d_lead = to_device(lead);
     DevBuf t1((size_t)D * 4), silu_c((size_t)D * 4);
-    L.linear(d_lead.p, D, m.W("backbone.time_mlp.0.weight"), D, m.W("backbone.time_mlp.0.bias"), t1.p, D, 1, D, D, AURORA_F32,
-             AURORA_ACT_SILU);
-    L.linear(t1.p, D, m.W("backbone.time_mlp.2.weight"), D, m.W("backbone.time_mlp.2.bias"), silu_c.p, D, 1, D, D, AURORA_F32,
-             AURORA_ACT_SILU);   // SiLU(c): the only way c is ever used
+    L.linear(LinearOp(d_lead.p, D, m.W("backbone.time_mlp.0.weight"), D, m.W("backbone.time_mlp.0.bias"), t1.p, D, 1, D, D, AURORA_F32)
+                 .activation(AURORA_ACT_SILU));
+    L.linear(LinearOp(t1.p, D, m.W("backbone.time_mlp.2.weight"), D, m.W("backbone.time_mlp.2.bias"), silu_c.p, D, 1, D, D, AURORA_F32)
+                 .activation(AURORA_ACT_SILU));   // SiLU(c): the only way c is ever used
     int64_t rows = 0;
     for (const Block& b : m.blocks) rows += 4 * b.dim;
     DevBuf w_all((size_t)rows * D * 4), b_all((size_t)rows * 4);
@@ -896,7 +896,7 @@ extern "C" int aurora_hip_finalize(aurora_hip_model* mp, void* stream) {
         off += 2 * b.dim;
       }
     m.mod = DevBuf((size_t)rows * 4);
-    L.linear(silu_c.p, D, w_all.p, D, b_all.f(), m.mod.p, rows, 1, (int)rows, D, AURORA_F32);
+    L.linear(LinearOp(silu_c.p, D, w_all.p, D, b_all.f(), m.mod.p, rows, 1, (int)rows, D, AURORA_F32));
     off = 0;
     for (Block& b : m.blocks) {   // chunk(2): shift first, then scale (film.py:48); scale_bias is 0 in every config
       b.shift1 = m.mod.f() + off; b.gain1 = m.mod.f() + off + b.dim; off += 2 * b.dim;
@@ -918,14 +918,14 @@ extern "C" int aurora_hip_finalize(aurora_hip_model* mp, void* stream) {
     attn_weights(m, -1, stream);
     // ---- encoder / decoder constants that depend on parameters only ----
     m.lead_emb = DevBuf((size_t)D * 4);
-    L.linear(d_lead.p, D, m.W("encoder.lead_time_embed.weight"), D, m.W("encoder.lead_time_embed.bias"), m.lead_emb.p, D, 1, D, D,
-             AURORA_F32);
+    L.linear(LinearOp(d_lead.p, D, m.W("encoder.lead_time_embed.weight"), D, m.W("encoder.lead_time_embed.bias"), m.lead_emb.p, D, 1, D,
+                      D, AURORA_F32));
     m.enc_rs = pack_resampler(m, "encoder.level_agg", m.enc_depth, m.perceiver_heads);
     m.dec_rs = pack_resampler(m, "decoder.level_decoder", m.dec_depth, m.perceiver_heads);
     const auto& l0 = m.enc_rs.layers[0];
     const int n_lat = m.Cl - 1;
     m.enc_q0 = DevBuf((size_t)n_lat * l0.inner * 4);
-    L.linear(m.W("encoder.atmos_latents"), D, l0.to_q, D, nullptr, m.enc_q0.p, l0.inner, n_lat, l0.inner, D, AURORA_F32);
+    L.linear(LinearOp(m.W("encoder.atmos_latents"), D, l0.to_q, D, nullptr, m.enc_q0.p, l0.inner, n_lat, l0.inner, D, AURORA_F32));
     if (l0.ln_q_w)
       L.layernorm(m.enc_q0.p, l0.inner, l0.ln_q_w, l0.ln_q_b, nullptr, 0, 0, m.enc_q0.f(), l0.inner, nullptr, 0, n_lat, l0.inner,
                   1e-5f, AURORA_F32);
@@ -1059,9 +1059,9 @@ extern "C" int aurora_hip_precompute(aurora_hip_model* mp, const aurora_hip_grid
       upload(d_pos.p, pos.data() + (size_t)h0 * m.Wp * D, (size_t)Lp * D * 4);       // the band's patch rows
       upload(d_scale.p, scale.data() + (size_t)h0 * m.Wp * D, (size_t)Lp * D * 4);
       m.pos_scale = DevBuf((size_t)Lp * D * 4);
-      L.linear(d_pos.p, D, m.W("encoder.pos_embed.weight"), D, m.W("encoder.pos_embed.bias"), pe.p, D, Lp, D, D, AURORA_F32);
-      L.linear(d_scale.p, D, m.W("encoder.scale_embed.weight"), D, m.W("encoder.scale_embed.bias"), m.pos_scale.p, D, Lp, D, D,
-               AURORA_F32, 0, nullptr, 0, pe.f(), D);
+      L.linear(LinearOp(d_pos.p, D, m.W("encoder.pos_embed.weight"), D, m.W("encoder.pos_embed.bias"), pe.p, D, Lp, D, D, AURORA_F32));
+      L.linear(LinearOp(d_scale.p, D, m.W("encoder.scale_embed.weight"), D, m.W("encoder.scale_embed.bias"), m.pos_scale.p, D, Lp, D, D,
+                        AURORA_F32).residual(pe.f(), D));
       hip_ok(hipStreamSynchronize(as_stream(stream)), "precompute sync");
     }
     // ---- pressure levels: per-level patch-embedding bias, decoder queries (encoder.py:318-330, decoder.py:176-200) ----
@@ -1077,24 +1077,24 @@ extern "C" int aurora_hip_precompute(aurora_hip_model* mp, const aurora_hip_grid
       DevBuf d_enc = to_device(enc), d_dec = to_device(dec);
       m.enc_bias = DevBuf((size_t)C * D * 4);
       if (m.level_condition.empty()) {
-        L.linear(d_enc.p, D, m.W("encoder.atmos_levels_embed.weight"), D, m.W("encoder.atmos_levels_embed.bias"), m.enc_bias.p, D, C,
-                 D, D, AURORA_F32, 0, nullptr, 0, m.W("encoder.atmos_token_embeds.bias"), 0);
+        L.linear(LinearOp(d_enc.p, D, m.W("encoder.atmos_levels_embed.weight"), D, m.W("encoder.atmos_levels_embed.bias"), m.enc_bias.p,
+                          D, C, D, D, AURORA_F32).residual(m.W("encoder.atmos_token_embeds.bias"), 0));
       } else {   // every level has its own patch embedding, bias included (levelcond.py:36-69)
         DevBuf pb((size_t)C * D * 4);
         for (int c = 0; c < C; ++c)
           hip_ok(hipMemcpy(pb.f() + (size_t)c * D, m.W("encoder.atmos_token_embeds.layers." + level_to_str(m.levels[c]) + ".bias"),
                            (size_t)D * 4, hipMemcpyDeviceToDevice), "copy");
-        L.linear(d_enc.p, D, m.W("encoder.atmos_levels_embed.weight"), D, m.W("encoder.atmos_levels_embed.bias"), m.enc_bias.p, D, C,
-                 D, D, AURORA_F32, 0, nullptr, 0, pb.f(), D);
+        L.linear(LinearOp(d_enc.p, D, m.W("encoder.atmos_levels_embed.weight"), D, m.W("encoder.atmos_levels_embed.bias"), m.enc_bias.p,
+                          D, C, D, D, AURORA_F32).residual(pb.f(), D));
         hip_ok(hipStreamSynchronize(as_stream(stream)), "precompute sync");
       }
       m.dec_queries = DevBuf((size_t)C * 2 * D * 4);
-      L.linear(d_dec.p, 2 * D, m.W("decoder.atmos_levels_embed.weight"), 2 * D, m.W("decoder.atmos_levels_embed.bias"),
-               m.dec_queries.p, 2 * D, C, 2 * D, 2 * D, AURORA_F32);
+      L.linear(LinearOp(d_dec.p, 2 * D, m.W("decoder.atmos_levels_embed.weight"), 2 * D, m.W("decoder.atmos_levels_embed.bias"),
+                        m.dec_queries.p, 2 * D, C, 2 * D, 2 * D, AURORA_F32));
       auto first_q = [&](const Resampler& rs, DevBuf& q) {
         const auto& d0 = rs.layers[0];
         q = DevBuf((size_t)C * d0.inner * 4);
-        L.linear(m.dec_queries.p, 2 * D, d0.to_q, 2 * D, nullptr, q.p, d0.inner, C, d0.inner, 2 * D, AURORA_F32);
+        L.linear(LinearOp(m.dec_queries.p, 2 * D, d0.to_q, 2 * D, nullptr, q.p, d0.inner, C, d0.inner, 2 * D, AURORA_F32));
         if (d0.ln_q_w)
           L.layernorm(q.p, d0.inner, d0.ln_q_w, d0.ln_q_b, nullptr, 0, 0, q.f(), d0.inner, nullptr, 0, C, d0.inner, 1e-5f, AURORA_F32);
       };

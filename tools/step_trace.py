@@ -1,0 +1,122 @@
+"""What one forecast step launches, how much workspace it takes and what it computes -- as text that two builds of the
+library can be diffed on.
+
+    AURORA_HIP_LIB=<library> python tools/step_trace.py --out FILE     (GPU box)
+
+One JSON record per line:
+  * every golden case of tests/golden_cases.py (built as tests/test_gpu_model.py builds them), in fp32 and under autocast:
+    the ordered (kind, work) list of a warmed step's launches with every kind profiled, the handle's workspace_bytes(),
+    the sha256 of every output variable's bytes, and `repeatable`: whether the next step of the same process gives the
+    same hashes (where a build does not reproduce itself, its hashes say nothing about another build);
+  * every rank of the band splits of tests/test_gpu_sharded.py::test_sharded_equals_unsharded (base_pad at 192x96 over
+    2 and 3 ranks, at 256x96 over 5), fp32 and autocast, with a transport whose `post` / `wait` do nothing: launch list
+    and workspace only -- the halo bytes are not real, the values are the sharded tests' business.
+A refactor of the launch sequence (csrc/step.hip) is done when the files of the two builds are equal.  Printed: one short
+line per record -- workspace, launch count, the first 16 hex digits of the sha256 of the launch list and of the output
+hashes -- which is what a log keeps; the launch lists themselves are some 150 kB per build.
+"""
+import argparse
+import hashlib
+import json
+import sys
+from pathlib import Path
+
+import torch
+
+ROOT = Path(__file__).resolve().parents[1]
+sys.path.insert(0, str(ROOT))
+import aurora_amd  # noqa: E402
+from aurora_amd import Batch, Metadata  # noqa: E402
+from aurora_amd.engine import native  # noqa: E402
+from aurora_amd.engine.engine import Engine, Shard  # noqa: E402
+from tests import helpers  # noqa: E402
+from tests.golden_cases import CASES  # noqa: E402
+
+BANDS = ((192, 96, 2), (192, 96, 3), (256, 96, 5))
+
+
+class NoTransport(native._Transport):
+    def allocate(self, n_bytes):
+        super().allocate(n_bytes)
+        self.send.zero_()
+        self.recv.zero_()
+
+    def _post(self, *a):
+        return 0
+
+    def _wait(self, *a):
+        return 0
+
+
+def build(name, autocast, H=None, W=None):
+    case = dict(CASES[name])
+    if H:
+        case["H"], case["W"] = H, W
+    model = getattr(aurora_amd, case["cls"])(**case["kwargs"], autocast=autocast)
+    model.load_state_dict(helpers.case_state_dict(model, torch.float32), strict=True)
+    model = model.to("cuda").eval()
+    surf, static, atmos, lat, lon, times = helpers.case_inputs(case, model.config)
+    f = lambda d: {k: v.float() for k, v in d.items()}  # noqa: E731
+    return model, Batch(f(surf), f(static), f(atmos), Metadata(lat.float(), lon.float(), times, tuple(case["levels"])))
+
+
+def hashes(pred):
+    torch.cuda.synchronize()
+    return {f"{kind}.{k}": hashlib.sha256(v.contiguous().cpu().numpy().tobytes()).hexdigest()
+            for kind, d in (("surf", pred.surf_vars), ("atmos", pred.atmos_vars)) for k, v in d.items()}
+
+
+def traced(nat, step):
+    """(launch list, workspace bytes, prediction) of one `step()` with every kind profiled."""
+    nat.profile_begin()
+    pred = step()
+    launches = [[kind, work] for kind, _, work in nat.profile_end_list()]
+    return launches, nat.workspace_bytes(), pred
+
+
+def short(x):
+    return hashlib.sha256(json.dumps(x, sort_keys=True).encode()).hexdigest()[:16]
+
+
+def digest(r):
+    where = f"{r['case']} {'autocast' if r['autocast'] else 'fp32'}" + (f" rank {r['rank']}/{r['world']}" if "world" in r else "")
+    out = f" outputs {short(r['sha256'])} repeatable {r['repeatable']}" if "sha256" in r else ""
+    return f"{where}: workspace_bytes {r['workspace_bytes']} launches {r['n_launches']} {short(r['launches'])}{out}"
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", required=True)
+    args = ap.parse_args()
+    records = []
+    with torch.inference_mode():
+        for name in CASES:
+            for autocast in (False, True):
+                model, batch = build(name, autocast)
+                model.forward(batch)
+                launches, ws, pred = traced(model.engine().native, lambda: model.forward(batch))
+                h = hashes(pred)
+                records.append({"case": name, "autocast": autocast, "workspace_bytes": ws, "n_launches": len(launches),
+                                "repeatable": hashes(model.forward(batch)) == h, "sha256": h, "launches": launches})
+        for H, W, world in BANDS:
+            for autocast in (False, True):
+                model, batch = build("base_pad", autocast, H, W)
+                for rank in range(world):
+                    model._shard = Shard(rank, world, None, gather_output=False)
+                    eng = Engine(model, transport=NoTransport(None, "cuda"))
+                    model._shard = None
+                    band = eng.local_band(batch)
+                    eng.step(band)
+                    launches, ws, _ = traced(eng.native, lambda: eng.step(band))
+                    records.append({"case": f"base_pad {H}x{W}", "autocast": autocast, "world": world, "rank": rank,
+                                    "workspace_bytes": ws, "n_launches": len(launches), "launches": launches})
+    torch.cuda.synchronize()
+    Path(args.out).parent.mkdir(parents=True, exist_ok=True)
+    Path(args.out).write_text("".join(json.dumps(r, sort_keys=True) + "\n" for r in records))
+    flaky = [f"{r['case']} autocast={r['autocast']}" for r in records if r.get("repeatable") is False]
+    print("\n".join(digest(r) for r in records))
+    print(f"{len(records)} records; not repeatable within one process: {flaky or 'none'}")
+
+
+if __name__ == "__main__":
+    main()
