@@ -1,6 +1,6 @@
 // Host-side geometry of the 3D Swin backbone and of its latitude-band partition: window token / group tables, owned
 // rows per rank and stage, and the halo plans of window attention.  Pure host code (no device work); shared by the model
-// handle (model.hip / step.hip) and exposed through aurora_hip_band_partition / aurora_hip_band_plan.
+// handle (model_grid.hip / step.hip) and exposed through aurora_hip_band_partition / aurora_hip_band_plan.
 #pragma once
 
 #include <stdint.h>

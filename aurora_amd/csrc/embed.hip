@@ -304,7 +304,7 @@ __global__ __launch_bounds__(256) void perceiver_attention_kernel(const PercArgs
 // The same attention from PRE-MULTIPLIED scores (first Perceiver layer: its queries are model constants, so
 //   q_l . (W_k x_j) = (W_k^T q_l) . x_j
 // and the key half of to_kv shrinks from `inner` columns to Lq * heads -- the rows W_k^T q_l / sqrt(head_dim) are made when the
-// weights are packed, model.hip:score_weights).  A context row of `vs` holds [v (inner) | ... scores at s_off: (query l, head h)
+// weights are packed, model_weights.hip:score_weights).  A context row of `vs` holds [v (inner) | ... scores at s_off: (query l, head h)
 // at l * heads + h].  Lane layout as above; a group's scores are the same address in all its lanes (one broadcast load), the
 // softmax needs no cross-lane traffic at all: two passes over a query's Lk scores (maximum, then exponentials), one over
 // the values.  QC queries share a pass over the column's values.

@@ -1,12 +1,15 @@
-// The model handle of libaurora_hip.so: shared definitions of model.hip (creation, weights, tables) and step.hip (the
-// launch sequence of one forecast step).  Host code only; every launch goes through the operator ABI of this library.
+// The model handle of libaurora_hip.so: shared definitions of model.hip (creation, lifecycle), model_weights.hip (what
+// depends on parameters), model_grid.hip (what depends on grid, levels or time) and step.hip (the launch sequence of one
+// forecast step).  Host code only; every launch goes through the operator ABI of this library.
 #pragma once
 
 #include <math.h>
 #include <stdlib.h>
 #include <string.h>
 
+#include <algorithm>
 #include <array>
+#include <exception>
 #include <map>
 #include <memory>
 #include <stdexcept>
@@ -28,6 +31,17 @@ struct Fail {
       throw ::aurora::Fail{AURORA_E_ARG}; \
     }                                    \
   } while (0)
+// Body of a C ABI function: what it throws becomes the function's return code.
+#define GUARDED(...)                                    \
+  try {                                                 \
+    __VA_ARGS__;                                        \
+    return AURORA_OK;                                   \
+  } catch (const ::aurora::Fail& f) {                   \
+    return f.code;                                      \
+  } catch (const std::exception& e) {                   \
+    ::aurora::set_error("internal error: %s", e.what()); \
+    return AURORA_E_LAUNCH;                             \
+  }
 inline void ok(int code) {
   if (code != AURORA_OK) throw Fail{code};
 }
@@ -103,7 +117,7 @@ struct Resampler {
   };
   std::vector<Layer> layers;
   std::vector<DevBuf> own;
-  // First layer, queries known when the weights are packed (model.hip:score_weights): to_kv replaced by
+  // First layer, queries known when the weights are packed (model_weights.hip:score_weights): to_kv replaced by
   //   [W_v (inner rows) | W_k^T q_l / sqrt(head_dim) per (query l, head h) (n_s = Lq * heads rows) | zero rows up to n_vs]
   // -- a context row then carries its values and its SCORES with every query; the key projection does not exist.
   DevBuf vs_w, vs_ws;      // fp32, and the fp16-pair layout scaled by 2^6 (empty: not eligible)
@@ -219,7 +233,7 @@ struct aurora_hip_model {
   bool split_attention = false;
   bool qkv_planes = true;   // bf16 blocks: q | k | v leave the qkv linear one attention head per plane (aurora_hip_linear_planes)
   bool reassoc_out = true;  // decoder de-aggregation: to_out of the three value rows per column, combined in registers (perceiver_out.hip)
-  bool score_weights = true;   // first Perceiver layers: scores from W_k^T q rows instead of a key projection (model.hip:score_weights)
+  bool score_weights = true;   // first Perceiver layers: scores from W_k^T q rows instead of a key projection (model_weights.hip:score_weights)
 
   // per step
   aurora::DevBuf abs_enc, dyn_planes, ctx_max;
@@ -377,13 +391,18 @@ inline DevBuf to_device(const std::vector<float>& v) {
   upload(b.p, v.data(), v.size() * sizeof(float));
   return b;
 }
-inline std::vector<float> to_host(const Tensor& t) {
-  std::vector<float> h((size_t)t.numel);
-  hip_ok(hipMemcpy(h.data(), t.f(), h.size() * 4, hipMemcpyDeviceToHost), "download");
+inline std::vector<float> to_host(const float* dev, size_t n) {
+  std::vector<float> h(n);
+  hip_ok(hipMemcpy(h.data(), dev, n * 4, hipMemcpyDeviceToHost), "download");
   return h;
 }
+inline std::vector<float> to_host(const Tensor& t) { return to_host(t.f(), (size_t)t.numel); }
+inline bool contains(const std::vector<std::string>& v, const std::string& s) { return std::find(v.begin(), v.end(), s) != v.end(); }
 
 constexpr float F16_SAFE = 16384.0f;   // activations below this may take the two-term fp16 operand split
+// The two-term fp16 split scales weights by 2^6 and fp16 ends at 65504: only weights whose max |w| stays below this are
+// pre-split (or decide for the two-term mode at all)
+constexpr float PRESPLIT_W_MAX = 1000.0f;
 // fp32 GEMM mode of the linears whose input is bounded (by construction or by the device-side guard): the two-term fp16
 // split, unless the user pinned a mode through AURORA_F32_GEMM
 int bounded_mode();
@@ -391,8 +410,24 @@ std::string level_to_str(double level);   // `850`, `0_5` (aurora/normalisation.
 
 // model.hip
 int lora_key(const Model& m, int step);
+// model_weights.hip
+// What feeds the device-side range guards: max |x| of a device / host array, and the largest L1 row norm of a (rows, K)
+// matrix, never below `floor`.  Plain float accumulation in row order: the guard limits depend on it.
+float absmax(const float* dev, size_t n);
+float absmax(const std::vector<float>& h);
+inline float absmax(const Tensor& t) { return absmax(t.f(), (size_t)t.numel); }
+float max_row_l1(const std::vector<float>& h, int64_t rows, int64_t K, float floor);
+// The fp16-pair form, scaled by 2^6, of `groups` stacked fp32 device matrices (rows, K, ld) for the guarded two-term GEMM;
+// empty where `presplit_shape` rules the matrix out.  Split and synchronised when it returns.
+bool presplit_shape(int64_t rows, int64_t K, int row_multiple);
+DevBuf presplit(const float* w, int64_t rows, int64_t K, int64_t ld, int row_multiple, int groups = 1);
+void score_weights(Model& m, Resampler& r, const float* q0, int Lq, int heads);
+void build_atmos_heads(Model& m, bool per_level);
 const AttnSet& attn_weights(Model& m, int key, void* stream);
 const EmbedPack& embed_pack(Model& m, int kind, int T, const std::vector<char>& present);
+// model_grid.hip
+enum Expansion { POS, SCALE, LEAD_TIME, LEVELS, ABS_TIME };
+void fourier(Expansion kind, const double* x, int64_t n, int d, float* out);   // (n, d) Fourier features of `x`
 const DevTables& tables_for(Model& m, int stage, bool shifted);
 const DevPlan& plan_for(Model& m, int stage, bool shifted);
 // step.hip

@@ -37,7 +37,7 @@ LayerSpace layer_space(const Model& m, const Resampler& rs, size_t i, int B, int
   LayerSpace s{};
   s.unit = (size_t)n_rows * Dd * 4;
   // First layer, queries known at pack time: the context rows leave `to_kv` as [v | scores with every query] -- no keys
-  // (model.hip:score_weights); else k | v.
+  // (model_weights.hip:score_weights); else k | v.
   s.scores = i == 0 && rs.n_vs > 0 && rs.vs_lq == Lq && ly.ln_k_w == nullptr;
   s.kv_ld = s.scores ? rs.n_vs : 2 * inner;
   s.kv_bytes = (size_t)ctx_rows * s.kv_ld * 4;

@@ -819,7 +819,7 @@ def test_perceiver_out_reassociated_equals_attention_then_to_out(Lq, heads, N, c
 
 def _score_rows(q, w_kv, ctx, Lq, heads, hd):
     """fp64: the context rows as [v | scaled scores with every query | zero padding to a multiple of 4] -- what `to_kv` leaves
-    when its key half is replaced by the rows W_k^T q_l / sqrt(head_dim) (model.hip:score_weights)."""
+    when its key half is replaced by the rows W_k^T q_l / sqrt(head_dim) (model_weights.hip:score_weights)."""
     inner = heads * hd
     w_s = torch.einsum("lhd,hdc->lhc", q.reshape(Lq, heads, hd), w_kv[:inner].reshape(heads, hd, -1)) / hd ** 0.5
     w_vs = torch.cat([w_kv[inner:], w_s.reshape(Lq * heads, -1)], dim=0)

@@ -145,7 +145,7 @@ def test_decoder_reassociation_equals_attention_then_to_out_at_model_level(monke
 
 def test_scores_from_packed_query_rows_equal_key_projection_at_model_level(monkeypatch):
     """First Perceiver layers (encoder level aggregation, decoder de-aggregation): `to_kv` with its key half replaced by the
-    Lq x heads rows W_k^T q / sqrt(64) (csrc/model.hip:score_weights) and attention from those scores, against keys + q . k in
+    Lq x heads rows W_k^T q / sqrt(64) (csrc/model_weights.hip:score_weights) and attention from those scores, against keys + q . k in
     the same fp32 model at the production widths -- the same function re-associated; fp32 round-off apart."""
     outs = {}
     for on in ("1", "0"):

@@ -1,7 +1,8 @@
 """What one forecast step launches, how much workspace it takes and what it computes -- as text that two builds of the
 library can be diffed on.
 
-    AURORA_HIP_LIB=<library> python tools/step_trace.py --out FILE     (GPU box)
+    AURORA_HIP_LIB=<library> python tools/step_trace.py --out FILE                       (GPU box)
+    AURORA_HIP_LIB=<library> python tools/step_trace.py --out FILE --f32-gemm bf16      (its own process)
 
 One JSON record per line:
   * every golden case of tests/golden_cases.py (built as tests/test_gpu_model.py builds them), in fp32 and under autocast:
@@ -10,14 +11,23 @@ One JSON record per line:
     same hashes (where a build does not reproduce itself, its hashes say nothing about another build);
   * every rank of the band splits of tests/test_gpu_sharded.py::test_sharded_equals_unsharded (base_pad at 192x96 over
     2 and 3 ranks, at 256x96 over 5), fp32 and autocast, with a transport whose `post` / `wait` do nothing: launch list
-    and workspace only -- the halo bytes are not real, the values are the sharded tests' business.
-A refactor of the launch sequence (csrc/step.hip) is done when the files of the two builds are equal.  Printed: one short
+    and workspace only -- the halo bytes are not real, the values are the sharded tests' business;
+  * the production widths, built as tests/test_gpu_production.py builds them (`_seeded_model`, `_inputs`): AuroraPretrained()
+    on 181 x 360 and AuroraAirPollution() on 46 x 72, 13 levels, fp32 and autocast, recorded like the golden cases.  The
+    golden cases run at embed_dim 64, where most weights are too narrow for the fp16-pair form; at embed_dim 512 every
+    pre-split site of the handle (Perceiver layers, score rows, patch embeddings, surface MLP, output heads) is eligible, so
+    a changed eligibility rule changes these launch lists.
+`--f32-gemm MODE` pins AURORA_F32_GEMM=MODE before the library is first called -- the mode is read once per process, hence a
+run of its own -- and records AuroraPretrained() on 181 x 360 only: with a pinned mode the handle makes no pre-split buffer
+and no guarded launch pair.
+A refactor of the handle (csrc/step.hip, csrc/model*.hip) is done when the files of the two builds are equal.  Printed: one short
 line per record -- workspace, launch count, the first 16 hex digits of the sha256 of the launch list and of the output
 hashes -- which is what a log keeps; the launch lists themselves are some 150 kB per build.
 """
 import argparse
 import hashlib
 import json
+import os
 import sys
 from pathlib import Path
 
@@ -30,9 +40,11 @@ from aurora_amd import Batch, Metadata  # noqa: E402
 from aurora_amd.engine import native  # noqa: E402
 from aurora_amd.engine.engine import Engine, Shard  # noqa: E402
 from tests import helpers  # noqa: E402
+from tests import test_gpu_production as production  # noqa: E402
 from tests.golden_cases import CASES  # noqa: E402
 
 BANDS = ((192, 96, 2), (192, 96, 3), (256, 96, 5))
+PRODUCTION = (("AuroraPretrained", 181, 360), ("AuroraAirPollution", 46, 72))
 
 
 class NoTransport(native._Transport):
@@ -60,6 +72,14 @@ def build(name, autocast, H=None, W=None):
     return model, Batch(f(surf), f(static), f(atmos), Metadata(lat.float(), lon.float(), times, tuple(case["levels"])))
 
 
+def build_production(cls_name, H, W, autocast):
+    with torch.inference_mode(False):
+        model = production._seeded_model(getattr(aurora_amd, cls_name), autocast=autocast)
+    cfg = model.config
+    batch = production._inputs(cfg, H, W, production.LEVELS13, positive=cfg.positive_surf_vars + cfg.positive_atmos_vars)
+    return model, batch.to("cuda")
+
+
 def hashes(pred):
     torch.cuda.synchronize()
     return {f"{kind}.{k}": hashlib.sha256(v.contiguous().cpu().numpy().tobytes()).hexdigest()
@@ -84,21 +104,37 @@ def digest(r):
     return f"{where}: workspace_bytes {r['workspace_bytes']} launches {r['n_launches']} {short(r['launches'])}{out}"
 
 
+def whole_step(case, autocast, model, batch):
+    """The record of an un-sharded case: a warmed step traced, the next one hashed again."""
+    model.forward(batch)
+    launches, ws, pred = traced(model.engine().native, lambda: model.forward(batch))
+    h = hashes(pred)
+    return {"case": case, "autocast": autocast, "workspace_bytes": ws, "n_launches": len(launches),
+            "repeatable": hashes(model.forward(batch)) == h, "sha256": h, "launches": launches}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", required=True)
+    ap.add_argument("--f32-gemm", choices=("native", "bf16", "f16"),
+                    help="pin AURORA_F32_GEMM for this process and record AuroraPretrained() 181 x 360 only")
     args = ap.parse_args()
     records = []
+    if args.f32_gemm:
+        os.environ["AURORA_F32_GEMM"] = args.f32_gemm   # before the first call into the library, which reads it once
     with torch.inference_mode():
-        for name in CASES:
+        for cls_name, H, W in PRODUCTION[:1] if args.f32_gemm else PRODUCTION:
+            for autocast in (False, True):
+                pinned = f" AURORA_F32_GEMM={args.f32_gemm}" if args.f32_gemm else ""
+                model, batch = build_production(cls_name, H, W, autocast)
+                records.append(whole_step(f"{cls_name} {H}x{W}{pinned}", autocast, model, batch))
+                del model
+                torch.cuda.empty_cache()
+        for name in () if args.f32_gemm else CASES:
             for autocast in (False, True):
                 model, batch = build(name, autocast)
-                model.forward(batch)
-                launches, ws, pred = traced(model.engine().native, lambda: model.forward(batch))
-                h = hashes(pred)
-                records.append({"case": name, "autocast": autocast, "workspace_bytes": ws, "n_launches": len(launches),
-                                "repeatable": hashes(model.forward(batch)) == h, "sha256": h, "launches": launches})
-        for H, W, world in BANDS:
+                records.append(whole_step(name, autocast, model, batch))
+        for H, W, world in () if args.f32_gemm else BANDS:
             for autocast in (False, True):
                 model, batch = build("base_pad", autocast, H, W)
                 for rank in range(world):
