@@ -7,66 +7,28 @@
 #include <algorithm>
 
 #include "model.h"
+#include "resampler_space.h"
 
 namespace aurora {
 
 namespace {
 
-constexpr size_t round256(size_t x) { return (x + 255) & ~size_t(255); }
-
 struct CtxGuard { const float* word; float a, c, limit_kv; bool pairs; };
 
-// Workspace of a resampler layer: three regions instead of one buffer per intermediate (the decoder's intermediates are
-// 3.5 GB each at 0.25 degree) --
-//   Y  the layer's result (it outlives the rest; stack order); until fc2 writes it, it holds the attention output
-//   L  the MLP's input / residual (LayerNorm 1 output): fp32 values, or their fp16 pairs
-//   S  scratch: k | v (and q), then to_out's result, then the MLP's hidden layer, each dead before the next is written;
-//      the MLP runs in row chunks so that a chunk's hidden layer fits
-// Y and L are `unit` bytes each, S is `s_bytes`; the offsets are into S.
-struct LayerSpace {
-  size_t unit, kv_bytes, q_bytes, att_off, p_off, p_bytes, s_bytes, hid_row;
-  int kv_ld;
-  int64_t chunk_rows;
-  bool scores, att_in_y, att_pairs, reassoc, pairs;
-};
+// The workspace of layer `i` of `rs` (resampler_space.h) for one call of `resampler`.
 LayerSpace layer_space(const Model& m, const Resampler& rs, size_t i, int B, int64_t cols, int64_t ctx_rows, int Lq, int Lk,
                        int heads) {
   const auto& ly = rs.layers[i];
-  const int inner = ly.inner, Dd = ly.dim;
-  const int64_t n_cols = (int64_t)B * cols, n_rows = n_cols * Lq;
-  LayerSpace s{};
-  s.unit = (size_t)n_rows * Dd * 4;
-  // First layer, queries known at pack time: the context rows leave `to_kv` as [v | scores with every query] -- no keys
-  // (model_weights.hip:score_weights); else k | v.
-  s.scores = i == 0 && rs.n_vs > 0 && rs.vs_lq == Lq && ly.ln_k_w == nullptr;
-  s.kv_ld = s.scores ? rs.n_vs : 2 * inner;
-  s.kv_bytes = (size_t)ctx_rows * s.kv_ld * 4;
-  s.q_bytes = i > 0 ? (size_t)n_rows * inner * 4 : 0;
-  const size_t att_bytes = (size_t)n_rows * inner * 4;
-  s.att_in_y = att_bytes <= s.unit;   // (inner <= dim in every published model; else behind everything it coexists with)
-  const size_t kvq_bytes = round256(s.kv_bytes) + round256(s.q_bytes);
-  s.att_off = round256(std::max(s.unit, kvq_bytes));
-  s.hid_row = (size_t)ly.hidden * 4;
-  const size_t hid_min = (size_t)std::min<int64_t>(n_rows, 256) * s.hid_row;   // at least one row tile of the hidden layer
-  // The decoder's de-aggregation (first layer: queries shared by all columns, three keys per column) runs RE-ASSOCIATED
-  // (perceiver_out.hip): to_out of the three value rows per column and head, then the Lq x 3 convex combinations per head
-  // in registers -- the attention output and its Lq-row `to_out` GEMM do not exist.  Its inputs: the softmax weights P
-  // (behind to_out's result in the scratch region) and the value rows as fp16 pairs (in the result region, until fc2
-  // writes there).  Two fp16 terms: decided on the device by the guard of the linear it replaces.
-  s.att_pairs = ly.to_out_s != nullptr && inner % 32 == 0;
-  s.reassoc = m.reassoc_out && i == 0 && s.att_pairs && s.att_in_y && ly.f16_mode == 2 &&
-              (size_t)n_cols * Lk * inner * 4 <= s.unit && aurora_hip_perceiver_out_supported(Lq, Lk, heads, ly.head_dim, Dd) != 0;
-  s.p_off = round256(s.unit);
-  s.p_bytes = s.reassoc ? (size_t)n_cols * heads * 64 * 4 : 0;
-  s.s_bytes = std::max(std::max(s.att_in_y ? std::max(s.unit, kvq_bytes) : s.att_off + att_bytes, hid_min),
-                       s.reassoc ? s.p_off + s.p_bytes : (size_t)0);
-  // The MLP in the fp16-pair layout end to end: the LayerNorm writes its result already split (and ONLY split), fc1
-  // reads that and writes its GELU'd result split, fc2 reads that -- neither GEMM splits anything -- and the LayerNorm
-  // behind the MLP takes the split array as its residual.
-  s.pairs = ly.fc1_s && ly.fc2_s && Dd % 32 == 0;
-  s.chunk_rows = std::min<int64_t>(n_rows, (int64_t)(s.s_bytes / s.hid_row));
-  if (s.chunk_rows < n_rows) s.chunk_rows = s.chunk_rows / 256 * 256;   // whole row tiles per chunk (>= 256 rows fit: hid_min)
-  return s;
+  LayerShape sh{};
+  sh.layer = i;
+  sh.dim = ly.dim; sh.inner = ly.inner; sh.hidden = ly.hidden; sh.head_dim = ly.head_dim; sh.heads = heads;
+  sh.n_vs = rs.n_vs; sh.vs_lq = rs.vs_lq;
+  sh.ln_k = ly.ln_k_w != nullptr; sh.to_out_s = ly.to_out_s != nullptr; sh.fc1_s = ly.fc1_s != nullptr; sh.fc2_s = ly.fc2_s != nullptr;
+  sh.f16_mode = ly.f16_mode;
+  sh.reassoc_out = m.reassoc_out;
+  sh.out_supported = aurora_hip_perceiver_out_supported(Lq, Lk, heads, ly.head_dim, ly.dim) != 0;
+  sh.B = B; sh.cols = cols; sh.ctx_rows = ctx_rows; sh.Lq = Lq; sh.Lk = Lk;
+  return layer_space(sh);
 }
 
 // The MLP half of a resampler layer: LayerNorm 1 of to_out's result `o` (+ residual) into `lat1`, fc1 -> fc2 in row chunks
@@ -167,6 +129,9 @@ float* resampler(Model& m, Launcher& L, const Resampler& rs, const float* ctx, i
     const float lim_out = (F16_SAFE / ly.v_l1 - g_c) / g_a;
     float* o = (float*)S;   // (k | v and q are dead)
     if (sp.reassoc) {
+      // (the launch that writes P reads k | v, and to_out's result lands on [0, unit) while P is read)
+      REQUIRE(sp.p_off >= sp.kv_bytes && sp.p_off >= sp.unit && sp.p_off + sp.p_bytes <= sp.s_bytes,
+              "resampler: the softmax weights overlap k | v or to_out's result in the scratch region");
       float* P = (float*)(S + sp.p_off);
       void* Vp = y;
       timed(m, L.stream, K_PERCEIVER_ATTENTION, 0.0, [&] {

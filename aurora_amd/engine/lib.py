@@ -962,14 +962,28 @@ def tuning_from_env() -> HipTuning:
     """The AURORA_* switches of INTEGRATION.md, read HERE (once per handle creation) and handed to the library as fields of
     the configuration: the library itself never reads the environment."""
     t = HipTuning()
-    e = os.environ.get
-    if e("AURORA_FUSE_LN") is not None:
-        t.fuse_ln = int(e("AURORA_FUSE_LN")) + 1            # 0 / 1 / 2 -> never / fill rule / always
+
+    def value(var: str, allowed: tuple[int, ...]):
+        raw = os.environ.get(var)
+        if raw is None:
+            return None
+        try:
+            v = int(raw.strip())
+        except ValueError:
+            v = None
+        if v not in allowed:   # (a typo must not become the library's default: an A/B run would compare a path with itself)
+            raise ValueError(f"{var}={raw!r}: expected one of {', '.join(map(str, allowed))}")
+        return v
+
+    v = value("AURORA_FUSE_LN", (0, 1, 2))
+    if v is not None:
+        t.fuse_ln = v + 1            # 0 / 1 / 2 -> never / fill rule / always
     for field, var in (("band_split_attention", "AURORA_BAND_SPLIT_ATTENTION"), ("qkv_planes", "AURORA_QKV_PLANES"),
                        ("split_k", "AURORA_SPLIT_K"), ("perceiver_reassoc", "AURORA_PERCEIVER_REASSOC"),
                        ("score_weights", "AURORA_SCORE_WEIGHTS")):
-        if e(var) is not None:
-            setattr(t, field, 2 if int(e(var)) != 0 else 1)
+        v = value(var, (0, 1))
+        if v is not None:
+            setattr(t, field, 2 if v else 1)
     return t
 
 
