@@ -19,6 +19,9 @@ LIB = PKG / "_lib" / "libaurora_hip.so"
 SOURCES = ("runtime.hip", "gemm.hip", "gemm_f32.hip", "gemm_ln512.hip", "gemm_a4.hip", "attention.hip", "norm.hip", "embed.hip", "perceiver_out.hip", "band.hip",
            "model.hip", "model_weights.hip", "model_grid.hip", "step.hip", "regrid.hip", "scores.hip", "ensemble_scores.hip", "spectra.hip", "event_scores.hip")
 ARCH = "gfx950"
+# -amdgpu-mfma-vgpr-form: keep MFMA accumulators in arch VGPRs (gfx950 has one unified file);
+# otherwise the softmax in the attention kernel pays a v_accvgpr_read per score.
+COMPILE_FLAGS = (f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-mllvm", "-amdgpu-mfma-vgpr-form=1")
 
 
 def _hipcc() -> str:
@@ -45,12 +48,8 @@ def build_library(force: bool = False, verbose: bool = True) -> Path:
     procs = []
     for src in SOURCES:
         obj = LIB.parent / (src.replace(".hip", ".o"))
-        # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in arch VGPRs (gfx950 has one unified file);
-        # otherwise the softmax in the attention kernel pays a v_accvgpr_read per score.
-        # (AURORA_BUILD_FLAGS: extra compiler flags of a probe build, e.g. -DA4_EXPERIMENTS for tools/gemm_a4_stamps.py --
-        #  after `python tools/gen_gemm_asm.py 1 2 3` has written the gemm_a4_loop_v<N>.inc that build includes)
-        cmd = [_hipcc(), f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC", "-mllvm",
-               "-amdgpu-mfma-vgpr-form=1", *os.environ.get("AURORA_BUILD_FLAGS", "").split(), "-c", str(CSRC / src), "-o", str(obj)]
+        # (AURORA_BUILD_FLAGS: extra compiler flags of a probe build, e.g. -DPO_STAMPS for tools/probes/po_stamps.py)
+        cmd = [_hipcc(), *COMPILE_FLAGS, *os.environ.get("AURORA_BUILD_FLAGS", "").split(), "-c", str(CSRC / src), "-o", str(obj)]
         if verbose:
             print(" ".join(cmd), flush=True)
         procs.append((src, subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT)))

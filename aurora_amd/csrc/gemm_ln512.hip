@@ -46,13 +46,6 @@ __global__ __launch_bounds__(FTHREADS, 2) void linear_ln512_kernel(const LinearL
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wm = wave >> 2, wn = wave & 3;   // waves w and w+4 share a SIMD; wm = 1 runs one phase behind
   const int64_t m0 = (p.tile0 + blockIdx.x) * FM;
-#ifdef LN_PROBE_TIMES
-  uint64_t ts[8];
-  ts[0] = wall_clock64();
-#define LN_TS(i) ts[i] = wall_clock64()
-#else
-#define LN_TS(i)
-#endif
   // (Do the CUs of a launch run in lockstep -- every main loop at once with HBM idle, then every epilogue at once?  Holding
   // the first-round workgroups of every other CU back by 8 ... 55 us changed nothing but the delay itself,
   // profiles/r04_ab_ln512_stagger.log: a CU's epilogue is as fast as the bytes it keeps in flight allow, whatever its
@@ -106,7 +99,6 @@ __global__ __launch_bounds__(FTHREADS, 2) void linear_ln512_kernel(const LinearL
   __builtin_amdgcn_s_barrier();   // stage 0 is complete
   asm volatile("" ::: "memory");
   if (wm == 1) __builtin_amdgcn_s_barrier();   // the late half: one phase behind from here on
-  LN_TS(1);
 
   for (int s = 0; s < nt; ++s) {
     u32x4 fw[8], fx[4];
@@ -136,7 +128,6 @@ __global__ __launch_bounds__(FTHREADS, 2) void linear_ln512_kernel(const LinearL
   }
   if (wm == 0) __builtin_amdgcn_s_barrier();   // the early half waits for the late half's last phase: the ring is dead
   asm volatile("" ::: "memory");
-  LN_TS(2);
 
   // ---- epilogue.  Where a tile's time goes (profiles/r04_ln512_phases.log, K = 512: 40 us): prologue 3.3, main loop
   // 15.6, residual requests + bias + rounding 4-6, statistics 2-4, the four passes 12-13.  Every global address below is
@@ -183,7 +174,6 @@ __global__ __launch_bounds__(FTHREADS, 2) void linear_ln512_kernel(const LinearL
                           __uint_as_float(hi & 0xffff0000u)};
     }
   }
-  LN_TS(3);
   // ---- row statistics: two passes over the registers; partial sums of the four n-waves meet in LDS ----
   float* const st_sum = reinterpret_cast<float*>(smem + 65536);   // [128 rows][4 n-waves]
   float* const st_sq = st_sum + 512;
@@ -225,7 +215,6 @@ __global__ __launch_bounds__(FTHREADS, 2) void linear_ln512_kernel(const LinearL
   // ---- 16 rows at a time through this wave's 8 KiB: [16 rows][32 pieces of 16 B], piece P of row r at P ^ c(r) with
   //      c(r) = r ^ 2 (r >> 2): conflict-free for the b128 writes (a lane writes pieces 8g..8g+7 of row i16) and for the
   //      row-major b128 reads (two rows per instruction) under gfx950's 16-lane service groups ----
-  LN_TS(4);
   char* const mine = smem + wave * 8192;
   f32x4 gn = f32x4{1.f, 1.f, 1.f, 1.f}, sh = f32x4{0.f, 0.f, 0.f, 0.f};
   if (p.gain) gn = *reinterpret_cast<const f32x4*>(p.gain + col);
@@ -260,20 +249,7 @@ __global__ __launch_bounds__(FTHREADS, 2) void linear_ln512_kernel(const LinearL
           *reinterpret_cast<u32x2*>(b_wave + (int64_t)(rr * (int)p.ldb) * 2 + lane_b) = u32x2{pack_bf16x2(o.x, o.y), pack_bf16x2(o.z, o.w)};
       }
     }
-#ifdef LN_PROBE_TIMES
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    ts[5 + (fm & 1)] = wall_clock64();   // (5: passes 0 / 2 done, 6: passes 1 / 3 done -- the last two survive)
-#endif
   }
-#ifdef LN_PROBE_TIMES
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  ts[7] = wall_clock64();
-  if (p.xb && (tid & 63) == 0) {   // one record per wave in the (unused by the probe) bf16 shadow: row m0 + wave
-    uint64_t* rec = reinterpret_cast<uint64_t*>(p.xb + (m0 + wave) * p.ldb);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) rec[i] = ts[i];
-  }
-#endif
 }
 
 }  // namespace

@@ -2,8 +2,7 @@
 (linear_kernel_256a4, gemm_a4.hip) as ONE inline-asm block -- every instruction, register and wait placed here, nothing left
 to hipcc's scheduler.
 
-    python tools/gen_gemm_asm.py [variant ...]     writes aurora_amd/csrc/gemm_a4_loop.inc (variant 0; committed: the build does
-                                                   not run this) / gemm_a4_loop_v<N>.inc (experiments, not committed)
+    python tools/gen_gemm_asm.py     writes aurora_amd/csrc/gemm_a4_loop.inc (committed: the build does not run this)
 
 Tile: 4 waves (one per SIMD, 512 registers each), wave tile 128 x 128 = 8 x 8 MFMA tiles of 16 x 16 (v_mfma_f32_16x16x32_bf16);
 256 accumulators in a[0:255]; K in units of 64 = two 32-wide stages, each an LDS image of gemm.hip's 256 x 256 kernels
@@ -25,9 +24,17 @@ flight, two barriers per unit:
   H2: 64 MFMAs on set B; the 16 fragment reads of stage 2u+2 -> set A, the 8 pieces of stage 2u+5 into the image of stage 2u+1.
       s_waitcnt vmcnt(16) lgkmcnt(0); s_barrier.
 A piece has two halves (~2,100 cycles) to land.  (With all 16 pieces of a unit issued in H2 and one barrier per unit -- a piece
-then has ONE half -- the loop ran at 21.4-22 cycles per MFMA: the wait at the barrier, not the issue.)
+then has ONE half -- the loop ran at 21.4-22 cycles per MFMA: the wait at the barrier, not the issue.)  Placements of the same
+instructions that were tried against SCHEDULE below: a DMA piece behind every 8th MFMA instead of every 4th (ds=8), and the
+fragment reads behind every 2nd instead of every 4th (rs1 = rs2 = 2, r01 = r02 = 1, ds=8, d0=4): both 17.2-18.2 cycles per MFMA, wall
+clock within 1 % of what ships.  (Those variants and the stamp probe that timed them, tools/gemm_a4_stamps.py, left the tree
+together; commit 7bff69c still has them.)
 """
-import sys
+from pathlib import Path
+
+# what ships ("variant 0" in the .inc's first line and in the logs): a four-stage ring, two barriers per unit; the fragment reads
+# behind every rs-th MFMA of a half from MFMA r0 on, a DMA piece behind every ds-th from MFMA d0 on (M0 one MFMA ahead of its load)
+SCHEDULE = dict(ring=1, rs1=4, r01=0, rs2=4, r02=0, ds=4, d0=2)
 
 # ---- register map (VGPRs; the compiler keeps its own values below V_FIRST) ----
 V_FIRST = 48
@@ -82,8 +89,11 @@ def half(wset, xset, fillers):
     return out
 
 
-def build(variant):
-    ab = VARIANTS[variant]
+def build(variant=0):
+    # (the parameter is left from the days of variants 1-3: tests/test_generated_sources.py calls build(0), and the number is
+    #  part of the committed .inc's first line)
+    assert variant == 0, "only the schedule that ships is generated"
+    ab = SCHEDULE
     lines = []
     emit = lines.append
     # ---------------- prologue: units 0 and 1 on their way, accumulators cleared, unit 0 published, fragments of stage 0 ----------------
@@ -119,14 +129,11 @@ def build(variant):
     for f in range(8):
         emit(read_x(XA, f, 0))
     emit("s_waitcnt lgkmcnt(0)")
-    if ab.get("ring"):
-        emit("s_barrier")          # (the first half refills stage 0's image: everybody has read it)
+    emit("s_barrier")          # (the first half refills stage 0's image: everybody has read it)
     emit("s_memtime %[t1]")
     # ---------------- the loop: one unit per iteration ----------------
     emit("1:")
-    rs1, r01 = ab.get("rs1", 4), ab.get("r01", 0)
-    rs2, r02 = ab.get("rs2", 4), ab.get("r02", 0)
-    ds, d0 = ab.get("ds", 4), ab.get("d0", 2)
+    rs1, r01, rs2, r02, ds, d0 = (ab[k] for k in ("rs1", "r01", "rs2", "r02", "ds", "d0"))
     rd1 = [read_w(WB, f, 1) for f in range(8)] + [read_x(XB, f, 1) for f in range(8)]
     rd2 = [read_w(WA, f, 0) for f in range(8)] + [read_x(XA, f, 0) for f in range(8)]
     fill = {}
@@ -136,36 +143,30 @@ def build(variant):
     emit("s_min_u32 %[ka], %[knext], %[kmax]")
     emit("s_add_u32 %[kb], %[ka], 64")
     emit("s_add_u32 %[knext], %[knext], 128")
-    if ab.get("ring"):
-        # Ring of four stages, two barriers per unit: H1 refills the image of stage 2u (read in H2 of the unit before) with stage
-        # 2u + 4, H2 the image of stage 2u + 1 (read in H1) with stage 2u + 5 -- three stages (96 KiB) in flight, a piece has two
-        # halves (~2,100 cycles) to land; at the end of a half everything but the two youngest stages' pieces has landed.
-        for p in range(8):
-            a, b = dma_piece(p)
-            fill.setdefault(d0 + ds * p - 1, []).append(a)
-            fill.setdefault(d0 + ds * p, []).append(b)
-        assert all(0 <= k < 64 for k in fill), sorted(fill)
-        lines.extend(half(WA, XA, fill))
-        emit("s_waitcnt vmcnt(16) lgkmcnt(0)")
-    else:
-        lines.extend(half(WA, XA, fill))
-        emit("s_waitcnt vmcnt(0) lgkmcnt(0)")
+    # Ring of four stages, two barriers per unit: H1 refills the image of stage 2u (read in H2 of the unit before) with stage
+    # 2u + 4, H2 the image of stage 2u + 1 (read in H1) with stage 2u + 5 -- three stages (96 KiB) in flight, a piece has two
+    # halves (~2,100 cycles) to land; at the end of a half everything but the two youngest stages' pieces has landed.
+    for p in range(8):
+        a, b = dma_piece(p)
+        fill.setdefault(d0 + ds * p - 1, []).append(a)      # M0 one MFMA ahead of its load
+        fill.setdefault(d0 + ds * p, []).append(b)
+    assert all(0 <= k < 64 for k in fill), sorted(fill)
+    lines.extend(half(WA, XA, fill))
+    emit("s_waitcnt vmcnt(16) lgkmcnt(0)")
     emit("s_barrier")
     emit(f"v_xor_b32 v{RX}, 0x10000, v{RX}")
     emit(f"v_xor_b32 v{RW}, 0x10000, v{RW}")
     fill = {}
     for k, ins in enumerate(rd2):
         fill.setdefault(r02 + rs2 * k, []).append(ins)
-    for p in (range(8, 16) if ab.get("ring") else range(16)):
+    for p in range(8, 16):
         a, b = dma_piece(p)
-        q = p - 8 if ab.get("ring") else p
-        fill.setdefault(d0 + ds * q - 1, []).append(a)      # M0 one MFMA ahead of its load
-        fill.setdefault(d0 + ds * q, []).append(b)
+        fill.setdefault(d0 + ds * (p - 8) - 1, []).append(a)
+        fill.setdefault(d0 + ds * (p - 8), []).append(b)
     assert all(0 <= k < 64 for k in fill), sorted(fill)
     lines.extend(half(WB, XB, fill))
-    if ab.get("ring"):
-        emit("s_waitcnt vmcnt(16) lgkmcnt(0)")
-        emit("s_barrier")
+    emit("s_waitcnt vmcnt(16) lgkmcnt(0)")
+    emit("s_barrier")
     emit("s_xor_b32 %[ldsw], %[ldsw], 0x10000")
     emit("s_sub_u32 %[count], %[count], 1")
     emit("s_cmp_lg_u32 %[count], 0")
@@ -186,25 +187,12 @@ def build(variant):
     for l in lines:
         out.append(f'    "{l}\\n\\t" \\')
     out.append('    ""')
-    if variant == 0:
-        names = [f'"v{i}"' for i in range(V_FIRST, V_END)] + [f'"a{i}"' for i in range(256)]
-        out.append("#define A4_CLOBBERS \\")
-        for i in range(0, len(names), 16):
-            out.append("    " + ", ".join(names[i:i + 16]) + (", \\" if i + 16 < len(names) else ""))
+    names = [f'"v{i}"' for i in range(V_FIRST, V_END)] + [f'"a{i}"' for i in range(256)]
+    out.append("#define A4_CLOBBERS \\")
+    for i in range(0, len(names), 16):
+        out.append("    " + ", ".join(names[i:i + 16]) + (", \\" if i + 16 < len(names) else ""))
     return "\n".join(out) + "\n"
 
 
-# variant 0 ships; the others are placement experiments of the same instructions (tools/gemm_a4_stamps.py)
-VARIANTS = {
-    0: dict(ring=1, rs1=4, r01=0, rs2=4, r02=0, ds=4, d0=2),   # four-stage ring, two barriers per unit; a DMA piece behind every 4th MFMA of the first half of each half
-    1: dict(ring=1, rs1=4, r01=0, rs2=4, r02=0, ds=8, d0=2),   # ... every 8th (17.2-18.2 cycles per MFMA, wall clock within 1 % of variant 0)
-    2: dict(ring=1, rs1=2, r01=1, rs2=2, r02=1, ds=8, d0=4),   # reads behind every 2nd MFMA (the same)
-    3: dict(rs1=4, r01=0, rs2=4, r02=0, ds=4, d0=2),           # two units, one barrier per unit, all 16 pieces in H2: 21.4-22 cycles per MFMA (a piece has one half to land)
-}
-
 if __name__ == "__main__":
-    from pathlib import Path
-    dst = Path(__file__).resolve().parents[1] / "aurora_amd" / "csrc"
-    which = [int(a) for a in sys.argv[1:]] or [0]
-    for v in which:
-        (dst / ("gemm_a4_loop.inc" if v == 0 else f"gemm_a4_loop_v{v}.inc")).write_text(build(v))
+    (Path(__file__).resolve().parents[1] / "aurora_amd" / "csrc" / "gemm_a4_loop.inc").write_text(build())
