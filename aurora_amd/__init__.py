@@ -5,12 +5,14 @@ without moving the predictions off the device: only its search windows travel (a
 prediction against truth on the device (aurora_amd/scores.py) and `ensemble_scores` an ensemble of them (CRPS, spread, rank
 histogram: aurora_amd/ensemble.py), and `spectra` gives the zonal power spectra of a prediction, of the truth and of the error
 (aurora_amd/spectra.py), and `event_scores` the contingency tables and the fractions skill score of threshold exceedances
-(aurora_amd/events.py); the reference has no counterpart.
+(aurora_amd/events.py), and `FieldStats` accumulates per-point statistics over the steps of a roll-out or the members of an
+ensemble as maps (aurora_amd/fieldstats.py); the reference has no counterpart.
 """
 
 from aurora_amd.batch import Batch, Metadata
 from aurora_amd.ensemble import EnsembleScores, ensemble_scores
 from aurora_amd.events import EventScores, event_scores
+from aurora_amd.fieldstats import FieldStats
 from aurora_amd.model.aurora import (
     Aurora,
     Aurora12hPretrained,
@@ -47,5 +49,6 @@ __all__ = [
     "Spectra",
     "event_scores",
     "EventScores",
+    "FieldStats",
     "Tracker",
 ]

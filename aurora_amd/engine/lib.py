@@ -135,6 +135,9 @@ _SIGNATURES = {
     "aurora_hip_event_scores_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "aurora_hip_event_scores": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
                                         c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
+    "aurora_hip_field_stats_update": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_int,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -945,6 +948,82 @@ def event_rowsums(pred: list[torch.Tensor], truth: list[torch.Tensor], threshold
             _check(load().aurora_hip_event_scores(base, base + 8 * n, n, n_lat, n_lon, _ptr(thresholds), T, host_scales, S,
                                                   1 if below else 0, _ptr(rowsums), _ptr(valid), None, 0, _stream()))
     return rowsums, valid
+
+
+# ---- per-point statistics over a sequence of planes (aurora_hip_field_stats_update) -----------------------------------
+FIELD_STATS_MAX_SAMPLES, FIELD_STATS_MAX_THRESHOLDS = 64, 8
+# state array -> (dtype, per threshold); include/aurora_hip.h has the meanings
+FIELD_STATS_STATE = {"n": (torch.int32, False), "origin": (torch.float32, False), "s1": (torch.float64, False),
+                     "s2": (torch.float64, False), "vmin": (torch.float32, False), "vmax": (torch.float32, False),
+                     "argmin": (torch.int32, False), "argmax": (torch.int32, False), "exceed": (torch.int32, True),
+                     "run": (torch.int32, True), "longest": (torch.int32, True)}
+
+
+def field_stats_update(samples: list[list[torch.Tensor]], ref: Optional[list[torch.Tensor]],
+                       second: Optional[list[list[Optional[torch.Tensor]]]], thresholds: Optional[torch.Tensor], below: bool,
+                       sample_index: torch.Tensor, state: dict[str, torch.Tensor]) -> None:
+    """Applies S samples of every plane, in order, to the per-point `state` (include/aurora_hip.h: count, origin, shifted
+    sums, minimum / maximum and the sample that reached them, exceedances and run lengths), in ONE
+    aurora_hip_field_stats_update call, and advances `sample_index` on the device.
+
+    samples: S lists (1 <= S <= 64) of fp32 (..., n_lat, n_lon) tensors on one device with row-major contiguous planes (any
+    leading strides, any 4-byte plane alignment), the same leading shapes in each list; ref: one such list or None (v = x -
+    r); second: S such lists or None, an entry None where a field has no second operand (x <- sqrt(x^2 + b^2) elsewhere);
+    thresholds: contiguous (n_planes, T) fp32 on that device, T <= 8, or None; sample_index: one int64 on the device; state:
+    the arrays of FIELD_STATS_STATE, contiguous (n_planes, n_points) -- (n_planes, T, n_points) per threshold --, zero before
+    the first call.  The plane-pointer table is cached by address as in `scores_sums`.  Nothing is allocated and the host
+    does not wait for the device."""
+    S = len(samples)
+    assert 1 <= S <= FIELD_STATS_MAX_SAMPLES, f"field_stats_update: 1..{FIELD_STATS_MAX_SAMPLES} samples a call, got {S}"
+    assert samples[0], "field_stats_update: no fields"
+    dev = sample_index.device
+    assert sample_index.is_cuda and sample_index.dtype == torch.int64 and sample_index.numel() == 1, \
+        "field_stats_update: sample_index must be one int64 on the device"
+    n_lat, n_lon = samples[0][0].shape[-2:]
+    lists = [(f"sample {s}", fs) for s, fs in enumerate(samples)] + ([("reference", ref)] if ref is not None else [])
+    for _, fs in lists:
+        assert len(fs) == len(samples[0]), "field_stats_update: the lists differ in length"
+        for v, p in zip(fs, samples[0]):
+            assert v.device == dev, "field_stats_update: every tensor must be on the device of sample_index"
+            assert v.shape == p.shape, f"field_stats_update: shapes differ ({tuple(v.shape)} against {tuple(p.shape)})"
+    addresses = [a for what, fs in lists for a in _plane_addresses(fs, n_lat, n_lon, what)]
+    n = len(addresses) // len(lists)
+    if second is not None:
+        assert len(second) == S and all(len(fs) == len(samples[0]) for fs in second), \
+            "field_stats_update: the second operands differ from the samples in number"
+        for s, fs in enumerate(second):
+            for v, p in zip(fs, samples[s]):
+                if v is None:
+                    addresses += [0] * (p.numel() // (n_lat * n_lon))
+                    continue
+                assert v.device == dev and v.shape == p.shape, "field_stats_update: a second operand differs from its sample"
+                addresses += _plane_addresses([v], n_lat, n_lon, "second operand")
+    T = 0
+    if thresholds is not None:
+        assert thresholds.device == dev and thresholds.dtype == torch.float32 and thresholds.dim() == 2 and \
+            thresholds.is_contiguous() and thresholds.shape[0] == n, \
+            f"field_stats_update: thresholds must be a contiguous ({n}, T) fp32 matrix on the device"
+        T = thresholds.shape[1]
+        assert T <= FIELD_STATS_MAX_THRESHOLDS, f"field_stats_update: at most {FIELD_STATS_MAX_THRESHOLDS} thresholds, got {T}"
+    for name, (dt, per_thr) in FIELD_STATS_STATE.items():
+        if per_thr and T == 0:
+            continue
+        t = state[name]
+        want = (n, T, n_lat * n_lon) if per_thr else (n, n_lat * n_lon)
+        assert t.device == dev and t.dtype == dt and t.is_contiguous() and t.numel() == int(np.prod(want)), \
+            f"field_stats_update: state {name!r} must be contiguous {dt} of {want} on the device"
+    if n == 0:
+        return
+    with torch.cuda.device(dev):
+        table = _plane_table(tuple(addresses), dev)
+        base = table.data_ptr()
+        ref_at = base + 8 * S * n if ref is not None else None
+        second_at = base + 8 * (S + (ref is not None)) * n if second is not None else None
+        arrays = [_ptr(state[k]) if (T or not per_thr) else None for k, (_, per_thr) in FIELD_STATS_STATE.items()]
+        with _Timed("field_stats", float(n * n_lat * n_lon * (4 * S + 2 * (36 + 12 * T)))):
+            _check(load().aurora_hip_field_stats_update(base, ref_at, second_at, S, n, n_lat * n_lon,
+                                                        _ptr(thresholds) if T else None, T, 1 if below else 0,
+                                                        _ptr(sample_index), *arrays, _stream()))
 
 
 # ---- model handle (one forecast step behind the C ABI) ------------------------------------------------------

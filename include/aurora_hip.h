@@ -777,6 +777,45 @@ int aurora_hip_event_scores(const float* const* pred_planes, const float* const*
                             int n_lon, const float* thresholds, int n_thresholds, const int32_t* scales, int n_scales, int below,
                             int64_t* rowsums, int64_t* valid, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- per-point statistics over a sequence of planes on the device (aurora_amd.FieldStats; not in the reference) -----------
+ * The scorers above reduce a plane over space; this one reduces over SAMPLES (roll-out steps, ensemble members, forecast -
+ * truth pairs) and keeps the map.  A plane is n_points = n_lat x n_lon fp32 values; a call brings n_samples (1..64) samples
+ * of each of n_planes planes and applies them, in sample order, to a state the caller owns.
+ * Sample value of a point, with x the value in sample_planes:
+ *   second operand b given:  x <- fp32(sqrt((double)x^2 + (double)b^2))          (a wind speed from its components)
+ *   v = (double)x - (double)r with a reference r, else v = (double)x;   w = fp32(v)  (= v exactly without a reference)
+ * A sample whose x, b or r (or derived x) is not finite is SKIPPED at that point: nothing of the point's state changes.
+ * State: arrays [plane][point], contiguous; valid when zero-filled (n = 0 makes origin, vmin, vmax, argmin, argmax unset):
+ *   n        int32   valid samples so far
+ *   origin   fp32    w of the first valid sample
+ *   s1, s2   fp64    sum d and sum d^2 with d = v - (double)origin: SHIFTED sums (differences, never raw values), so that
+ *                    mean = origin + s1 / n, var = (s2 - s1^2 / n) / (n - ddof), mean square = (s2 + 2 origin s1 + n origin^2) / n
+ *   vmin, vmax       fp32   minimum and maximum of w
+ *   argmin, argmax   int32  global index of the FIRST sample that reached the minimum / maximum
+ *   exceed, run, longest   int32 [plane][t][point], t < T: with the event w >= thresholds[plane T + t] (<= with below != 0; a
+ *                    NaN threshold: no event) the number of events, the current run of consecutive events and the longest
+ *                    run.  A skipped sample neither extends nor breaks a run.
+ * The global index of the call's first sample is read from *sample_index (a DEVICE int64) by the main launch; a second,
+ * one-thread launch then adds n_samples to it.  No host counter: a captured call replays with the right indices.  Indices
+ * are kept as int32.
+ * sample_planes: DEVICE array of n_samples x n_planes plane pointers, sample-major (sample s, plane k at [s n_planes + k]);
+ * ref_planes: n_planes pointers or NULL; second_planes: n_samples x n_planes pointers or NULL; a NULL entry of either means
+ * "none for this plane".  All plane pointers 4-byte aligned; 16-byte loads and stores are used for a plane where
+ * n_points % 4 == 0 and every pointer involved is 16-byte aligned (the same elements either way).  thresholds: n_planes x T
+ * device floats, 0 <= T <= 8 (T = 0: thresholds, exceed, run, longest may be NULL).  s1, s2, sample_index 8-byte aligned.
+ * Determinism: nothing is reduced across threads.  A point's state depends on its own samples in their order alone: not on
+ * n_planes, on the other planes, on pointer alignment, or on how the samples are grouped into calls (one call with S samples
+ * leaves the bits that S calls with one sample leave).
+ * One main launch over all planes and samples (a point's state is read once and written once: 4 n_samples + 2 (36 + 12 T)
+ * bytes per point) and the one-thread launch.  Arguments are checked before anything is enqueued (AURORA_E_ARG and
+ * aurora_hip_last_error()).  n_planes = 0 is a no-op.  The inputs are not modified.  No workspace, no atomics, no host
+ * synchronisation, no allocation, no environment variable: capturable in a hipGraph. */
+int aurora_hip_field_stats_update(const float* const* sample_planes, const float* const* ref_planes,
+                                  const float* const* second_planes, int n_samples, int n_planes, int64_t n_points,
+                                  const float* thresholds, int n_thresholds, int below, int64_t* sample_index, int32_t* n,
+                                  float* origin, double* s1, double* s2, float* vmin, float* vmax, int32_t* argmin,
+                                  int32_t* argmax, int32_t* exceed, int32_t* run, int32_t* longest, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
