@@ -5,8 +5,9 @@ without moving the predictions off the device: only its search windows travel (a
 prediction against truth on the device (aurora_amd/scores.py) and `ensemble_scores` an ensemble of them (CRPS, spread, rank
 histogram: aurora_amd/ensemble.py), and `spectra` gives the zonal power spectra of a prediction, of the truth and of the error
 (aurora_amd/spectra.py), and `event_scores` the contingency tables and the fractions skill score of threshold exceedances
-(aurora_amd/events.py), and `FieldStats` accumulates per-point statistics over the steps of a roll-out or the members of an
-ensemble as maps (aurora_amd/fieldstats.py); the reference has no counterpart.
+(aurora_amd/events.py), and `probability_scores` the Brier score, reliability diagram and ROC of an ensemble's event
+probabilities (aurora_amd/probability.py), and `FieldStats` accumulates per-point statistics over the steps of a roll-out or
+the members of an ensemble as maps (aurora_amd/fieldstats.py); the reference has no counterpart.
 """
 
 from aurora_amd.batch import Batch, Metadata
@@ -23,6 +24,7 @@ from aurora_amd.model.aurora import (
     AuroraSmallPretrained,
     AuroraWave,
 )
+from aurora_amd.probability import ProbabilityScores, probability_scores
 from aurora_amd.rollout import rollout, write_rollout
 from aurora_amd.scores import Scores, scores
 from aurora_amd.spectra import Spectra, spectra
@@ -49,6 +51,8 @@ __all__ = [
     "Spectra",
     "event_scores",
     "EventScores",
+    "probability_scores",
+    "ProbabilityScores",
     "FieldStats",
     "Tracker",
 ]

@@ -138,6 +138,8 @@ _SIGNATURES = {
     "aurora_hip_field_stats_update": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int64, c_void_p, c_int, c_int,
                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "aurora_hip_probability_scores": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
+                                              c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -948,6 +950,45 @@ def event_rowsums(pred: list[torch.Tensor], truth: list[torch.Tensor], threshold
             _check(load().aurora_hip_event_scores(base, base + 8 * n, n, n_lat, n_lon, _ptr(thresholds), T, host_scales, S,
                                                   1 if below else 0, _ptr(rowsums), _ptr(valid), None, 0, _stream()))
     return rowsums, valid
+
+
+# ---- event probabilities of an ensemble (aurora_hip_probability_scores) -----------------------------------------------
+def probability_rows(members: list[list[torch.Tensor]], truth: list[torch.Tensor], thresholds: torch.Tensor,
+                     below: bool = False) -> torch.Tensor:
+    """The integer table of include/aurora_hip.h -- per row of every plane, threshold and (event observed o, k of M members
+    forecasting it) the number of valid points -- in ONE aurora_hip_probability_scores call: an (n_planes, n_lat, T, 2, M + 1)
+    int32 tensor on the device.
+
+    members: M lists (2 <= M <= 64), each like `truth`: fp32 (..., n_lat, n_lon) tensors on one device with row-major
+    contiguous planes (any leading strides, any 4-byte plane alignment) and the leading shapes of `truth`; thresholds:
+    contiguous (n_planes, T) fp32 on that device (NaN: no event).  The plane-pointer table is cached by address as in
+    `scores_sums`.  Nothing but the result is allocated and the host does not wait for the device."""
+    assert thresholds.is_cuda and thresholds.dtype == torch.float32 and thresholds.dim() == 2 and thresholds.is_contiguous(), \
+        "probability_rows: thresholds must be a contiguous (n_planes, T) fp32 matrix on the device"
+    dev, (n_thr_planes, T) = thresholds.device, thresholds.shape
+    M = len(members)
+    assert 2 <= M <= ENSEMBLE_MAX_MEMBERS, f"probability_rows: members must hold 2..{ENSEMBLE_MAX_MEMBERS} lists, got {M}"
+    assert 1 <= T <= EVENT_MAX_THRESHOLDS, f"probability_rows: 1..{EVENT_MAX_THRESHOLDS} thresholds, got {T}"
+    assert truth and all(len(fs) == len(truth) for fs in members), "probability_rows: the lists differ in length or are empty"
+    for fs in (truth, *members):
+        for v, t in zip(fs, truth):
+            assert v.device == dev, "probability_rows: every tensor must be on the device of thresholds"
+            assert v.shape == t.shape, f"probability_rows: shapes differ ({tuple(v.shape)} against {tuple(t.shape)})"
+    n_lat, n_lon = truth[0].shape[-2:]
+    addresses = [_plane_addresses(fs, n_lat, n_lon, f"member {m}") for m, fs in enumerate(members)]
+    addresses.append(_plane_addresses(truth, n_lat, n_lon, "truth"))
+    n = len(addresses[-1])
+    assert n == n_thr_planes, f"probability_rows: {n} planes but thresholds for {n_thr_planes}"
+    rows = torch.empty(n, n_lat, T, 2, M + 1, dtype=torch.int32, device=dev)
+    if n == 0:
+        return rows
+    with torch.cuda.device(dev):
+        table = _plane_table(tuple(a for row in addresses for a in row), dev)
+        base = table.data_ptr()
+        with _Timed("probability_scores", 0.0):
+            _check(load().aurora_hip_probability_scores(base, base + 8 * M * n, M, n, n_lat, n_lon, _ptr(thresholds), T,
+                                                        1 if below else 0, _ptr(rows), _stream()))
+    return rows
 
 
 # ---- per-point statistics over a sequence of planes (aurora_hip_field_stats_update) -----------------------------------

@@ -816,6 +816,36 @@ int aurora_hip_field_stats_update(const float* const* sample_planes, const float
                                   float* origin, double* s1, double* s2, float* vmin, float* vmax, int32_t* argmin,
                                   int32_t* argmax, int32_t* exceed, int32_t* run, int32_t* longest, void* stream);
 
+/* ---- event probabilities of an ENSEMBLE on the device (aurora_amd.probability_scores: Brier score and its decomposition,
+ * reliability diagram, ROC; not in the reference) ----------------------------------------------------------------------------
+ * Planes, members and thresholds as above: for every plane p < n_planes the M = n_members member planes x_1 .. x_M and the
+ * truth plane y are read once.  A point is VALID where y and all M members are finite.  For the threshold
+ * thr = thresholds[p T + t] (fp32, compared in fp32), over the valid points:
+ *   k(i,j) = #{m : x_m >= thr} in 0..M,    o(i,j) = [y >= thr]       (both <= with below != 0; a NaN threshold: k = 0, o = 0)
+ *   rows[(((p n_lat + i) T + t) 2 + o) (M + 1) + k] = the number of valid points of row i with that (o, k)
+ * -- the whole output.  The ensemble's forecast probability of the event at a point is k / M, so with row weights w_i and
+ * W[o][k] = sum_i w_i rows[i][t][o][k], n_k = W[0][k] + W[1][k], N = sum_k n_k, p_k = k / M, the caller forms
+ *   Brier score = sum_k (W[1][k] (1 - p_k)^2 + W[0][k] p_k^2) / N,   base rate obar = sum_k W[1][k] / N,
+ *   observed frequency obar_k = W[1][k] / n_k,   reliability = sum_k n_k (p_k - obar_k)^2 / N,
+ *   resolution = sum_k n_k (obar_k - obar)^2 / N,   uncertainty = obar (1 - obar)     (Brier = reliability - resolution +
+ *   uncertainty exactly: the forecast takes M + 1 values only),   and the ROC points of "warn when k >= c":
+ *   hit rate = sum_{k >= c} W[1][k] / sum_k W[1][k],  false alarm rate likewise from W[0]    (aurora_amd/probability.py).
+ * Every number is an exact integer (an entry <= n_lon < 2^31), so the table does not depend on any order of addition and is
+ * repeatable bit for bit; a plane's table depends on its own values and thresholds alone -- not on n_planes, on the other
+ * planes, or on pointer alignment -- and the order of the members does not matter.  The bins of a (row, t) add up to the
+ * row's valid points; a row or plane without a valid point gives zeros.
+ * member_planes: DEVICE array of n_members x n_planes plane pointers, member-major (member m, plane p at [m n_planes + p]);
+ * truth_planes: n_planes pointers (all 4-byte aligned; 16-byte loads are used for a plane where every pointer of it is 16-byte
+ * aligned and n_lon % 4 == 0: the same elements either way).  thresholds: n_planes x T DEVICE floats.  2 <= n_members <= 64,
+ * 1 <= T <= 8, n_lat >= 1, 1 <= n_lon < 2^31.  rows: n_planes x n_lat x T x 2 x (M + 1) device int32, 4-byte aligned, no
+ * initialisation needed: every entry is written, with plain stores, by the wavefront that owns the row (no global atomics,
+ * no clearing launch).  There is no workspace and no plane-sized temporary.  Arguments are checked before anything is enqueued
+ * (AURORA_E_ARG and aurora_hip_last_error()).  n_planes = 0 is a no-op.  The inputs are not modified.  One launch; the call
+ * allocates nothing, does not wait for the device and reads no environment variable: capturable in a hipGraph. */
+int aurora_hip_probability_scores(const float* const* member_planes, const float* const* truth_planes, int n_members,
+                                  int n_planes, int n_lat, int n_lon, const float* thresholds, int n_thresholds, int below,
+                                  int32_t* rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
