@@ -7,10 +7,13 @@ histogram: aurora_amd/ensemble.py), and `spectra` gives the zonal power spectra 
 (aurora_amd/spectra.py), and `event_scores` the contingency tables and the fractions skill score of threshold exceedances
 (aurora_amd/events.py), and `probability_scores` the Brier score, reliability diagram and ROC of an ensemble's event
 probabilities (aurora_amd/probability.py), and `FieldStats` accumulates per-point statistics over the steps of a roll-out or
-the members of an ensemble as maps (aurora_amd/fieldstats.py); the reference has no counterpart.
+the members of an ensemble as maps (aurora_amd/fieldstats.py), and `diagnostics` forms the derived fields all of them can
+then take -- vorticity, divergence, wind speed, integrated vapour transport -- as a `Batch` (aurora_amd/diagnostics.py); the
+reference has no counterpart.
 """
 
 from aurora_amd.batch import Batch, Metadata
+from aurora_amd.diagnostics import diagnostics
 from aurora_amd.ensemble import EnsembleScores, ensemble_scores
 from aurora_amd.events import EventScores, event_scores
 from aurora_amd.fieldstats import FieldStats
@@ -54,5 +57,6 @@ __all__ = [
     "probability_scores",
     "ProbabilityScores",
     "FieldStats",
+    "diagnostics",
     "Tracker",
 ]

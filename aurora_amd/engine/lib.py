@@ -140,6 +140,9 @@ _SIGNATURES = {
                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "aurora_hip_probability_scores": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p,
                                               c_void_p]),
+    "aurora_hip_diagnostics": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_double, c_int,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
+                                       c_void_p, c_int, c_int, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1067,8 +1070,81 @@ def field_stats_update(samples: list[list[torch.Tensor]], ref: Optional[list[tor
                                                         _ptr(sample_index), *arrays, _stream()))
 
 
+# ---- derived fields (aurora_hip_diagnostics) ----------------------------------------------------------------------------
+DIAGNOSTICS_MAX_LEVELS = 64
+
+
+def diagnostics(n_lat: int, n_lon: int, *, u: Optional[list[torch.Tensor]] = None, v: Optional[list[torch.Tensor]] = None,
+                vo: Optional[list[torch.Tensor]] = None, div: Optional[list[torch.Tensor]] = None,
+                ws: Optional[list[torch.Tensor]] = None, row_table: Optional[torch.Tensor] = None, L: float = 0.0,
+                wrap: bool = False, q: Optional[list[torch.Tensor]] = None, col_u: Optional[list[torch.Tensor]] = None,
+                col_v: Optional[list[torch.Tensor]] = None, tcwv: Optional[list[torch.Tensor]] = None,
+                ivtu: Optional[list[torch.Tensor]] = None, ivtv: Optional[list[torch.Tensor]] = None,
+                ivt: Optional[list[torch.Tensor]] = None, level_w: Optional[torch.Tensor] = None) -> None:
+    """Vorticity, divergence and wind speed of the wind planes (u, v) into (vo, div, ws), and the vertical integrals of the
+    columns (q, col_u, col_v) into (tcwv, ivtu, ivtv, ivt), in ONE aurora_hip_diagnostics call: one launch per group
+    (include/aurora_hip.h has the arithmetic).
+
+    Every argument but the tables is a list of fp32 (..., n_lat, n_lon) tensors on one device with row-major contiguous
+    planes (any leading strides, any 4-byte plane alignment) or None: an output that is None is skipped (an entry None of
+    vo, div or ws, given entry for entry with u, skips it for the planes of that entry), and u = None / q = None leaves
+    the group out.  The planes of a list are counted in row-major order of the leading dimensions: a wind
+    output holds as many planes as u, and q (col_u, col_v) holds C = len(level_w) planes for every plane of a column
+    output, levels fastest.  row_table: contiguous (n_lat, 4) fp64 on the device (None for wind speed alone); level_w: (C,)
+    fp64 on the device.  An output must not share memory with an input.  The plane-pointer table is cached by address as
+    in `scores_sums`.  Nothing is allocated and the host does not wait for the device."""
+    groups = (("u", u), ("v", v), ("vo", vo), ("div", div), ("ws", ws), ("q", q), ("col_u", col_u), ("col_v", col_v),
+              ("tcwv", tcwv), ("ivtu", ivtu), ("ivtv", ivtv), ("ivt", ivt))
+    tensors = [t for _, fs in groups if fs is not None for t in fs if t is not None]
+    if not tensors:
+        return
+    dev = tensors[0].device
+    assert all(t.device == dev for t in tensors), "diagnostics: every tensor must be on one device"
+    for what, t, shape in (("row_table", row_table, (n_lat, 4)), ("level_w", level_w, None)):
+        assert t is None or (t.device == dev and t.dtype == torch.float64 and t.is_contiguous() and
+                             (t.dim() == 1 if shape is None else tuple(t.shape) == shape)), \
+            f"diagnostics: {what} must be a contiguous fp64 {'vector' if shape is None else shape} on the device of the fields"
+    addr = {}
+    for what, fs in groups:
+        if fs is None:
+            continue
+        if what in ("vo", "div", "ws") and any(t is None for t in fs):   # an entry None: NULL for the planes of that u entry
+            assert u is not None and len(fs) == len(u), f"diagnostics: {what} with None entries must have an entry per u entry"
+            addr[what] = [a for t, like in zip(fs, u) for a in
+                          ([0] * (like.numel() // (n_lat * n_lon)) if t is None else _plane_addresses([t], n_lat, n_lon, what))]
+        else:
+            addr[what] = _plane_addresses(fs, n_lat, n_lon, what)
+    n_wind, n_cols = len(addr.get("u", ())), 0
+    C = 0 if level_w is None else level_w.shape[0]
+    for what in ("v", "vo", "div", "ws"):
+        assert what not in addr or len(addr[what]) == n_wind, f"diagnostics: {what} holds {len(addr[what])} planes, u {n_wind}"
+    if q is not None:
+        assert C >= 1 and len(addr["q"]) % C == 0, f"diagnostics: q holds {len(addr['q'])} planes, which is no multiple of the {C} level weights"
+        n_cols = len(addr["q"]) // C
+        for what in ("col_u", "col_v"):
+            assert what not in addr or len(addr[what]) == n_cols * C, f"diagnostics: {what} holds {len(addr[what])} planes, q {n_cols * C}"
+        for what in ("tcwv", "ivtu", "ivtv", "ivt"):
+            assert what not in addr or len(addr[what]) == n_cols, f"diagnostics: {what} holds {len(addr[what])} planes for {n_cols} columns"
+    if n_wind == 0 and n_cols == 0:
+        return
+    with torch.cuda.device(dev):
+        order = [what for what, _ in groups if what in addr]
+        table = _plane_table(tuple(a for what in order for a in addr[what]), dev)
+        at, first = {}, table.data_ptr()
+        for what in order:
+            at[what], first = first, first + 8 * len(addr[what])
+        moved = 4.0 * n_lat * n_lon * (n_wind * (2 + sum(k in addr for k in ("vo", "div", "ws"))) +
+                                       n_cols * (C * (1 + sum(k in addr for k in ("col_u", "col_v"))) +
+                                                 sum(k in addr for k in ("tcwv", "ivtu", "ivtv", "ivt"))))
+        with _Timed("diagnostics", moved):
+            _check(load().aurora_hip_diagnostics(at.get("u"), at.get("v"), at.get("vo"), at.get("div"), at.get("ws"), n_wind,
+                                                 _ptr(row_table), float(L), 1 if wrap else 0, at.get("q"), at.get("col_u"),
+                                                 at.get("col_v"), at.get("tcwv"), at.get("ivtu"), at.get("ivtv"), at.get("ivt"),
+                                                 n_cols, C, _ptr(level_w), n_lat, n_lon, _stream()))
+
+
 # ---- model handle (one forecast step behind the C ABI) ------------------------------------------------------
-_PD = ctypes.POINTER(ctypes.c_double)
+_PD =ctypes.POINTER(ctypes.c_double)
 _PF = ctypes.POINTER(ctypes.c_float)
 _PS = ctypes.POINTER(ctypes.c_char_p)
 

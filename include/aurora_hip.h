@@ -846,6 +846,54 @@ int aurora_hip_probability_scores(const float* const* member_planes, const float
                                   int n_planes, int n_lat, int n_lon, const float* thresholds, int n_thresholds, int below,
                                   int32_t* rows, void* stream);
 
+/* ---- derived fields on the device (aurora_amd.diagnostics: relative vorticity, divergence, wind speed, total column water
+ * vapour, integrated vapour transport; not in the reference) -----------------------------------------------------------------
+ * Planes as above (n_lat x n_lon fp32, row-major), n_lat >= 2, n_lon >= 2.  Constants of the caller's tables: the Earth's
+ * radius a = 6 371 229 m and g = 9.80665 m s^-2.  All inputs are fp32; every expression is evaluated in fp64 and the result
+ * is rounded to fp32 ONCE; a result that is not finite is stored as NaN.  Every term of a formula is evaluated, also where
+ * its coefficient is 0, so a NaN or an infinity that a stencil reads propagates by the IEEE rules (inf x 0 = NaN).
+ * WIND GROUP, n_wind items, ONE launch.  Item k reads the planes wind_u[k] and wind_v[k] and writes vo_planes[k],
+ * div_planes[k] and ws_planes[k]; a table that is NULL as a whole, or a NULL entry of a table, skips that output.
+ *   row_table: n_lat x 4 device doubles (A, m0, m1, m2)_i, computed by the caller in fp64 from the latitudes phi_i (radians):
+ *     A_i = 1 / (a cos phi_i), NaN for a pole row (|lat_i| >= 90 - 1e-9 degrees): pole rows come out NaN, no polar-cap formula;
+ *     (m0, m1, m2)_i = (c0 cos phi_{i-1}, c1 cos phi_i, c2 cos phi_{i+1}) with the three-point first-derivative formula for
+ *     unequal spacing, h1 = phi_i - phi_{i-1}, h2 = phi_{i+1} - phi_i:
+ *       c0 = -h2 / (h1 (h1 + h2)),   c1 = (h2 - h1) / (h1 h2),   c2 = h1 / (h2 (h1 + h2));
+ *     first row c = (0, -1 / h2, 1 / h2), last row c = (-1 / h1, 1 / h1, 0); a row that does not exist has the coefficient 0
+ *     and is read at the clamped index.  The true phi enter, so descending latitudes need no sign flag.
+ *   L = 1 / (2 dlambda), dlambda the longitude step in radians.  With wrap != 0 the grid covers the full circle:
+ *     d_lambda f = (f[j + 1 mod n_lon] - f[j - 1 mod n_lon]) L.  With wrap == 0 the grid is regional: interior columns
+ *     likewise, column 0 takes (f[1] - f[0]) 2 L and column n_lon - 1 takes (f[n_lon - 1] - f[n_lon - 2]) 2 L.
+ *   vo  = A_i (d_lambda v - (m0 u[i-1] + m1 u[i] + m2 u[i+1]))            relative vorticity, s^-1
+ *   div = A_i (d_lambda u + (m0 v[i-1] + m1 v[i] + m2 v[i+1]))            horizontal divergence, s^-1
+ *   ws  = fp32(sqrt((double)u^2 + (double)v^2))                           the expression of aurora_hip_field_stats_update
+ *   u and v of an item are read from memory once for all three outputs (a wavefront walks down a strip of 256 columns with a
+ *   rolling three-row window in registers; the east and west neighbours across a lane's four columns are overlapping 4-byte
+ *   loads of the row just fetched).  An item without vo and div reads no neighbour rows.  row_table may be NULL when both
+ *   vo_planes and div_planes are.
+ * COLUMN GROUP, n_cols items (one per batch element), ONE launch.  Item k reads the n_levels planes q_planes[k C + c] and,
+ * where needed, col_u[k C + c] and col_v[k C + c] (C = n_levels, 2..64), and writes, each table and each entry nullable,
+ *   tcwv[k] = sum_c w_c q_c,   ivtu[k] = sum_c w_c q_c u_c,   ivtv[k] = sum_c w_c q_c v_c,   ivt[k] = sqrt(ivtu^2 + ivtv^2)
+ *   with w = level_w: C device doubles in the order of the planes, w_c = 100 (p_next - p_prev) / (2 g) with the neighbours of
+ *   level c in the SORTED pressures (hPa); an end level takes half its one interval; nothing is extrapolated to the surface
+ *   or to the top.  The levels are accumulated in fp64 in level order in registers (the product as (w_c q_c) u_c); ivt is
+ *   formed from the fp64 sums.  col_u (col_v) may be NULL unless ivtu (ivtv) or ivt is asked for.
+ * Either group may be empty (n_wind = 0, n_cols = 0: its pointers are not looked at); both empty is a no-op.  All tables are
+ * DEVICE arrays of plane pointers; the entries of the input tables must not be NULL.  Plane pointers are 4-byte aligned;
+ * 16-byte loads and stores are used for a plane where its pointer is 16-byte aligned and n_lon % 4 == 0 (columns: n_lat x
+ * n_lon % 4 == 0 and every input plane of the item aligned): the same elements either way.  Nothing is reduced across
+ * threads: a point's result depends on the values its formula names alone, is repeatable bit for bit, and does not depend
+ * on the other items of the call or on pointer alignment.  The inputs are not modified.  An output plane must not overlap
+ * an input plane (another wavefront may still have to read the neighbours of a point) or another output plane.
+ * Arguments are checked before anything is enqueued (AURORA_E_ARG and aurora_hip_last_error()).  No workspace, no atomics, no
+ * host synchronisation, no allocation, no environment variable: capturable in a hipGraph. */
+int aurora_hip_diagnostics(const float* const* wind_u, const float* const* wind_v, float* const* vo_planes,
+                           float* const* div_planes, float* const* ws_planes, int n_wind, const double* row_table, double L,
+                           int wrap, const float* const* q_planes, const float* const* col_u, const float* const* col_v,
+                           float* const* tcwv_planes, float* const* ivtu_planes, float* const* ivtv_planes,
+                           float* const* ivt_planes, int n_cols, int n_levels, const double* level_w, int n_lat, int n_lon,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
