@@ -715,41 +715,62 @@ _plane_tables: "OrderedDict[tuple, list]" = OrderedDict()   # plane addresses ->
 _plane_tables_lock = threading.Lock()
 
 
-def _plane_addresses(fields: list[torch.Tensor], n_lat: int, n_lon: int, what: str) -> list[int]:
+def _plane_addresses(fn: str, fields: list[torch.Tensor], n_lat: int, n_lon: int, what: str) -> list[int]:
     """The address of every (n_lat, n_lon) plane of every tensor, in row-major order of the leading dimensions.  A plane
     must be row-major contiguous; the leading dimensions may have any strides (history slices and other views)."""
     out: list[int] = []
     for v in fields:
-        assert v.dim() >= 2 and tuple(v.shape[-2:]) == (n_lat, n_lon), f"scores_sums: a {what} field is {tuple(v.shape)}, not (..., {n_lat}, {n_lon})"
-        assert v.dtype == torch.float32, f"scores_sums: {what} fields must be fp32, got {v.dtype}"
+        assert v.dim() >= 2 and tuple(v.shape[-2:]) == (n_lat, n_lon), f"{fn}: a {what} field is {tuple(v.shape)}, not (..., {n_lat}, {n_lon})"
+        assert v.dtype == torch.float32, f"{fn}: {what} fields must be fp32, got {v.dtype}"
         assert (n_lon == 1 or v.stride(-1) == 1) and (n_lat == 1 or v.stride(-2) == n_lon), \
-            f"scores_sums: the planes of a {what} field are not row-major contiguous (strides {v.stride()})"
+            f"{fn}: the planes of a {what} field are not row-major contiguous (strides {v.stride()})"
         base, lead, strides = v.data_ptr(), v.shape[:-2], v.stride()[:-2]
         out += [base + 4 * sum(i * s for i, s in zip(idx, strides)) for idx in np.ndindex(*lead)]
     return out
 
 
-def _plane_table(addresses: tuple, device: torch.device) -> torch.Tensor:
-    """Device copy of the plane-pointer arrays of a call, cached by the addresses (a roll-out scores the same buffers again
-    and again, and a captured graph must find its table alive and unchanged at every replay).  A miss uploads from pinned
-    memory without synchronising; during stream capture a miss is an error, and a table a graph uses is never evicted."""
-    key = (device.index, addresses)
+def _cached_table(tables: OrderedDict, limit: int, key: tuple, make, device: torch.device, on_capture: str) -> torch.Tensor:
+    """Device copy of a small host table, kept in `tables` under `key` (a roll-out asks for the same one again and again, and a
+    captured graph must find its table alive and unchanged at every replay).  A miss uploads `make()` from pinned memory without
+    synchronising; during stream capture a miss is an error, and a table a graph uses is never evicted; the others leave least
+    recently used first once more than `limit` are kept."""
     capturing = torch.cuda.is_current_stream_capturing()
     with _plane_tables_lock:
-        hit = _plane_tables.get(key)
+        hit = tables.get(key)
         if hit is not None:
-            _plane_tables.move_to_end(key)
+            tables.move_to_end(key)
             hit[1] = hit[1] or capturing
             return hit[0]
     if capturing:
-        raise RuntimeError("scores_sums: call once on these tensors before capturing a graph (the plane-pointer table "
-                           "is uploaded on the first call, which a captured graph cannot replay)")
-    table = torch.tensor(addresses, dtype=torch.int64).pin_memory().to(device, non_blocking=True)
+        raise RuntimeError(on_capture)
+    table = make().pin_memory().to(device, non_blocking=True)
     with _plane_tables_lock:
-        _plane_tables[key] = [table, False]
-        for old in [k for k, v in _plane_tables.items() if not v[1]][: max(0, len(_plane_tables) - _PLANE_TABLES_MAX)]:
-            del _plane_tables[old]
+        tables[key] = [table, False]
+        for old in [k for k, v in tables.items() if not v[1]][: max(0, len(tables) - limit)]:
+            del tables[old]
     return table
+
+
+def _plane_table(fn: str, addresses: tuple, device: torch.device) -> torch.Tensor:
+    """Device copy of the plane-pointer arrays of a call, cached by the addresses."""
+    return _cached_table(_plane_tables, _PLANE_TABLES_MAX, (device.index, addresses),
+                         lambda: torch.tensor(addresses, dtype=torch.int64), device,
+                         f"{fn}: call once on these tensors before capturing a graph (the plane-pointer table "
+                         "is uploaded on the first call, which a captured graph cannot replay)")
+
+
+def _plane_lists(fn: str, lists, dev: torch.device, anchor: str, n_lat: int, n_lon: int, like: int = 0) -> tuple[int, list[int]]:
+    """What every plane binding checks of its labelled lists [(what, fields)] -- the same length, every field on `dev` (the
+    device of the argument `anchor`) and shaped like its counterpart in list `like` -- and the plane addresses of list 0, 1, ...
+    one after the other: (planes per list, addresses)."""
+    first = lists[like][1]
+    assert all(len(fs) == len(first) for _, fs in lists), f"{fn}: the lists differ in length"
+    for _, fs in lists:
+        for v, p in zip(fs, first):
+            assert v.device == dev, f"{fn}: every tensor must be on the device of {anchor}"
+            assert v.shape == p.shape, f"{fn}: shapes differ ({tuple(v.shape)} against {tuple(p.shape)})"
+    addresses = [a for what, fs in lists for a in _plane_addresses(fn, fs, n_lat, n_lon, what)]
+    return len(addresses) // len(lists), addresses
 
 
 def scores_workspace_bytes(n_planes: int, n_lat: int, n_lon: int) -> int:
@@ -769,19 +790,13 @@ def scores_sums(pred: list[torch.Tensor], truth: list[torch.Tensor], clim: Optio
         "scores_sums: row_w must be a contiguous fp64 vector on the device"
     dev, n_lat = row_w.device, row_w.shape[0]
     lists = [("prediction", pred), ("truth", truth)] + ([("climatology", clim)] if clim is not None else [])
-    assert all(len(fs) == len(pred) for _, fs in lists), "scores_sums: the lists differ in length"
-    for _, fs in lists:
-        for v, p in zip(fs, pred):
-            assert v.device == dev, "scores_sums: every tensor must be on the device of row_w"
-            assert v.shape == p.shape, f"scores_sums: shapes differ ({tuple(v.shape)} against {tuple(p.shape)})"
     n_lon = pred[0].shape[-1] if pred else 1
-    addresses = [_plane_addresses(fs, n_lat, n_lon, what) for what, fs in lists]
-    n = len(addresses[0])
+    n, addresses = _plane_lists("scores_sums", lists, dev, "row_w", n_lat, n_lon)
     sums = torch.empty(n, 8, dtype=torch.float64, device=dev)
     if n == 0:
         return sums
     with torch.cuda.device(dev):
-        table = _plane_table(tuple(a for row in addresses for a in row), dev)
+        table = _plane_table("scores_sums", tuple(addresses), dev)
         workspace = torch.empty(scores_workspace_bytes(n, n_lat, n_lon), dtype=torch.uint8, device=dev)
         base = table.data_ptr()
         with _Timed("scores", 0.0):
@@ -813,21 +828,15 @@ def ensemble_scores_sums(members: list[list[torch.Tensor]], truth: list[torch.Te
     M = len(members)
     assert 2 <= M <= ENSEMBLE_MAX_MEMBERS, f"ensemble_scores_sums: members must hold 2..{ENSEMBLE_MAX_MEMBERS} lists, got {M}"
     dev, n_lat = row_w.device, row_w.shape[0]
-    assert all(len(fs) == len(truth) for fs in members), "ensemble_scores_sums: the lists differ in length"
-    for fs in (truth, *members):
-        for v, t in zip(fs, truth):
-            assert v.device == dev, "ensemble_scores_sums: every tensor must be on the device of row_w"
-            assert v.shape == t.shape, f"ensemble_scores_sums: shapes differ ({tuple(v.shape)} against {tuple(t.shape)})"
     n_lon = truth[0].shape[-1] if truth else 1
-    addresses = [_plane_addresses(fs, n_lat, n_lon, f"member {m}") for m, fs in enumerate(members)]
-    addresses.append(_plane_addresses(truth, n_lat, n_lon, "truth"))
-    n = len(addresses[-1])
+    lists = [(f"member {m}", fs) for m, fs in enumerate(members)] + [("truth", truth)]
+    n, addresses = _plane_lists("ensemble_scores_sums", lists, dev, "row_w", n_lat, n_lon, like=-1)
     sums = torch.empty(n, 8, dtype=torch.float64, device=dev)
     hist = torch.empty(n, M + 2, dtype=torch.int64, device=dev)
     if n == 0:
         return sums, hist
     with torch.cuda.device(dev):
-        table = _plane_table(tuple(a for row in addresses for a in row), dev)
+        table = _plane_table("ensemble_scores_sums", tuple(addresses), dev)
         workspace = torch.empty(ensemble_scores_workspace_bytes(M, n, n_lat, n_lon), dtype=torch.uint8, device=dev)
         base = table.data_ptr()
         with _Timed("ensemble_scores", 0.0):
@@ -838,27 +847,19 @@ def ensemble_scores_sums(members: list[list[torch.Tensor]], truth: list[torch.Te
 
 # ---- zonal power spectra (aurora_hip_spectra) -------------------------------------------------------------------------
 SPECTRA_MAX_BANDS, SPECTRA_MAX_LON = 8, 4096
-_twiddles: dict[tuple, torch.Tensor] = {}     # (n_lon, device) -> (n_lon, 2) fp64 device table
-_twiddles_lock = threading.Lock()
+_twiddles: "OrderedDict[tuple, list]" = OrderedDict()   # (n_lon, device) -> [(n_lon, 2) fp64 device table, used in a captured graph]
 
 
 def spectra_twiddle(n_lon: int, device: torch.device) -> torch.Tensor:
     """(n_lon, 2) fp64 on `device`: cos(2 pi m / n_lon), sin(2 pi m / n_lon), computed on the host in fp64 and kept per
     (n_lon, device)."""
-    key = (int(n_lon), str(device))
-    with _twiddles_lock:
-        hit = _twiddles.get(key)
-    if hit is None:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("spectra_power: call once for this n_lon before capturing a graph (the twiddle table is "
-                               "uploaded on the first call, which a captured graph cannot replay)")
+    def make():
         a = 2.0 * np.pi * np.arange(n_lon, dtype=np.float64) / n_lon
-        hit = torch.from_numpy(np.stack([np.cos(a), np.sin(a)], axis=1)).pin_memory().to(device, non_blocking=True)
-        with _twiddles_lock:
-            if len(_twiddles) >= 64:
-                _twiddles.clear()
-            _twiddles[key] = hit
-    return hit
+        return torch.from_numpy(np.stack([np.cos(a), np.sin(a)], axis=1))
+
+    return _cached_table(_twiddles, 64, (int(n_lon), str(device)), make, device,
+                         "spectra_power: call once for this n_lon before capturing a graph (the twiddle table is "
+                         "uploaded on the first call, which a captured graph cannot replay)")
 
 
 def spectra_workspace_bytes(n_planes: int, n_lat: int, n_lon: int, n_bands: int, has_truth: bool) -> int:
@@ -880,21 +881,16 @@ def spectra_power(pred: list[torch.Tensor], truth: Optional[list[torch.Tensor]],
     dev, (n_bands, n_lat) = band_w.device, band_w.shape
     assert 1 <= n_bands <= SPECTRA_MAX_BANDS, f"spectra_power: 1..{SPECTRA_MAX_BANDS} bands, got {n_bands}"
     lists = [("prediction", pred)] + ([("truth", truth)] if truth is not None else [])
-    assert all(len(fs) == len(pred) for _, fs in lists), "spectra_power: the lists differ in length"
-    for _, fs in lists:
-        for v, p in zip(fs, pred):
-            assert v.device == dev, "spectra_power: every tensor must be on the device of band_w"
-            assert v.shape == p.shape, f"spectra_power: shapes differ ({tuple(v.shape)} against {tuple(p.shape)})"
     n_lon = pred[0].shape[-1] if pred else 2
     assert 2 <= n_lon <= SPECTRA_MAX_LON, f"spectra_power: n_lon must be in 2..{SPECTRA_MAX_LON}, got {n_lon}"
-    addresses = [_plane_addresses(fs, n_lat, n_lon, what) for what, fs in lists]
-    n, F, K = len(addresses[0]), len(lists) * 2 - 1, n_lon // 2 + 1
+    n, addresses = _plane_lists("spectra_power", lists, dev, "band_w", n_lat, n_lon)
+    F, K = len(lists) * 2 - 1, n_lon // 2 + 1
     power = torch.empty(n, F, n_bands, K, dtype=torch.float64, device=dev)
     rows = torch.empty(n, n_bands, dtype=torch.int64, device=dev)
     if n == 0:
         return power, rows
     with torch.cuda.device(dev):
-        table = _plane_table(tuple(a for row in addresses for a in row), dev)
+        table = _plane_table("spectra_power", tuple(addresses), dev)
         twiddle = spectra_twiddle(n_lon, dev)
         nbytes = spectra_workspace_bytes(n, n_lat, n_lon, n_bands, truth is not None)
         workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)   # (from torch's caching allocator: no hipMalloc warm)
@@ -934,12 +930,8 @@ def event_rowsums(pred: list[torch.Tensor], truth: list[torch.Tensor], threshold
     assert 1 <= T <= EVENT_MAX_THRESHOLDS, f"event_rowsums: 1..{EVENT_MAX_THRESHOLDS} thresholds, got {T}"
     assert 1 <= S <= EVENT_MAX_SCALES, f"event_rowsums: 1..{EVENT_MAX_SCALES} scales, got {S}"
     assert len(truth) == len(pred) and pred, "event_rowsums: the lists differ in length or are empty"
-    for v, p in zip(truth, pred):
-        assert v.device == dev and p.device == dev, "event_rowsums: every tensor must be on the device of thresholds"
-        assert v.shape == p.shape, f"event_rowsums: shapes differ ({tuple(v.shape)} against {tuple(p.shape)})"
     n_lat, n_lon = pred[0].shape[-2:]
-    addresses = [_plane_addresses(fs, n_lat, n_lon, what) for what, fs in (("prediction", pred), ("truth", truth))]
-    n = len(addresses[0])
+    n, addresses = _plane_lists("event_rowsums", [("prediction", pred), ("truth", truth)], dev, "thresholds", n_lat, n_lon)
     assert n == n_thr_planes, f"event_rowsums: {n} planes but thresholds for {n_thr_planes}"
     rowsums = torch.empty(n, T, S, n_lat, 3, dtype=torch.int64, device=dev)
     valid = torch.empty(n, n_lat, dtype=torch.int64, device=dev)
@@ -947,7 +939,7 @@ def event_rowsums(pred: list[torch.Tensor], truth: list[torch.Tensor], threshold
         return rowsums, valid
     host_scales = (c_int32 * S)(*scales)
     with torch.cuda.device(dev):
-        table = _plane_table(tuple(a for row in addresses for a in row), dev)
+        table = _plane_table("event_rowsums", tuple(addresses), dev)
         base = table.data_ptr()
         with _Timed("event_scores", 0.0):
             _check(load().aurora_hip_event_scores(base, base + 8 * n, n, n_lat, n_lon, _ptr(thresholds), T, host_scales, S,
@@ -973,20 +965,15 @@ def probability_rows(members: list[list[torch.Tensor]], truth: list[torch.Tensor
     assert 2 <= M <= ENSEMBLE_MAX_MEMBERS, f"probability_rows: members must hold 2..{ENSEMBLE_MAX_MEMBERS} lists, got {M}"
     assert 1 <= T <= EVENT_MAX_THRESHOLDS, f"probability_rows: 1..{EVENT_MAX_THRESHOLDS} thresholds, got {T}"
     assert truth and all(len(fs) == len(truth) for fs in members), "probability_rows: the lists differ in length or are empty"
-    for fs in (truth, *members):
-        for v, t in zip(fs, truth):
-            assert v.device == dev, "probability_rows: every tensor must be on the device of thresholds"
-            assert v.shape == t.shape, f"probability_rows: shapes differ ({tuple(v.shape)} against {tuple(t.shape)})"
     n_lat, n_lon = truth[0].shape[-2:]
-    addresses = [_plane_addresses(fs, n_lat, n_lon, f"member {m}") for m, fs in enumerate(members)]
-    addresses.append(_plane_addresses(truth, n_lat, n_lon, "truth"))
-    n = len(addresses[-1])
+    lists = [(f"member {m}", fs) for m, fs in enumerate(members)] + [("truth", truth)]
+    n, addresses = _plane_lists("probability_rows", lists, dev, "thresholds", n_lat, n_lon, like=-1)
     assert n == n_thr_planes, f"probability_rows: {n} planes but thresholds for {n_thr_planes}"
     rows = torch.empty(n, n_lat, T, 2, M + 1, dtype=torch.int32, device=dev)
     if n == 0:
         return rows
     with torch.cuda.device(dev):
-        table = _plane_table(tuple(a for row in addresses for a in row), dev)
+        table = _plane_table("probability_rows", tuple(addresses), dev)
         base = table.data_ptr()
         with _Timed("probability_scores", 0.0):
             _check(load().aurora_hip_probability_scores(base, base + 8 * M * n, M, n, n_lat, n_lon, _ptr(thresholds), T,
@@ -1025,13 +1012,7 @@ def field_stats_update(samples: list[list[torch.Tensor]], ref: Optional[list[tor
         "field_stats_update: sample_index must be one int64 on the device"
     n_lat, n_lon = samples[0][0].shape[-2:]
     lists = [(f"sample {s}", fs) for s, fs in enumerate(samples)] + ([("reference", ref)] if ref is not None else [])
-    for _, fs in lists:
-        assert len(fs) == len(samples[0]), "field_stats_update: the lists differ in length"
-        for v, p in zip(fs, samples[0]):
-            assert v.device == dev, "field_stats_update: every tensor must be on the device of sample_index"
-            assert v.shape == p.shape, f"field_stats_update: shapes differ ({tuple(v.shape)} against {tuple(p.shape)})"
-    addresses = [a for what, fs in lists for a in _plane_addresses(fs, n_lat, n_lon, what)]
-    n = len(addresses) // len(lists)
+    n, addresses = _plane_lists("field_stats_update", lists, dev, "sample_index", n_lat, n_lon)
     if second is not None:
         assert len(second) == S and all(len(fs) == len(samples[0]) for fs in second), \
             "field_stats_update: the second operands differ from the samples in number"
@@ -1041,7 +1022,7 @@ def field_stats_update(samples: list[list[torch.Tensor]], ref: Optional[list[tor
                     addresses += [0] * (p.numel() // (n_lat * n_lon))
                     continue
                 assert v.device == dev and v.shape == p.shape, "field_stats_update: a second operand differs from its sample"
-                addresses += _plane_addresses([v], n_lat, n_lon, "second operand")
+                addresses += _plane_addresses("field_stats_update", [v], n_lat, n_lon, "second operand")
     T = 0
     if thresholds is not None:
         assert thresholds.device == dev and thresholds.dtype == torch.float32 and thresholds.dim() == 2 and \
@@ -1059,7 +1040,7 @@ def field_stats_update(samples: list[list[torch.Tensor]], ref: Optional[list[tor
     if n == 0:
         return
     with torch.cuda.device(dev):
-        table = _plane_table(tuple(addresses), dev)
+        table = _plane_table("field_stats_update", tuple(addresses), dev)
         base = table.data_ptr()
         ref_at = base + 8 * S * n if ref is not None else None
         second_at = base + 8 * (S + (ref is not None)) * n if second is not None else None
@@ -1111,9 +1092,9 @@ def diagnostics(n_lat: int, n_lon: int, *, u: Optional[list[torch.Tensor]] = Non
         if what in ("vo", "div", "ws") and any(t is None for t in fs):   # an entry None: NULL for the planes of that u entry
             assert u is not None and len(fs) == len(u), f"diagnostics: {what} with None entries must have an entry per u entry"
             addr[what] = [a for t, like in zip(fs, u) for a in
-                          ([0] * (like.numel() // (n_lat * n_lon)) if t is None else _plane_addresses([t], n_lat, n_lon, what))]
+                          ([0] * (like.numel() // (n_lat * n_lon)) if t is None else _plane_addresses("diagnostics", [t], n_lat, n_lon, what))]
         else:
-            addr[what] = _plane_addresses(fs, n_lat, n_lon, what)
+            addr[what] = _plane_addresses("diagnostics", fs, n_lat, n_lon, what)
     n_wind, n_cols = len(addr.get("u", ())), 0
     C = 0 if level_w is None else level_w.shape[0]
     for what in ("v", "vo", "div", "ws"):
@@ -1129,7 +1110,7 @@ def diagnostics(n_lat: int, n_lon: int, *, u: Optional[list[torch.Tensor]] = Non
         return
     with torch.cuda.device(dev):
         order = [what for what, _ in groups if what in addr]
-        table = _plane_table(tuple(a for what in order for a in addr[what]), dev)
+        table = _plane_table("diagnostics", tuple(a for what in order for a in addr[what]), dev)
         at, first = {}, table.data_ptr()
         for what in order:
             at[what], first = first, first + 8 * len(addr[what])

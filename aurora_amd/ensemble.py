@@ -45,12 +45,12 @@ from typing import Sequence, Union
 import numpy as np
 import torch
 
-from aurora_amd.batch import BandBatch, Batch
-from aurora_amd.scores import _check_same_grid, _device_weights, _host, latitude_weights
+from aurora_amd import _fields
+from aurora_amd._fields import MAX_MEMBERS, latitude_weights
+from aurora_amd.batch import Batch
 
 __all__ = ["ensemble_scores", "EnsembleScores", "MAX_MEMBERS"]
 
-MAX_MEMBERS = 64
 _SUMS, _RMSE, _BIAS, _MAE, _CRPS, _FAIR, _SPREAD, _RATIO = slice(0, 8), 8, 9, 10, 11, 12, 13, 14
 
 
@@ -66,13 +66,7 @@ class EnsembleScores:
     members: int
 
     def _column(self, col, of=None) -> dict[str, torch.Tensor]:
-        of = self.table if of is None else of
-        out = {}
-        for name, first, shape in self.layout:
-            n = int(np.prod(shape))
-            v = of[first:first + n, col]
-            out[name] = v.reshape(*shape, *v.shape[1:])
-        return out
+        return _fields.by_variable(self.layout, (self.table if of is None else of)[:, col])
 
     crps = property(lambda self: self._column(_CRPS))
     fair_crps = property(lambda self: self._column(_FAIR))
@@ -126,107 +120,27 @@ def _ensemble_sums_host(members: np.ndarray, truth: np.ndarray, w: np.ndarray) -
 
 
 # ---- public function -----------------------------------------------------------------------------------------
-def _same_grid(member: Batch, truth: Batch, who: str) -> None:
-    """`_check_same_grid` of `scores` with the member in the prediction's place, its messages naming the member."""
-    try:
-        _check_same_grid(member, truth, "truth")
-    except ValueError as err:
-        text = str(err).replace("scores: pred", f"ensemble_scores: {who}").replace("scores: ", "ensemble_scores: ")
-        raise ValueError(text.replace("the prediction was", f"{who} was")) from None
-
-
 def ensemble_scores(members: Union[Batch, Sequence[Batch]], truth: Batch) -> EnsembleScores:
     """CRPS, fair CRPS, the ensemble mean's RMSE / bias / MAE, spread, spread / skill and the rank histogram of M members
     against `truth`; see the module's text."""
-    if isinstance(truth, BandBatch):
-        raise ValueError("ensemble_scores: truth is a latitude band (BandBatch); gather the forecast first, band scores are "
-                         "not supported")
-    if not isinstance(truth, Batch):
-        raise TypeError(f"ensemble_scores: truth must be a Batch, got {type(truth).__name__}")
-    one_batch = isinstance(members, Batch)
-    batches = [members] if one_batch else list(members)
-    for m, b in enumerate(batches):
-        if not isinstance(b, Batch):
-            raise TypeError(f"ensemble_scores: members[{m}] must be a Batch, got {type(b).__name__}")
-    who = (lambda m: "members") if one_batch else (lambda m: f"members[{m}]")
-    if not one_batch and not 2 <= len(batches) <= MAX_MEMBERS:
-        raise ValueError(f"ensemble_scores: members must hold 2 to {MAX_MEMBERS} batches, got {len(batches)}")
-    for m, b in enumerate(batches):
-        _same_grid(b, truth, who(m))
-    n_lat, n_lon = truth.metadata.lat.shape[0], truth.metadata.lon.shape[0]
-
-    names, truth_fields, member_fields = [], [], [[] for _ in batches]
-    for group in ("surf_vars", "atmos_vars"):
-        for k, t in getattr(truth, group).items():
-            if not all(k in getattr(b, group) for b in batches):
-                continue
-            if k in names:
-                raise ValueError(f"ensemble_scores: {k!r} is both a surface and an atmospheric variable")
-            names.append(k)
-            want = 4 if group == "surf_vars" else 5
-            for what, f in [("truth", t)] + [(who(m), getattr(b, group)[k]) for m, b in enumerate(batches)]:
-                if f.dim() != want or tuple(f.shape[-2:]) != (n_lat, n_lon):
-                    raise ValueError(f"ensemble_scores: {what}.{group}[{k!r}] has shape {tuple(f.shape)}, which does not "
-                                     f"fit a {n_lat} x {n_lon} grid")
-            t = t[:, -1]
-            truth_fields.append(t)
-            for m, b in enumerate(batches):
-                f = getattr(b, group)[k][:, -1]
-                if one_batch:
-                    if t.shape[0] != 1:
-                        raise ValueError(f"ensemble_scores: members is ONE Batch (its batch elements are the members), so "
-                                         f"truth must have batch size 1, got {t.shape[0]} for {k!r}; pass a sequence of "
-                                         "Batches to score a batch of ensembles")
-                    if f.shape[1:] != t.shape[1:]:
-                        raise ValueError(f"ensemble_scores: members and truth differ in shape for {k!r}: {tuple(f.shape)} "
-                                         f"against {tuple(t.shape)}")
-                elif f.shape != t.shape:
-                    what_differs = "batch size" if f.shape[0] != t.shape[0] else "shape"
-                    raise ValueError(f"ensemble_scores: {who(m)} and truth differ in {what_differs} for {k!r}: "
-                                     f"{tuple(f.shape)} against {tuple(t.shape)}")
-                member_fields[m].append(f)
+    names, truth_fields, member_fields, layout = _fields.select_members("ensemble_scores", members, truth)
     if not names:
         raise ValueError("ensemble_scores: members and truth have no surface or atmospheric variable in common")
-    if one_batch:                                          # the batch elements of the one Batch are the members
-        sizes = {f.shape[0] for f in member_fields[0]}
-        M = sizes.pop()
-        if sizes or not 2 <= M <= MAX_MEMBERS:
-            raise ValueError(f"ensemble_scores: members is ONE Batch, whose batch size is the number of members: it must be "
-                             f"2 to {MAX_MEMBERS}, got {sorted(sizes | {M})}")
-        member_fields = [[f[m:m + 1] for f in member_fields[0]] for m in range(M)]
     M = len(member_fields)
+    n_lat, n_lon = truth.metadata.lat.shape[0], truth.metadata.lon.shape[0]
 
-    layout, first = [], 0
-    for name, f in zip(names, truth_fields):
-        shape = tuple(f.shape[:-2])
-        layout.append((name, first, shape))
-        first += int(np.prod(shape))
-
-    everything = [("truth", truth_fields)] + [(f"members[{m}]", fs) for m, fs in enumerate(member_fields)]
-    devices = {f.device for _, fs in everything for f in fs}
-    lat = _host(truth.metadata.lat)
-    if all(d.type == "cpu" for d in devices):
-        stack = lambda fs: np.concatenate([f.detach().reshape(-1, n_lat, n_lon).numpy() for f in fs])  # noqa: E731
-        sums, hist = _ensemble_sums_host(np.stack([stack(fs) for fs in member_fields]), stack(truth_fields),
-                                         latitude_weights(lat))
+    everything = [("truth", names, truth_fields)] + [(f"members[{m}]", names, fs) for m, fs in enumerate(member_fields)]
+    device = _fields.place("ensemble_scores", everything, n_lat, n_lon, fields="the fields of members and truth")
+    lat = _fields._host(truth.metadata.lat)
+    if device == "cpu":
+        sums, hist = _ensemble_sums_host(np.stack([_fields.stack(fs, n_lat, n_lon) for fs in member_fields]),
+                                         _fields.stack(truth_fields, n_lat, n_lon), latitude_weights(lat))
         sums, hist = torch.from_numpy(sums), torch.from_numpy(hist)
-    elif len(devices) == 1 and next(iter(devices)).type == "cuda":
+    else:
         from aurora_amd.engine import lib
 
-        dev = next(iter(devices))
-        for what, fs in everything:
-            for name, f in zip(names, fs):
-                if f.dtype != torch.float32:
-                    raise TypeError(f"ensemble_scores: {what} variable {name!r} is {f.dtype}; the device path scores float32 "
-                                    "fields (move the batches to the CPU to score other precisions)")
-                if (n_lon > 1 and f.stride(-1) != 1) or (n_lat > 1 and f.stride(-2) != n_lon):
-                    raise ValueError(f"ensemble_scores: the planes of {what} variable {name!r} are not row-major "
-                                     "contiguous; call .contiguous() on it first")
-        sums, hist = lib.ensemble_scores_sums(member_fields, truth_fields, _device_weights(lat, dev))
-    else:
-        raise ValueError(f"ensemble_scores: the fields of members and truth are on {sorted(map(str, devices))}; move the "
-                         "batches to the CPU or to one GPU first")
-    return EnsembleScores(_finalise(sums, M), hist, tuple(layout), M)
+        sums, hist = lib.ensemble_scores_sums(member_fields, truth_fields, _fields.device_weights("ensemble_scores", lat, device))
+    return EnsembleScores(_finalise(sums, M), hist, layout, M)
 
 
 def _finalise(sums: torch.Tensor, M: int) -> torch.Tensor:

@@ -50,12 +50,13 @@ from typing import Mapping, Optional, Sequence
 import numpy as np
 import torch
 
-from aurora_amd.batch import BandBatch, Batch, derive_metadata
-from aurora_amd.scores import _check_same_grid, _host
+from aurora_amd import _fields
+from aurora_amd._fields import MAX_THRESHOLDS, _host
+from aurora_amd.batch import Batch, derive_metadata
 
 __all__ = ["FieldStats", "MAX_SAMPLES", "MAX_THRESHOLDS"]
 
-MAX_SAMPLES, MAX_THRESHOLDS = 64, 8
+MAX_SAMPLES = 64
 DERIVED = {"10ws": ("surf_vars", "10u", "10v"), "ws": ("atmos_vars", "u", "v")}
 # state array -> (dtype, per threshold); include/aurora_hip.h has the meanings
 _STATE = {"n": (torch.int32, False), "origin": (torch.float32, False), "s1": (torch.float64, False),
@@ -63,26 +64,6 @@ _STATE = {"n": (torch.int32, False), "origin": (torch.float32, False), "s1": (to
           "argmin": (torch.int32, False), "argmax": (torch.int32, False), "exceed": (torch.int32, True),
           "run": (torch.int32, True), "longest": (torch.int32, True)}
 _MAPS = ("mean", "std", "var", "rms", "min", "max")
-
-
-def _threshold_rows(name: str, value, levels: Optional[int]) -> np.ndarray:
-    """(1 or C, T_v) float32 thresholds of one variable."""
-    try:
-        a = np.asarray(value, dtype=np.float64)
-    except (TypeError, ValueError):
-        raise ValueError(f"FieldStats: the thresholds of {name!r} must be numbers") from None
-    if a.ndim == 1:
-        a = a[None]
-    elif a.ndim == 2 and levels is not None:
-        if a.shape[0] != levels:
-            raise ValueError(f"FieldStats: the thresholds of {name!r} have shape {a.shape}; a (C, T) array needs C = {levels} "
-                             "levels")
-    else:
-        want = "a sequence" if levels is None else f"a sequence or a ({levels}, T) array"
-        raise ValueError(f"FieldStats: the thresholds of {name!r} have shape {a.shape}; {want} is needed")
-    if not 1 <= a.shape[1] <= MAX_THRESHOLDS:
-        raise ValueError(f"FieldStats: 1 to {MAX_THRESHOLDS} thresholds per variable, {name!r} has {a.shape[1]}")
-    return a.astype(np.float32)
 
 
 def _update_host(state: dict, x: np.ndarray, b: Optional[np.ndarray], has_b: np.ndarray, r: Optional[np.ndarray],
@@ -140,11 +121,8 @@ class FieldStats:
         out = []
         for group in ("surf_vars", "atmos_vars"):
             vars_ = getattr(batch, group)
-            want = 4 if group == "surf_vars" else 5
             for k, f in vars_.items():
-                if f.dim() != want or tuple(f.shape[-2:]) != (n_lat, n_lon):
-                    raise ValueError(f"FieldStats: {what}.{group}[{k!r}] has shape {tuple(f.shape)}, which does not fit a "
-                                     f"{n_lat} x {n_lon} grid")
+                _fields.check_field("FieldStats", f, what, group, k, n_lat, n_lon)
                 if k in DERIVED and k in self._derived and not reference:
                     raise ValueError(f"FieldStats: {what} holds {k!r}, which is also a derived variable")
                 if not (reference and k in DERIVED and k not in self._derived):
@@ -179,7 +157,7 @@ class FieldStats:
             first += n
             rows = np.full((1, 1), np.nan, dtype=np.float32)
             if name in self._thresholds:
-                rows = _threshold_rows(name, self._thresholds[name], None if group == "surf_vars" else shape[1])
+                rows = _fields.threshold_rows("FieldStats", name, self._thresholds[name], None if group == "surf_vars" else shape[1])
             # (1 or C, T_v) -> one row per plane, planes in (B, [C]) order
             thr_rows.append(np.broadcast_to(rows, (B, n // B, rows.shape[1])).reshape(n, rows.shape[1]))
         known = {name for name, *_ in layout}
@@ -190,8 +168,7 @@ class FieldStats:
         T = max(r.shape[1] for r in thr_rows) if self._thresholds else 0
         thr = None
         if T:
-            thr = np.concatenate([np.pad(r, ((0, 0), (0, T - r.shape[1])), constant_values=np.nan) for r in thr_rows])
-            thr = torch.from_numpy(np.ascontiguousarray(thr, dtype=np.float32)).to(device)
+            thr = torch.from_numpy(_fields.pad_thresholds(thr_rows)).to(device)
         self._layout, self._n_planes, self._T, self._thr = tuple(layout), first, T, thr
         self._grid = (n_lat, n_lon)
         self._lat, self._lon = _host(batch.metadata.lat), _host(batch.metadata.lon)
@@ -203,7 +180,7 @@ class FieldStats:
         self._last = None
 
     def _check_grid(self, batch: Batch, what: str) -> None:
-        """The comparison and wording of `scores._check_same_grid`, against the grid of the first update."""
+        """The comparison and wording of `_fields.check_same_coordinates`, against the grid of the first update."""
         for c, mine in (("lat", self._lat), ("lon", self._lon)):
             o = getattr(batch.metadata, c)
             if o.shape[0] != mine.shape[0]:
@@ -223,19 +200,11 @@ class FieldStats:
         for what, b in (("batch", batch), ("minus", minus)):
             if b is None:
                 continue
-            if isinstance(b, BandBatch):
-                raise ValueError(f"FieldStats: {what} is a latitude band (BandBatch); gather the forecast first, band "
-                                 "statistics are not supported")
             if not isinstance(b, Batch):
                 raise TypeError(f"FieldStats: {what} must be a Batch, got {type(b).__name__}")
-            if b.metadata.lat.dim() != 1 or b.metadata.lon.dim() != 1:
-                raise ValueError(f"FieldStats: {what} has matrices for latitudes / longitudes; vector coordinates are needed")
+            _fields.check_vector_grid("FieldStats", b, what, band="statistics")
         if minus is not None:
-            try:
-                _check_same_grid(batch, minus, "minus")
-            except ValueError as err:
-                raise ValueError(str(err).replace("scores: pred", "FieldStats: batch").replace("scores: ", "FieldStats: ")
-                                 .replace("the prediction was", "batch was")) from None
+            _fields.check_same_coordinates("FieldStats", batch, minus, "batch", "minus", "batch")
         fields = self._fields(batch, "batch")
         sizes = {f.shape[0] for _, _, f, _ in fields}
         if len(sizes) != 1:
@@ -262,14 +231,7 @@ class FieldStats:
                 refs.append(r)
 
         everything = [f for _, _, f, b in fields for f in ((f,) if b is None else (f, b))] + (refs or [])
-        devices = {f.device for f in everything}
-        if all(d.type == "cpu" for d in devices):
-            device = torch.device("cpu")
-        elif len(devices) == 1 and next(iter(devices)).type == "cuda":
-            device = next(iter(devices))
-        else:
-            raise ValueError(f"FieldStats: the fields are on {sorted(map(str, devices))}; move the batches to the CPU or to one "
-                             "GPU first")
+        device = torch.device(_fields.device_of("FieldStats", everything))
         if self._state is None:
             self._start(batch, fields, B, device)
         else:
@@ -297,15 +259,9 @@ class FieldStats:
             from aurora_amd.engine import lib
 
             n_lat, n_lon = self._grid
-            for what, fs in (("batch", [f for fs in samples for f in fs] + [b for bs in (second or []) for b in bs if b is not None]),
-                             ("minus", refs or [])):
-                for f in fs:
-                    if f.dtype != torch.float32:
-                        raise TypeError(f"FieldStats: a variable of {what} is {f.dtype}; the device path takes float32 fields "
-                                        "(move the batches to the CPU for other precisions)")
-                    if (n_lon > 1 and f.stride(-1) != 1) or (n_lat > 1 and f.stride(-2) != n_lon):
-                        raise ValueError(f"FieldStats: the planes of a variable of {what} are not row-major contiguous; call "
-                                         ".contiguous() on it first")
+            of_batch = [f for fs in samples for f in fs] + [b for bs in (second or []) for b in bs if b is not None]
+            _fields.check_planes("FieldStats", [("batch", of_batch, of_batch), ("minus", refs or [], refs or [])], n_lat, n_lon,
+                                 _fields.TAKES_TASK, noun=lambda what, _: f"a variable of {what}")
             lib.field_stats_update(samples, refs, second, self._thr, self._below, self._index, self._state)
         else:
             self._update_host(samples, refs, second)

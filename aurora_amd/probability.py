@@ -59,10 +59,9 @@ from typing import Mapping, Sequence, Union
 import numpy as np
 import torch
 
-from aurora_amd.batch import BandBatch, Batch
-from aurora_amd.ensemble import MAX_MEMBERS, _same_grid
-from aurora_amd.events import _device_thresholds, _ratio, _threshold_rows, _tree_sum
-from aurora_amd.scores import _device_weights, _host, latitude_weights
+from aurora_amd import _fields
+from aurora_amd._fields import latitude_weights, ratio as _ratio, tree_sum as _tree_sum, tree_sum_rows as _tree_sum_rows
+from aurora_amd.batch import Batch
 
 __all__ = ["probability_scores", "ProbabilityScores"]
 
@@ -85,12 +84,7 @@ class ProbabilityScores:
     below: bool
 
     def _field(self, t: torch.Tensor) -> dict[str, torch.Tensor]:
-        out = {}
-        for name, first, shape in self.layout:
-            n = int(np.prod(shape))
-            v = t[first:first + n]
-            out[name] = v.reshape(*shape, *v.shape[1:])
-        return out
+        return _fields.by_variable(self.layout, t)
 
     brier = property(lambda self: self._field(self.scores_table[..., _BRIER]))
     fair_brier = property(lambda self: self._field(self.scores_table[..., _FAIR]))
@@ -141,21 +135,6 @@ def _rows_host(members: np.ndarray, truth: np.ndarray, thr: np.ndarray, below: b
 
 
 # ---- finalisation: the same torch code on either device ----------------------------------------------------------------
-def _tree_sum_rows(x: torch.Tensor) -> torch.Tensor:
-    """`_tree_sum` of events.py over dimension 1, the rows, with the same pairs in the same order (so a sum taken here and one
-    taken there over the same numbers have the same bits), on slices that stay contiguous in the bins."""
-    n = x.shape[1]
-    size = 1
-    while size < n:
-        size *= 2
-    if size != n:
-        x = torch.cat([x, x.new_zeros(x.shape[0], size - n, *x.shape[2:])], dim=1)
-    while size > 1:
-        size //= 2
-        x = x[:, :size] + x[:, size:]
-    return x[:, 0]
-
-
 def _finalise(rows: torch.Tensor, w: torch.Tensor, thr: torch.Tensor, M: int):
     """(counts (P, T, 2, M + 1) int64, scores (P, T, 8), bins (P, T, 2, M + 1), roc (P, T, 2, M + 2) fp64, p (M + 1,) fp64)
     from the integer table; elementwise operations and fixed trees on the device of `rows`, no read-back."""
@@ -200,118 +179,33 @@ def _finalise(rows: torch.Tensor, w: torch.Tensor, thr: torch.Tensor, M: int):
 
 
 # ---- public function -----------------------------------------------------------------------------------------------------
-def _renamed(fn, *args):
-    """A neighbour's helper with its messages worded for this module."""
-    try:
-        return fn(*args)
-    except (ValueError, RuntimeError) as err:
-        text = str(err).replace("ensemble_scores: ", "probability_scores: ").replace("event_scores: ", "probability_scores: ")
-        raise type(err)(text) from None
-
-
 def probability_scores(members: Union[Batch, Sequence[Batch]], truth: Batch, thresholds: Mapping[str, object],
                        below: bool = False) -> ProbabilityScores:
     """Brier score, its decomposition and skill, reliability diagram and ROC of the fraction of M members over each threshold,
     of the last history entry of the variables named in `thresholds`; see the module's text."""
-    if isinstance(truth, BandBatch):
-        raise ValueError("probability_scores: truth is a latitude band (BandBatch); gather the forecast first, band scores are "
-                         "not supported")
-    if not isinstance(truth, Batch):
-        raise TypeError(f"probability_scores: truth must be a Batch, got {type(truth).__name__}")
-    one_batch = isinstance(members, Batch)
-    batches = [members] if one_batch else list(members)
-    for m, b in enumerate(batches):
-        if not isinstance(b, Batch):
-            raise TypeError(f"probability_scores: members[{m}] must be a Batch, got {type(b).__name__}")
-    who = (lambda m: "members") if one_batch else (lambda m: f"members[{m}]")
-    if not one_batch and not 2 <= len(batches) <= MAX_MEMBERS:
-        raise ValueError(f"probability_scores: members must hold 2 to {MAX_MEMBERS} batches, got {len(batches)}")
-    for m, b in enumerate(batches):
-        _renamed(_same_grid, b, truth, who(m))
-    n_lat, n_lon = truth.metadata.lat.shape[0], truth.metadata.lon.shape[0]
     if not isinstance(thresholds, Mapping) or not thresholds:
         raise ValueError("probability_scores: thresholds must be a non-empty mapping from variable name to values")
-
-    names, truth_fields, member_fields, thr_rows = [], [], [[] for _ in batches], []
-    for group in ("surf_vars", "atmos_vars"):
-        for k, t in getattr(truth, group).items():
-            if k not in thresholds or not all(k in getattr(b, group) for b in batches):
-                continue
-            if k in names:
-                raise ValueError(f"probability_scores: {k!r} is both a surface and an atmospheric variable")
-            names.append(k)
-            want = 4 if group == "surf_vars" else 5
-            for what, f in [("truth", t)] + [(who(m), getattr(b, group)[k]) for m, b in enumerate(batches)]:
-                if f.dim() != want or tuple(f.shape[-2:]) != (n_lat, n_lon):
-                    raise ValueError(f"probability_scores: {what}.{group}[{k!r}] has shape {tuple(f.shape)}, which does not "
-                                     f"fit a {n_lat} x {n_lon} grid")
-            t = t[:, -1]
-            truth_fields.append(t)
-            for m, b in enumerate(batches):
-                f = getattr(b, group)[k][:, -1]
-                if one_batch:
-                    if t.shape[0] != 1:
-                        raise ValueError(f"probability_scores: members is ONE Batch (its batch elements are the members), so "
-                                         f"truth must have batch size 1, got {t.shape[0]} for {k!r}; pass a sequence of "
-                                         "Batches to score a batch of ensembles")
-                    if f.shape[1:] != t.shape[1:]:
-                        raise ValueError(f"probability_scores: members and truth differ in shape for {k!r}: "
-                                         f"{tuple(f.shape)} against {tuple(t.shape)}")
-                elif f.shape != t.shape:
-                    what_differs = "batch size" if f.shape[0] != t.shape[0] else "shape"
-                    raise ValueError(f"probability_scores: {who(m)} and truth differ in {what_differs} for {k!r}: "
-                                     f"{tuple(f.shape)} against {tuple(t.shape)}")
-                member_fields[m].append(f)
-            lead = t.shape[:-2]
-            rows = _renamed(_threshold_rows, k, thresholds[k], None if group == "surf_vars" else lead[1])
-            if group == "atmos_vars":
-                rows = np.broadcast_to(rows, (lead[1], rows.shape[1]))
-            thr_rows.append(np.broadcast_to(rows, (lead[0], *rows.shape)).reshape(-1, rows.shape[1]))
+    names, truth_fields, member_fields, layout = _fields.select_members("probability_scores", members, truth, only=thresholds)
+    thr = _fields.threshold_table("probability_scores", thresholds, layout) if names else None
     for k in thresholds:
         if k not in names:
             raise ValueError(f"probability_scores: thresholds name the variable {k!r}, which members and truth do not all hold "
                              "as a surface or atmospheric variable")
-    if one_batch:                                          # the batch elements of the one Batch are the members
-        sizes = {f.shape[0] for f in member_fields[0]}
-        M = sizes.pop()
-        if sizes or not 2 <= M <= MAX_MEMBERS:
-            raise ValueError(f"probability_scores: members is ONE Batch, whose batch size is the number of members: it must "
-                             f"be 2 to {MAX_MEMBERS}, got {sorted(sizes | {M})}")
-        member_fields = [[f[m:m + 1] for f in member_fields[0]] for m in range(M)]
     M = len(member_fields)
-    T = max(r.shape[1] for r in thr_rows)
-    thr = np.concatenate([np.pad(r, ((0, 0), (0, T - r.shape[1])), constant_values=np.nan) for r in thr_rows]).astype(np.float32)
+    n_lat, n_lon = truth.metadata.lat.shape[0], truth.metadata.lon.shape[0]
 
-    layout, first = [], 0
-    for name, f in zip(names, truth_fields):
-        shape = tuple(f.shape[:-2])
-        layout.append((name, first, shape))
-        first += int(np.prod(shape))
-
-    everything = [("truth", truth_fields)] + [(f"members[{m}]", fs) for m, fs in enumerate(member_fields)]
-    devices = {f.device for _, fs in everything for f in fs}
-    lat = _host(truth.metadata.lat)
-    if all(d.type == "cpu" for d in devices):
-        stack = lambda fs: np.concatenate([f.detach().reshape(-1, n_lat, n_lon).numpy() for f in fs])  # noqa: E731
-        rows = torch.from_numpy(_rows_host(np.stack([stack(fs) for fs in member_fields]), stack(truth_fields), thr, bool(below)))
+    everything = [("truth", names, truth_fields)] + [(f"members[{m}]", names, fs) for m, fs in enumerate(member_fields)]
+    device = _fields.place("probability_scores", everything, n_lat, n_lon, fields="the fields of members and truth")
+    lat = _fields._host(truth.metadata.lat)
+    if device == "cpu":
+        rows = torch.from_numpy(_rows_host(np.stack([_fields.stack(fs, n_lat, n_lon) for fs in member_fields]),
+                                           _fields.stack(truth_fields, n_lat, n_lon), thr, bool(below)))
         thr_t, w = torch.from_numpy(thr), torch.from_numpy(latitude_weights(lat))
-    elif len(devices) == 1 and next(iter(devices)).type == "cuda":
+    else:
         from aurora_amd.engine import lib
 
-        dev = next(iter(devices))
-        for what, fs in everything:
-            for name, f in zip(names, fs):
-                if f.dtype != torch.float32:
-                    raise TypeError(f"probability_scores: {what} variable {name!r} is {f.dtype}; the device path scores "
-                                    "float32 fields (move the batches to the CPU to score other precisions)")
-                if (n_lon > 1 and f.stride(-1) != 1) or (n_lat > 1 and f.stride(-2) != n_lon):
-                    raise ValueError(f"probability_scores: the planes of {what} variable {name!r} are not row-major "
-                                     "contiguous; call .contiguous() on it first")
-        thr_t = _renamed(_device_thresholds, thr, dev)
+        thr_t = _fields.device_thresholds("probability_scores", thr, device)
         rows = lib.probability_rows(member_fields, truth_fields, thr_t, bool(below))
-        w = _device_weights(lat, dev)
-    else:
-        raise ValueError(f"probability_scores: the fields of members and truth are on {sorted(map(str, devices))}; move the "
-                         "batches to the CPU or to one GPU first")
+        w = _fields.device_weights("probability_scores", lat, device)
     counts, scores, bins, roc, p = _finalise(rows, w, thr_t, M)
-    return ProbabilityScores(rows, counts, scores, bins, roc, p, tuple(layout), M, bool(below))
+    return ProbabilityScores(rows, counts, scores, bins, roc, p, layout, M, bool(below))

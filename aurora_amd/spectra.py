@@ -35,18 +35,18 @@ fp64 cast).
 from __future__ import annotations
 
 import dataclasses
-import threading
 from typing import Optional, Sequence
 
 import numpy as np
 import torch
 
+from aurora_amd import _fields
+from aurora_amd._fields import MAX_LON, latitude_weights  # noqa: F401  (MAX_LON: the limit lives with the longitude check)
 from aurora_amd.batch import Batch
-from aurora_amd.scores import _check_same_grid, _host, latitude_weights
 
 __all__ = ["spectra", "Spectra"]
 
-MAX_BANDS, MAX_LON = 8, 4096
+MAX_BANDS = 8
 
 
 @dataclasses.dataclass(frozen=True)
@@ -60,12 +60,7 @@ class Spectra:
     bands: tuple[tuple[float, float], ...]
 
     def _field(self, t: torch.Tensor) -> dict[str, torch.Tensor]:
-        out = {}
-        for name, first, shape in self.layout:
-            n = int(np.prod(shape))
-            v = t[first:first + n]
-            out[name] = v.reshape(*shape, *v.shape[1:])
-        return out
+        return _fields.by_variable(self.layout, t)
 
     @property
     def has_truth(self) -> bool:
@@ -101,10 +96,6 @@ class Spectra:
 
 
 # ---- bands -------------------------------------------------------------------------------------------------------
-_lock = threading.Lock()
-_band_tables: dict[tuple, torch.Tensor] = {}   # (latitude bytes, bands, device) -> (n_bands, n_lat) device weights
-
-
 def _check_bands(bands) -> tuple[tuple[float, float], ...]:
     if bands is None:
         return ((-90.0, 90.0),)
@@ -127,32 +118,6 @@ def band_weights(lat: np.ndarray, bands: Sequence[tuple[float, float]]) -> np.nd
     w = np.maximum(latitude_weights(lat), np.finfo(np.float64).tiny)
     lat = np.asarray(lat, dtype=np.float64)
     return np.stack([np.where((lat >= s) & (lat <= n), w, 0.0) for s, n in bands])
-
-
-def _device_band_weights(lat: np.ndarray, bands, device: torch.device) -> torch.Tensor:
-    key = (lat.tobytes(), bands, str(device))
-    with _lock:
-        hit = _band_tables.get(key)
-    if hit is None:
-        if torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("spectra: call once with these bands before capturing a graph (the band weights are uploaded "
-                               "on the first call, which a captured graph cannot replay)")
-        hit = torch.from_numpy(band_weights(lat, bands)).pin_memory().to(device, non_blocking=True)
-        with _lock:
-            if len(_band_tables) >= 64:
-                _band_tables.clear()
-            _band_tables[key] = hit
-    return hit
-
-
-def _check_longitudes(lon: np.ndarray) -> None:
-    n = lon.shape[0]
-    if not 2 <= n <= MAX_LON:
-        raise ValueError(f"spectra: the grid has {n} longitudes; 2 to {MAX_LON} are supported")
-    step = 360.0 / n
-    if not np.all(np.abs(lon - lon[0] - np.arange(n, dtype=np.float64) * step) <= 1e-6 * step):
-        raise ValueError("spectra: the longitudes must be equally spaced and cover the full circle (a zonal spectrum of a "
-                         "regional or irregular grid is not defined)")
 
 
 # ---- the spectra on the host ---------------------------------------------------------------------------------------
@@ -184,63 +149,27 @@ def spectra(pred: Batch, truth: Optional[Batch] = None, bands=None) -> Spectra:
     """Zonal power spectra, per latitude band, of the last history entry of every surface and atmospheric variable of `pred`
     (with a `truth`: of every variable both hold, for pred, truth and pred - truth); see the module's text."""
     bands = _check_bands(bands)
-    _check_same_grid(pred, truth if truth is not None else pred, "truth")
+    _fields.check_same_grid("scores", pred, truth if truth is not None else pred, "pred", "truth", "the prediction")
     n_lat, n_lon = pred.metadata.lat.shape[0], pred.metadata.lon.shape[0]
-    _check_longitudes(_host(pred.metadata.lon))
-    batches = [("pred", pred)] + ([("truth", truth)] if truth is not None else [])
-
-    names, fields = [], [[] for _ in batches]
-    for group in ("surf_vars", "atmos_vars"):
-        for k in getattr(pred, group):
-            if truth is not None and k not in getattr(truth, group):
-                continue
-            if k in names:
-                raise ValueError(f"spectra: {k!r} is both a surface and an atmospheric variable")
-            names.append(k)
-            for slot, (what, b) in enumerate(batches):
-                f = getattr(b, group)[k]
-                want = 4 if group == "surf_vars" else 5
-                if f.dim() != want or tuple(f.shape[-2:]) != (n_lat, n_lon):
-                    raise ValueError(f"spectra: {what}.{group}[{k!r}] has shape {tuple(f.shape)}, which does not fit a "
-                                     f"{n_lat} x {n_lon} grid")
-                f = f[:, -1]
-                if slot and f.shape != fields[0][-1].shape:
-                    p_shape = fields[0][-1].shape
-                    what_differs = "batch size" if f.shape[0] != p_shape[0] else "shape"
-                    raise ValueError(f"spectra: pred and {what} differ in {what_differs} for {k!r}: {tuple(p_shape)} against "
-                                     f"{tuple(f.shape)}")
-                fields[slot].append(f)
+    _fields.check_longitudes(_fields._host(pred.metadata.lon))
+    others = [("truth", truth)] if truth is not None else []
+    names, fields, layout = _fields.select_pair("spectra", pred, others)
     if not names:
         raise ValueError("spectra: pred and truth have no surface or atmospheric variable in common" if truth is not None
                          else "spectra: pred has no surface or atmospheric variable")
 
-    layout, first = [], 0
-    for name, f in zip(names, fields[0]):
-        shape = tuple(f.shape[:-2])
-        layout.append((name, first, shape))
-        first += int(np.prod(shape))
-
-    devices = {f.device for fs in fields for f in fs}
-    lat = _host(pred.metadata.lat)
-    if all(d.type == "cpu" for d in devices):
-        stack = lambda fs: np.concatenate([f.detach().reshape(-1, n_lat, n_lon).numpy() for f in fs])  # noqa: E731
-        power, rows = _power_host(stack(fields[0]), stack(fields[1]) if truth is not None else None, band_weights(lat, bands))
+    device = _fields.place("spectra", [(what, names, fs) for what, fs in zip(("pred", "truth"), fields)], n_lat, n_lon,
+                           task="transforms float32 fields (move the batches to the CPU for other precisions)")
+    lat = _fields._host(pred.metadata.lat)
+    if device == "cpu":
+        power, rows = _power_host(_fields.stack(fields[0], n_lat, n_lon),
+                                  _fields.stack(fields[1], n_lat, n_lon) if truth is not None else None, band_weights(lat, bands))
         power, rows = torch.from_numpy(power), torch.from_numpy(rows)
-    elif len(devices) == 1 and next(iter(devices)).type == "cuda":
+    else:
         from aurora_amd.engine import lib
 
-        dev = next(iter(devices))
-        for (what, _), fs in zip(batches, fields):
-            for name, f in zip(names, fs):
-                if f.dtype != torch.float32:
-                    raise TypeError(f"spectra: {what} variable {name!r} is {f.dtype}; the device path transforms float32 "
-                                    "fields (move the batches to the CPU for other precisions)")
-                if f.stride(-1) != 1 or (n_lat > 1 and f.stride(-2) != n_lon):
-                    raise ValueError(f"spectra: the planes of {what} variable {name!r} are not row-major contiguous; "
-                                     "call .contiguous() on it first")
-        power, rows = lib.spectra_power(fields[0], fields[1] if truth is not None else None,
-                                        _device_band_weights(lat, bands, dev))
-    else:
-        raise ValueError(f"spectra: the fields are on {sorted(map(str, devices))}; move the batches to the CPU or to one GPU "
-                         "first")
-    return Spectra(power, rows, tuple(layout), bands)
+        band_w = _fields.tables.get(("band weights", lat.tobytes(), bands), device, lambda: band_weights(lat, bands),
+                                    "spectra: call once with these bands before capturing a graph (the band weights are "
+                                    "uploaded on the first call, which a captured graph cannot replay)")
+        power, rows = lib.spectra_power(fields[0], fields[1] if truth is not None else None, band_w)
+    return Spectra(power, rows, layout, bands)

@@ -263,7 +263,11 @@ def test_updates_are_capturable_in_a_hip_graph():
 
 
 def test_a_cold_call_during_capture_is_refused(monkeypatch):
-    acc = FieldStats().update(make_batch(17, 32, seed=2, B=1).to(DEV))
+    # (the allocator hands the addresses of dead tensors out again, and a table that an earlier test's graph used is never
+    #  evicted: an empty table cache and a warm batch that stays alive make `fresh` cold whatever ran before)
+    monkeypatch.setattr(lib, "_plane_tables", type(lib._plane_tables)())
+    warm = make_batch(17, 32, seed=2, B=1).to(DEV)
+    acc = FieldStats().update(warm)
     fresh = make_batch(17, 32, seed=3, B=1).to(DEV)                    # addresses no call has seen
     monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: True)
     with pytest.raises(RuntimeError, match="before capturing"):

@@ -26,7 +26,7 @@ import torch.nn.functional as F
 sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
 from aurora_amd import Batch, Metadata, event_scores  # noqa: E402
 from aurora_amd.engine import lib  # noqa: E402
-from aurora_amd.scores import _device_weights  # noqa: E402
+from aurora_amd._fields import device_weights  # noqa: E402
 
 SURF, ATMOS, LEVELS = ("2t", "10u", "10v", "msl"), ("z", "u", "v", "t", "q"), 13
 N_LAT, N_LON = 721, 1440
@@ -110,7 +110,7 @@ def main() -> None:
     thresholds = {k: thr_of(v)[0].tolist() for k, v in truth.surf_vars.items()}
     thresholds.update({k: thr_of(v).cpu().numpy() for k, v in truth.atmos_vars.items()})
     thr = torch.cat([thr_of(v) for v in (*truth.surf_vars.values(), *truth.atmos_vars.values())]).float().contiguous()
-    row_w = _device_weights(truth.metadata.lat.numpy(), torch.device("cuda", torch.cuda.current_device()))
+    row_w = device_weights("event_scores_bench", truth.metadata.lat.numpy(), torch.device("cuda", torch.cuda.current_device()))
 
     kernel = lambda: lib.event_rowsums(P, T, thr, SCALES)  # noqa: E731
     whole = lambda: event_scores(pred, truth, thresholds, scales=SCALES)  # noqa: E731

@@ -130,8 +130,9 @@ def case(M: int, calls: int, repeats: int, plain_lib) -> dict:
     off_corner = (1 - (counts[:, 0, 0] + counts[:, 1, M]).double() / counts.sum(dim=(1, 2)).double()).tolist()
     arms = {"kernel": kernel, "ensemble": ensemble}
     if plain_lib is not None:
-        addresses = [lib._plane_addresses(fs, N_LAT, N_LON, "member") for fs in X] + [lib._plane_addresses(Y, N_LAT, N_LON, "truth")]
-        table = lib._plane_table(tuple(a for row in addresses for a in row), thr.device)
+        _, addresses = lib._plane_lists("probability_scores_bench", [("member", fs) for fs in X] + [("truth", Y)], thr.device, "thr",
+                                        N_LAT, N_LON)
+        table = lib._plane_table("probability_scores_bench", tuple(addresses), thr.device)
         rows_plain = torch.empty_like(got)
 
         def plain():
