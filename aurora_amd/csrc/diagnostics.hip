@@ -2,9 +2,8 @@
 // vertical integrals of moisture (total column water vapour, integrated vapour transport).  include/aurora_hip.h has the
 // arithmetic; this file has the two launches.
 //
-// Wind group.  The unit of work is one WAVEFRONT: a strip of 256 columns (a lane = four consecutive columns: 16-byte loads
-// and stores where n_lon % 4 == 0 and the plane's pointer is 16-byte aligned, 4-byte ones otherwise -- the same elements
-// either way) times 16 rows, which the wave walks from north to south with a rolling three-row window of u and v in
+// Wind group.  The unit of work is one WAVEFRONT: a strip of 256 columns (a lane = four consecutive columns: load4 / store4
+// of planes.h) times 16 rows, which the wave walks from north to south with a rolling three-row window of u and v in
 // registers: a row is loaded once by the wave and serves as row i + 1, then i, then i - 1.  The two halo rows of a chunk are
 // the neighbouring wave's (the four waves of a workgroup own consecutive chunks, so they come out of the L1 / L2 and not out
 // of HBM a second time).  East and west neighbours inside a lane's four columns are registers; the two across its edges are
@@ -15,7 +14,7 @@
 //
 // Column group.  A lane owns four consecutive points of the plane and walks the levels in level order, four levels in
 // flight, with the three sums of each point in fp64 registers.
-#include "common.h"
+#include "planes.h"
 
 namespace aurora {
 namespace {
@@ -29,8 +28,6 @@ constexpr int kBlockRows = kWaveRows * (kThreads / kWave);     // rows of a work
 constexpr int kChunk = kThreads * kPerLane;                    // points of a workgroup (column group)
 constexpr int kGroup = 4;                                      // levels in flight
 constexpr int kMaxLevels = 64;
-
-template <typename T> using gptr = __attribute__((address_space(1))) T*;
 
 struct WindArgs {
   const float* const* u;
@@ -60,34 +57,7 @@ __device__ __forceinline__ float result(double x) {
   const float r = (float)x;
   return __builtin_isfinite(r) ? r : __builtin_nanf("");
 }
-// The expression of field_stats.hip (both squares are exact in fp64: one rounding in the sum).
-__device__ __forceinline__ float wind_speed(float u, float v) {
-  const double a = (double)u, b = (double)v;
-  return result(__builtin_sqrt(__builtin_fma(a, a, b * b)));
-}
-
-// Four consecutive elements from element i0 of `base`; elements past `last` are clamped loads (never used).
-__device__ __forceinline__ void load4(const float* base, int64_t i0, int64_t last, bool vec, float (&out)[kPerLane]) {
-  const gptr<const float> g = (gptr<const float>)base;
-  if (vec) {
-    const f32x4 q = *(gptr<const f32x4>)(g + i0);
-#pragma unroll
-    for (int k = 0; k < kPerLane; ++k) out[k] = q[k];
-  } else {
-#pragma unroll
-    for (int k = 0; k < kPerLane; ++k) out[k] = g[i0 + k < last ? i0 + k : last];
-  }
-}
-__device__ __forceinline__ void store4(float* base, int64_t i0, int cnt, bool vec, const float (&in)[kPerLane]) {
-  const gptr<float> g = (gptr<float>)base;
-  if (vec) {
-    *(gptr<f32x4>)(g + i0) = f32x4{in[0], in[1], in[2], in[3]};
-  } else {
-#pragma unroll
-    for (int k = 0; k < kPerLane; ++k)
-      if (k < cnt) g[i0 + k] = in[k];
-  }
-}
+__device__ __forceinline__ float wind_speed(float u, float v) { return result(wind_speed_f64(u, v)); }
 
 __global__ __launch_bounds__(kThreads) void diagnostics_wind_kernel(const WindArgs a) {
   unsigned b = blockIdx.x;

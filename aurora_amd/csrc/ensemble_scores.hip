@@ -17,49 +17,31 @@
 //                          histogram one ballot per k: the number of valid points of the wave with x_(k) < y, added
 //                          up in scalar registers (two 16-bit counts each, flushed to lane k of a vector register).  Only sorted values enter S5, S6 and the counts, so they do not depend
 //                          on the order of the members, bit for bit.
-// Buckets up to 16 take four columns per lane (one 16-byte load per input where every plane pointer of the plane is
-// 16-byte aligned and n_lon % 4 == 0, four 4-byte loads otherwise: the same elements in the same order either way);
-// buckets 32 and 64 take one column per lane.
+// Buckets up to 16 take a quad of columns per lane (the quad rule of planes.h); buckets 32 and 64 take one column.
 //
-// The reduction tree is fixed, so a plane's sums are repeatable bit for bit and depend on nothing but its own values,
-// n_lat, n_lon and the bucket -- not on the other planes of the call, and not on the alignment of the plane pointers:
-//   lane      items (quads or columns) lane, lane + 64, ... of a row, over the rows wave, wave + 4, ... of the
-//             workgroup's row chunk;
-//   wave      xor butterfly over the 64 lanes (the counts are wave sums from the start: popcounts of ballots);
-//   workgroup the four waves' sums through LDS, added in wave order: one partial per (plane, row chunk);
-//   plane     ensemble_finish_kernel adds the partials of a plane in chunk order and turns the cumulative counts
-//             #{points : x_(k) < y} into the M + 1 bins.
-// No atomics of any kind, no tickets: the second launch is the hand-off.
+// The fp64 sums go through the reduction tree of planes.h, four waves to a workgroup, with a chunk size that depends on
+// the bucket; the integer counts ride along (they are wave sums from the start: popcounts of ballots).
+// ensemble_finish_kernel is the tree's second launch and also turns the cumulative counts #{points : x_(k) < y} into
+// the M + 1 bins.  No atomics of any kind.
 #include <utility>
 
-#include "common.h"
+#include "planes.h"
 
 namespace aurora {
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-constexpr int kSlots = 8;
+constexpr int kSlots = kSumSlots;
 constexpr int kMaxMembers = 64;
-
-template <typename T> using gptr = __attribute__((address_space(1))) T*;
 
 constexpr int bucket_of(int n_members) {
   return n_members <= 4 ? 4 : n_members <= 8 ? 8 : n_members <= 16 ? 16 : n_members <= 32 ? 32 : 64;
 }
-// Target size of a row chunk (elements of one input): the chunk of scores.hip where a point is cheap, smaller chunks
-// (more workgroups to balance) where a point costs hundreds of instructions.
+// Target size of a row chunk (elements of one input): that of scores.hip where a point is cheap, smaller chunks (more
+// workgroups to balance) where a point costs hundreds of instructions.
 constexpr int chunk_elems(int bucket) { return bucket <= 8 ? 40960 : 16384; }
 
-// Rows per chunk: a function of n_lon and the bucket alone, never of n_planes.
-__host__ __device__ constexpr int chunk_rows(int n_lon, int bucket) {
-  const int r = (chunk_elems(bucket) + n_lon - 1) / n_lon;
-  return r < kWaves ? kWaves : r;
-}
-inline int64_t chunks_per_plane(int n_lat, int n_lon, int bucket) {
-  const int r = chunk_rows(n_lon, bucket);
-  return ((int64_t)n_lat + r - 1) / r;
-}
 // Bytes of one workgroup's partial: eight doubles, then bucket + 2 counts (valid points, #{x_(k) < y} for k < bucket,
 // ties) padded to whole doubles.
 __host__ __device__ constexpr int64_t partial_bytes(int bucket) { return kSlots * 8 + ((bucket + 2) * 4 + 7) / 8 * 8; }
@@ -178,12 +160,6 @@ __device__ __forceinline__ void point(Acc& a, Counts<MB>& c, const Scale& sc, do
   a.s7 = __builtin_fma(w, vz, a.s7);
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // One workgroup = one row chunk of one plane.  MB: the bucket; PPL: points per lane and item (4: a quad of columns, 1: a
 // column).  partial: per workgroup partial_bytes(MB) bytes.
 template <int MB, int PPL>
@@ -200,17 +176,16 @@ __global__ __launch_bounds__(kThreads) void ensemble_scores_kernel(const float* 
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   const int M = __builtin_amdgcn_readfirstlane(n_members);
   const Scale sc{M, 1.0 / (double)M, 2.0 / ((double)M * (double)M), 1.0 / (double)(M - 1)};
-  // (the plane pointers are global memory: said so, the loads are global_*, not flat_*)
   const gptr<const float> T = (gptr<const float>)truth_planes[plane];
   const float* const* __restrict__ members = member_planes + plane;          // member m: members[m * n_planes]
   bool vec = false;
-  if (PPL == 4) {
+  if (PPL == 4) {                                                // the quad rule over T and the M member pointers
     uintptr_t bits = (uintptr_t)T | (uintptr_t)(n_lon & 3);
     for (int m = 0; m < M; ++m) bits |= (uintptr_t)members[(int64_t)m * n_planes];
     vec = (bits & 15) == 0;
   }
   const int n_items = PPL == 4 ? (n_lon + 3) >> 2 : n_lon;
-  const int rows = chunk_rows(n_lon, MB);
+  const int rows = chunk_rows(n_lon, chunk_elems(MB), kWaves);
   const int r_begin = chunk * rows, r_end = min(r_begin + rows, n_lat);
   const float inf = __builtin_inff();
   constexpr int kBlock = Counts<MB>::kFlushPoints / PPL;       // items between two flushes of the packed counts
@@ -235,7 +210,7 @@ __global__ __launch_bounds__(kThreads) void ensemble_scores_kernel(const float* 
 #pragma unroll
         for (int m = 0; m < MB; ++m)
           x[0][m] = m < M ? ((gptr<const float>)members[(int64_t)m * n_planes])[row0 + item] : inf;
-      } else if (vec) {
+      } else if (vec) {                                        // the quad rule, written out for the `m < M` guards
         const f32x4 t = ((gptr<const f32x4>)(T + row0))[item];
 #pragma unroll
         for (int p = 0; p < PPL; ++p) y[p] = t[p], in_row[p] = in;
@@ -283,10 +258,7 @@ __global__ __launch_bounds__(kThreads) void ensemble_scores_kernel(const float* 
   char* const mine = partial + (int64_t)blockIdx.x * partial_bytes(MB);
   const int t = (int)threadIdx.x;
   if (t < kSlots) {
-    double v = s_wave[0][t];
-#pragma unroll
-    for (int k = 1; k < kWaves; ++k) v += s_wave[k][t];
-    ((double*)mine)[t] = v;
+    ((double*)mine)[t] = sum_waves(s_wave, t);
   } else if (t >= 64 && t < 64 + MB + 2) {                     // (the second wave: both stores go out side by side)
     int v = 0;
 #pragma unroll
@@ -340,7 +312,7 @@ using namespace aurora;
 extern "C" size_t aurora_hip_ensemble_scores_workspace_bytes(int n_members, int n_planes, int n_lat, int n_lon) {
   if (n_members < 2 || n_members > kMaxMembers || n_planes < 1 || n_lat < 1 || n_lon < 1) return 0;
   const int bucket = bucket_of(n_members);
-  return (size_t)n_planes * (size_t)chunks_per_plane(n_lat, n_lon, bucket) * (size_t)partial_bytes(bucket);
+  return (size_t)n_planes * (size_t)chunks_per_plane(n_lat, n_lon, chunk_elems(bucket), kWaves) * (size_t)partial_bytes(bucket);
 }
 
 extern "C" int aurora_hip_ensemble_scores(const float* const* member_planes, const float* const* truth_planes, int n_members,
@@ -357,9 +329,9 @@ extern "C" int aurora_hip_ensemble_scores(const float* const* member_planes, con
                    "ensemble_scores: weights, outputs and workspace must be 8-byte aligned");
   const int bucket = bucket_of(n_members);
   // (a wave's counts are 32-bit: at most chunk_rows x n_lon points of a workgroup)
-  AURORA_CHECK_ARG((int64_t)chunk_rows(n_lon, bucket) * n_lon <= 0x7fffffff, "ensemble_scores: n_lon %d is too long a row",
+  AURORA_CHECK_ARG((int64_t)chunk_rows(n_lon, chunk_elems(bucket), kWaves) * n_lon <= 0x7fffffff, "ensemble_scores: n_lon %d is too long a row",
                    n_lon);
-  const int64_t n_chunks = chunks_per_plane(n_lat, n_lon, bucket);
+  const int64_t n_chunks = chunks_per_plane(n_lat, n_lon, chunk_elems(bucket), kWaves);
   const int64_t groups = n_chunks * n_planes;
   AURORA_CHECK_ARG(groups <= 0x7fffffff, "ensemble_scores: too many planes for one launch (%d planes x %lld row chunks)",
                    n_planes, (long long)n_chunks);

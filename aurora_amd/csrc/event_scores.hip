@@ -27,7 +27,7 @@
 // is a partial window, so it is bounded likewise); one lane's square <= 3969^2 = 15 752 961; the sum over a tile's 256 lanes
 // <= 256 x 15 752 961 = 4 032 758 016 < 2^32, so the workgroup's reduction is exact in 32 bits; everything after it (the
 // atomics, the tables) is 64-bit: an entry <= 4096 x 63^4 < 2^36.
-#include "common.h"
+#include "planes.h"
 
 namespace aurora {
 namespace {
@@ -38,7 +38,6 @@ constexpr int kMaxT = 8, kMaxS = 8, kMaxN = 63, kMaxLon = 4096;
 constexpr int kMaxLevels = 6;          // W1, W2, W4, W8, W16, W32: one per binary digit of the largest window size
 static_assert((1 << kMaxLevels) > kMaxN && (1 << (kMaxLevels - 1)) <= kMaxN, "kMaxLevels must be the number of binary digits of kMaxN");
 
-template <typename T> using gptr = __attribute__((address_space(1))) T*;
 
 struct ScaleList {
   int n[kMaxS];

@@ -6,18 +6,17 @@
 // include/aurora_hip.h has the table) is read once, updated by the call's n_samples values of that point in sample order
 // in registers, and written once.  Nothing is reduced across threads, so there is no tree to fix: a point's state
 // depends on its own samples alone -- not on n_planes, on the other planes, on how the samples are grouped into calls
-// (the one `update` below runs once per sample whether a call brings 1 or 64), or on pointer alignment.
+// (the one `update` below runs once per sample whether a call brings 1 or 64), or on pointer alignment (planes.h).
 //
 // The sums are SHIFTED: d = v - origin with origin the point's first valid value, so a pressure of 1e5 Pa that varies by
 // a few hundred keeps its digits (sum d^2 - (sum d)^2 / n cancels at the size of the variation, not of the raw value).
 //
-// One workgroup = one chunk of 1024 consecutive points of one plane, a lane = four consecutive points (16-byte loads and
-// stores where n_points % 4 == 0 and the plane's pointers are 16-byte aligned, 4-byte ones otherwise: the same elements
-// either way).  The samples are loaded four at a time, then applied one after the other.  The kernel is a template on a
+// One workgroup = one chunk of 1024 consecutive points of one plane, a lane = four consecutive points (load4 / store4 of
+// planes.h).  The samples are loaded four at a time, then applied one after the other.  The kernel is a template on a
 // threshold-count bucket (0, 1, 2, 4, 8) with a wave-uniform `t < T` guard, so the per-threshold state has compile-time
 // register indices.  The global index of the call's first sample is read from device memory; a second one-thread launch
 // advances it, so a captured call replays with the right indices.
-#include "common.h"
+#include "planes.h"
 
 namespace aurora {
 namespace {
@@ -29,9 +28,6 @@ constexpr int kGroup = 4;                       // samples in flight
 constexpr int kMaxSamples = 64;
 constexpr int kMaxThresholds = 8;
 
-template <typename T> using gptr = __attribute__((address_space(1))) T*;
-// 16 bytes of V: four 4-byte or two 8-byte elements.
-template <typename V> struct Vec16 { typedef V type __attribute__((ext_vector_type(16 / sizeof(V)))); };
 
 struct State {
   int32_t* n;
@@ -68,8 +64,7 @@ __device__ __forceinline__ void update(Point<TB>& p, float x, float b, float r, 
   bool ok = __builtin_isfinite(x);
   if (has_b) {
     ok = ok && __builtin_isfinite(b);
-    const double a = (double)x, bb = (double)b;
-    x = (float)__builtin_sqrt(__builtin_fma(a, a, bb * bb));    // (both squares are exact in fp64: one rounding in the sum)
+    x = (float)wind_speed_f64(x, b);
     ok = ok && __builtin_isfinite(x);
   }
   if (has_r) ok = ok && __builtin_isfinite(r);
@@ -92,44 +87,6 @@ __device__ __forceinline__ void update(Point<TB>& p, float x, float b, float r, 
       p.lg[t] = max(p.lg[t], p.run[t]);
     }
   p.n += 1;
-}
-
-// Four consecutive elements from i0; `cnt` of them are inside the plane (the others are clamped loads / skipped stores).
-template <typename V>
-__device__ __forceinline__ void load4(const V* base, int64_t i0, int64_t last, bool vec, V (&out)[kPerLane]) {
-  const gptr<const V> g = (gptr<const V>)base;
-  typedef typename Vec16<V>::type vec_t;
-  constexpr int kPer = 16 / (int)sizeof(V);
-  if (vec) {
-#pragma unroll
-    for (int j = 0; j < kPerLane / kPer; ++j) {
-      const vec_t q = ((gptr<const vec_t>)(g + i0))[j];
-#pragma unroll
-      for (int k = 0; k < kPer; ++k) out[j * kPer + k] = q[k];
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < kPerLane; ++k) out[k] = g[i0 + k < last ? i0 + k : last];
-  }
-}
-template <typename V>
-__device__ __forceinline__ void store4(V* base, int64_t i0, int cnt, bool vec, const V (&in)[kPerLane]) {
-  const gptr<V> g = (gptr<V>)base;
-  typedef typename Vec16<V>::type vec_t;
-  constexpr int kPer = 16 / (int)sizeof(V);
-  if (vec) {
-#pragma unroll
-    for (int j = 0; j < kPerLane / kPer; ++j) {
-      vec_t q;
-#pragma unroll
-      for (int k = 0; k < kPer; ++k) q[k] = in[j * kPer + k];
-      ((gptr<vec_t>)(g + i0))[j] = q;
-    }
-  } else {
-#pragma unroll
-    for (int k = 0; k < kPerLane; ++k)
-      if (k < cnt) g[i0 + k] = in[k];
-  }
 }
 
 #define AURORA_FS_LOAD(V, array, field)                                 \
@@ -160,7 +117,7 @@ template <int TB> __global__ __launch_bounds__(kThreads) void field_stats_kernel
   const float* const R = a.ref ? a.ref[plane] : nullptr;
   const bool has_r = R != nullptr;
   const bool has_b = a.second != nullptr && a.second[plane] != nullptr;
-  uintptr_t bits = (uintptr_t)R | (uintptr_t)((a.n_points & 3) * 4);
+  uintptr_t bits = (uintptr_t)R | (uintptr_t)((a.n_points & 3) * 4);   // the quad rule over every input pointer of the plane
   for (int s = 0; s < S; ++s) {
     bits |= (uintptr_t)a.planes[(int64_t)s * a.n_planes + plane];
     if (has_b) bits |= (uintptr_t)a.second[(int64_t)s * a.n_planes + plane];

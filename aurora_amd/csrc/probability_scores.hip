@@ -10,8 +10,7 @@
 //
 // Mapping.  A wavefront owns a row: a 256-thread workgroup takes four consecutive rows of one plane, the grid is n_planes x
 // ceil(n_lat / 4), and the plane index, its thresholds and its pointers are wave-uniform (scalar loads).  A lane takes a
-// quad of columns per step (one 16-byte load per input where n_lon % 4 == 0 and every pointer of the plane is 16-byte
-// aligned, four 4-byte loads otherwise: the same elements either way) and STREAMS the members past it in a runtime loop
+// quad of columns per step (the quad rule and load_quad of planes.h) and STREAMS the members past it in a runtime loop
 // unrolled by four: per member `ok &= finite(x)` and a byte-packed counter gets `+= (x >= thr_t) << 8 (t mod 4)` (k <= 64
 // fits a byte; thresholds 0..3 share one register, 4..7 a second one that only the T > 4 instantiation carries).  No
 // member-count bucket, no template on M; slots t >= T hold a NaN threshold and are never binned.
@@ -22,7 +21,7 @@
 // LDS address.  kCornerBallot takes those two bins by __ballot + popcount into scalar registers, added once per row by one
 // lane per threshold, and sends only the remaining lanes through the atomic; AURORA_PROBABILITY_PLAIN_ATOMICS builds the
 // plain form (every valid lane an LDS atomic) for tools/probability_scores_bench.py, which times the two side by side.
-#include "common.h"
+#include "planes.h"
 
 namespace aurora {
 namespace {
@@ -37,15 +36,6 @@ constexpr bool kCornerBallot = false;
 #else
 constexpr bool kCornerBallot = true;
 #endif
-
-template <typename T> using gptr = __attribute__((address_space(1))) T*;
-
-// The quad `item` of a row: columns 4 item .. 4 item + 3 (VEC), or the columns col[0..3] (clamped into the row by the caller).
-template <bool VEC>
-__device__ __forceinline__ f32x4 load_quad(gptr<const float> row, int item, const unsigned (&col)[4]) {
-  if (VEC) return ((gptr<const f32x4>)row)[item];
-  return f32x4{row[col[0]], row[col[1]], row[col[2]], row[col[3]]};
-}
 
 template <bool BELOW> __device__ __forceinline__ bool event(float x, float thr) { return BELOW ? x <= thr : x >= thr; }
 
@@ -150,10 +140,9 @@ __global__ __launch_bounds__(kThreads) void probability_scores_kernel(const floa
     float thr[TT];
 #pragma unroll
     for (int t = 0; t < TT; ++t) thr[t] = t < T ? thresholds[(int64_t)plane * T + t] : __builtin_nanf("");
-    // (the plane pointers are global memory: said so, the loads are global_*, not flat_*)
     const gptr<const float> truth = (gptr<const float>)truth_planes[plane];
     const float* const* __restrict__ members = member_planes + plane;        // member m: members[m * n_planes]
-    uintptr_t bits = (uintptr_t)truth | (uintptr_t)(n_lon & 3);
+    uintptr_t bits = (uintptr_t)truth | (uintptr_t)(n_lon & 3);   // the quad rule over truth and the M member pointers
     for (int m = 0; m < M; ++m) bits |= (uintptr_t)members[(int64_t)m * n_planes];
     const int64_t row0 = (int64_t)row * n_lon;
     if ((bits & 15) == 0)

@@ -10,7 +10,7 @@
 #include <cmath>
 #include <vector>
 
-#include "common.h"
+#include "planes.h"
 
 namespace aurora {
 namespace {
@@ -20,7 +20,6 @@ constexpr int kColsPerThread = 2;               // output columns per lane: kThr
 constexpr int kRowsPerTile = 4;                 // output rows per workgroup
 constexpr int kPlanesPerGroup = 8;              // planes one workgroup sweeps with the same table entries
 
-template <typename T> using gptr = __attribute__((address_space(1))) T*;
 
 // scipy's evaluate_linear_2d: v00 (1-y)(1-x) + v01 (1-y) x + v10 y (1-x) + v11 y x, left to right.
 __device__ __forceinline__ double bilinear(double v00, double v01, double v10, double v11, double ay0, double ay1,

@@ -5,39 +5,20 @@
 // that is present is finite, with the row weight w[i] (include/aurora_hip.h has the table).  All differences and
 // products are formed in fp64 from the fp32 inputs; nothing is accumulated in fp32.
 //
-// The reduction tree is fixed, so a plane's sums are repeatable bit for bit and depend on nothing but its own values,
-// n_lat and n_lon -- not on the other planes of the call, and not on the alignment of the plane pointers:
-//   lane      columns 4 q .. 4 q + 3 of a row for q = lane, lane + 64, ... (one 16-byte load per input where the plane
-//             pointers are 16-byte aligned and n_lon % 4 == 0, four 4-byte loads otherwise: the same elements in the
-//             same order either way), over the rows wave, wave + 4, ... of the workgroup's row chunk;
-//   wave      xor butterfly over the 64 lanes;
-//   workgroup the four waves' sums through LDS, added in wave order: one partial per (plane, row chunk);
-//   plane     scores_finish_kernel adds the partials of a plane in chunk order.
-// No floating-point atomics, no tickets: the second launch is the hand-off.
-#include "common.h"
+// A lane takes quads of columns (the quad rule of planes.h) and the sums go through the reduction tree of planes.h, four
+// waves to a workgroup; scores_finish_kernel is its second launch.
+#include "planes.h"
 
 namespace aurora {
 namespace {
 
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
-constexpr int kSlots = 8;
+constexpr int kSlots = kSumSlots;
 #ifndef AURORA_SCORES_CHUNK_ELEMS               // (a probe build may set it: AURORA_BUILD_FLAGS=-DAURORA_SCORES_CHUNK_ELEMS=...)
 #define AURORA_SCORES_CHUNK_ELEMS 40960
 #endif
 constexpr int kChunkElems = AURORA_SCORES_CHUNK_ELEMS;   // target size of a row chunk (elements of one input)
-
-template <typename T> using gptr = __attribute__((address_space(1))) T*;
-
-// Rows per chunk: a function of n_lon alone (and chunks per plane of n_lat, n_lon alone), never of n_planes.
-__host__ __device__ inline int chunk_rows(int n_lon) {
-  const int r = (kChunkElems + n_lon - 1) / n_lon;
-  return r < kWaves ? kWaves : r;
-}
-inline int64_t chunks_per_plane(int n_lat, int n_lon) {
-  const int r = chunk_rows(n_lon);
-  return ((int64_t)n_lat + r - 1) / r;
-}
 
 struct Acc {
   double s2 = 0.0, s3 = 0.0, s4 = 0.0, s5 = 0.0, s6 = 0.0, s7 = 0.0;
@@ -67,12 +48,6 @@ __device__ __forceinline__ void point(Acc& a, double w, float pf, float tf, floa
   }
 }
 
-__device__ __forceinline__ double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
-
 // One workgroup = one row chunk of one plane; partial[(plane * n_chunks + chunk) * 8 + slot].
 template <bool kClim>
 __global__ __launch_bounds__(kThreads) void scores_kernel(const float* const* __restrict__ pred_planes,
@@ -84,13 +59,12 @@ __global__ __launch_bounds__(kThreads) void scores_kernel(const float* const* __
   const int plane = (int)(blockIdx.x / (unsigned)n_chunks), chunk = (int)(blockIdx.x % (unsigned)n_chunks);
   const int lane = (int)threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
-  // (the plane pointers are global memory: said so, the loads are global_*, not flat_*)
   const gptr<const float> P = (gptr<const float>)pred_planes[plane];
   const gptr<const float> T = (gptr<const float>)truth_planes[plane];
   const gptr<const float> C = kClim ? (gptr<const float>)clim_planes[plane] : P;
-  const bool vec = (n_lon & 3) == 0 && ((((uintptr_t)P | (uintptr_t)T | (uintptr_t)C) & 15) == 0);
+  const bool vec = quads_aligned(n_lon, P, T, C);
   const int n_quads = (n_lon + 3) >> 2;
-  const int rows = chunk_rows(n_lon);
+  const int rows = chunk_rows(n_lon, kChunkElems, kWaves);
   const int r_begin = chunk * rows, r_end = min(r_begin + rows, n_lat);
 
   Acc a;
@@ -100,7 +74,7 @@ __global__ __launch_bounds__(kThreads) void scores_kernel(const float* const* __
     const double w = row_w[r];
     const int64_t row0 = (int64_t)r * n_lon;
     a.n = 0;
-    if (vec) {
+    if (vec) {                                                 // the quad rule, p, t and c column by column
       const gptr<const f32x4> p4 = (gptr<const f32x4>)(P + row0), t4 = (gptr<const f32x4>)(T + row0),
                               c4 = (gptr<const f32x4>)(C + row0);
 #pragma unroll 2
@@ -139,13 +113,7 @@ __global__ __launch_bounds__(kThreads) void scores_kernel(const float* const* __
   __syncthreads();
   if (threadIdx.x < kSlots) {
     const int s = (int)threadIdx.x;
-    double v = 0.0;
-    if (kClim || s < 5) {
-      v = s_wave[0][s];
-#pragma unroll
-      for (int k = 1; k < kWaves; ++k) v += s_wave[k][s];
-    }
-    partial[(int64_t)blockIdx.x * kSlots + s] = v;
+    partial[(int64_t)blockIdx.x * kSlots + s] = kClim || s < 5 ? sum_waves(s_wave, s) : 0.0;
   }
 }
 
@@ -169,7 +137,7 @@ using namespace aurora;
 
 extern "C" size_t aurora_hip_scores_workspace_bytes(int n_planes, int n_lat, int n_lon) {
   if (n_planes < 1 || n_lat < 1 || n_lon < 1) return 0;
-  return (size_t)n_planes * (size_t)chunks_per_plane(n_lat, n_lon) * kSlots * sizeof(double);
+  return (size_t)n_planes * (size_t)chunks_per_plane(n_lat, n_lon, kChunkElems, kWaves) * kSlots * sizeof(double);
 }
 
 extern "C" int aurora_hip_scores(const float* const* pred_planes, const float* const* truth_planes,
@@ -182,7 +150,7 @@ extern "C" int aurora_hip_scores(const float* const* pred_planes, const float* c
                    "scores: null plane array, weight, output or workspace pointer");
   AURORA_CHECK_ARG(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)sums & 7) == 0 && ((uintptr_t)row_w & 7) == 0,
                    "scores: weights, output and workspace must be 8-byte aligned");
-  const int64_t n_chunks = chunks_per_plane(n_lat, n_lon);
+  const int64_t n_chunks = chunks_per_plane(n_lat, n_lon, kChunkElems, kWaves);
   const int64_t groups = n_chunks * n_planes;
   AURORA_CHECK_ARG(groups <= 0x7fffffff, "scores: too many planes for one launch (%d planes x %lld row chunks)", n_planes,
                    (long long)n_chunks);

@@ -26,7 +26,7 @@
 // Row validity comes from the inputs: while staging, a non-finite value flags its grid row and is replaced by 0.
 // The tree is fixed and depends on n_lat, N and has_truth only: results are repeatable bit for bit, independent of the other
 // planes of the call, and independent of pointer alignment (every global load of a plane is a 4-byte load).
-#include "common.h"
+#include "planes.h"
 
 namespace aurora {
 namespace {
@@ -45,7 +45,6 @@ constexpr int kMaxBands = 8;
 constexpr int kMaxLon = 4096;
 constexpr int kStageQ = 16 * kChunkJ / kThreads;        // staged values per thread and chunk (4)
 
-template <typename T> using gptr = __attribute__((address_space(1))) T*;
 
 __host__ __device__ inline int64_t chunks_per_plane(int n_lat) { return ((int64_t)n_lat + kChunkRows - 1) / kChunkRows; }
 // doubles of one chunk partial: (field, band, k) sums, then per band the weight sum and the count of valid rows
