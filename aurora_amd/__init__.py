@@ -8,11 +8,13 @@ histogram: aurora_amd/ensemble.py), and `spectra` gives the zonal power spectra 
 (aurora_amd/events.py), and `probability_scores` the Brier score, reliability diagram and ROC of an ensemble's event
 probabilities (aurora_amd/probability.py), and `FieldStats` accumulates per-point statistics over the steps of a roll-out or
 the members of an ensemble as maps (aurora_amd/fieldstats.py), and `diagnostics` forms the derived fields all of them can
-then take -- vorticity, divergence, wind speed, integrated vapour transport -- as a `Batch` (aurora_amd/diagnostics.py); the
-reference has no counterpart.
+then take -- vorticity, divergence, wind speed, integrated vapour transport -- as a `Batch` (aurora_amd/diagnostics.py), and
+`conditional_scores` gives the error by bin of the truth and over its tails, against climatology maps such as those of
+`FieldStats` (aurora_amd/conditional.py); the reference has no counterpart.
 """
 
 from aurora_amd.batch import Batch, Metadata
+from aurora_amd.conditional import ConditionalScores, conditional_scores
 from aurora_amd.diagnostics import diagnostics
 from aurora_amd.ensemble import EnsembleScores, ensemble_scores
 from aurora_amd.events import EventScores, event_scores
@@ -58,5 +60,7 @@ __all__ = [
     "ProbabilityScores",
     "FieldStats",
     "diagnostics",
+    "conditional_scores",
+    "ConditionalScores",
     "Tracker",
 ]

@@ -131,10 +131,11 @@ def layout_of(names: Sequence[str], fields: Sequence[torch.Tensor]) -> Layout:
     return tuple(layout)
 
 
-def select_pair(fn: str, pred: Batch, others: Sequence[tuple[str, Batch]], only=None):
+def select_pair(fn: str, pred: Batch, others: Sequence[tuple[str, Batch]], only=None, repeated: Sequence[str] = ()):
     """The last history entry of every variable (of `only`, if given) that `pred` and the first of `others` hold, which
     every further one must hold too, for the deterministic front ends: (names, one list of fields per batch, pred's first,
-    and the layout).  The batches are on one checked grid."""
+    and the layout).  The batches are on one checked grid.  An operand named in `repeated` may have batch size 1 against a
+    larger `pred`: its field is then expanded, a view whose batch elements are the one plane (nothing is copied)."""
     n_lat, n_lon = pred.metadata.lat.shape[0], pred.metadata.lon.shape[0]
     batches = [("pred", pred), *others]
     names, fields = [], [[] for _ in batches]
@@ -152,6 +153,8 @@ def select_pair(fn: str, pred: Batch, others: Sequence[tuple[str, Batch]], only=
                 f = getattr(b, group)[k]
                 check_field(fn, f, what, group, k, n_lat, n_lon)
                 f = f[:, -1]
+                if what in repeated and f.shape[0] == 1 and f.shape[1:] == fields[0][-1].shape[1:]:
+                    f = f.expand_as(fields[0][-1])
                 if slot and f.shape != fields[0][-1].shape:
                     raise _differ(fn, "pred", what, k, fields[0][-1].shape, f.shape)
                 fields[slot].append(f)
@@ -272,23 +275,23 @@ def place(fn: str, labelled, n_lat: int, n_lon: int, task: str = SCORES_TASK, fi
 
 
 # ---- thresholds --------------------------------------------------------------------------------------------------------
-def threshold_rows(fn: str, name: str, value, levels: Optional[int]) -> np.ndarray:
-    """(1 or C, T_v) float32 thresholds of one variable."""
+def threshold_rows(fn: str, name: str, value, levels: Optional[int], noun: str = "thresholds") -> np.ndarray:
+    """(1 or C, T_v) float32 thresholds of one variable; `noun` is what the messages call them."""
     try:
         a = np.asarray(value, dtype=np.float64)
     except (TypeError, ValueError):
-        raise ValueError(f"{fn}: the thresholds of {name!r} must be numbers") from None
+        raise ValueError(f"{fn}: the {noun} of {name!r} must be numbers") from None
     if a.ndim == 1:
         a = a[None]
     elif a.ndim == 2 and levels is not None:
         if a.shape[0] != levels:
-            raise ValueError(f"{fn}: the thresholds of {name!r} have shape {a.shape}; a (C, T) array needs C = {levels} "
+            raise ValueError(f"{fn}: the {noun} of {name!r} have shape {a.shape}; a (C, T) array needs C = {levels} "
                              "levels")
     else:
         want = "a sequence" if levels is None else f"a sequence or a ({levels}, T) array"
-        raise ValueError(f"{fn}: the thresholds of {name!r} have shape {a.shape}; {want} is needed")
+        raise ValueError(f"{fn}: the {noun} of {name!r} have shape {a.shape}; {want} is needed")
     if not 1 <= a.shape[1] <= MAX_THRESHOLDS:
-        raise ValueError(f"{fn}: 1 to {MAX_THRESHOLDS} thresholds per variable, {name!r} has {a.shape[1]}")
+        raise ValueError(f"{fn}: 1 to {MAX_THRESHOLDS} {noun} per variable, {name!r} has {a.shape[1]}")
     return a.astype(np.float32)
 
 
@@ -298,15 +301,24 @@ def pad_thresholds(rows: Sequence[np.ndarray]) -> np.ndarray:
     return np.concatenate([np.pad(r, ((0, 0), (0, T - r.shape[1])), constant_values=np.nan) for r in rows]).astype(np.float32)
 
 
-def threshold_table(fn: str, thresholds, layout: Layout) -> np.ndarray:
+def threshold_table(fn: str, thresholds, layout: Layout, noun: str = "thresholds") -> np.ndarray:
     """(n_planes, T) float32: the thresholds of every variable of `layout`, one row per plane in (B, [C]) order."""
     rows = []
     for name, _, lead in layout:
-        r = threshold_rows(fn, name, thresholds[name], lead[1] if len(lead) == 2 else None)
+        r = threshold_rows(fn, name, thresholds[name], lead[1] if len(lead) == 2 else None, noun)
         if len(lead) == 2:
             r = np.broadcast_to(r, (lead[1], r.shape[1]))
         rows.append(np.broadcast_to(r, (lead[0], *r.shape)).reshape(-1, r.shape[1]))
     return pad_thresholds(rows)
+
+
+def check_ascending(fn: str, table: np.ndarray, layout: Layout, noun: str = "edges") -> None:
+    """The values of every row of `table` ((n_planes, T), NaN: none) that are not NaN ascend strictly."""
+    for name, first, lead in layout:
+        for row in table[first:first + math.prod(lead)]:
+            v = row[~np.isnan(row)]
+            if not np.all(v[1:] > v[:-1]):
+                raise ValueError(f"{fn}: the {noun} of {name!r} must be strictly ascending, got {v.tolist()}")
 
 
 # ---- finalisation: the same torch code on either device ----------------------------------------------------------------

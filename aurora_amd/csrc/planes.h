@@ -1,6 +1,7 @@
 // Plane access and fixed-order reduction shared by the verification kernels (scores, ensemble_scores, probability_scores,
-// event_scores, field_stats, spectra, diagnostics) and regrid.  Three contracts live here and nowhere else: the quad rule,
-// the reduction tree and the wind-speed expression.  A plane is n_lat x n_lon fp32, row-major, in global memory.
+// event_scores, conditional_scores, field_stats, spectra, diagnostics) and regrid.  Three contracts live here and nowhere
+// else: the quad rule, the reduction tree and the wind-speed expression.  A plane is n_lat x n_lon fp32, row-major, in global
+// memory.
 #pragma once
 
 #include "common.h"
@@ -103,9 +104,10 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
   for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
   return v;
 }
-// Slot s of the workgroup: lane 0 of wave k has stored its wave's sum in s_wave[k][s], and a barrier has passed.
-template <int W>
-__device__ __forceinline__ double sum_waves(const double (&s_wave)[W][kSumSlots], int s) {
+// Slot s of the workgroup: lane 0 of wave k has stored its wave's sum in s_wave[k][s], and a barrier has passed.  (S slots
+// per wave: kSumSlots, or bins x slots where a kernel keeps its sums per bin.)
+template <int W, int S>
+__device__ __forceinline__ double sum_waves(const double (&s_wave)[W][S], int s) {
   double v = s_wave[0][s];
 #pragma unroll
   for (int k = 1; k < W; ++k) v += s_wave[k][s];

@@ -143,6 +143,9 @@ _SIGNATURES = {
     "aurora_hip_diagnostics": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, ctypes.c_double, c_int,
                                        c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int,
                                        c_void_p, c_int, c_int, c_void_p]),
+    "aurora_hip_conditional_scores_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int]),
+    "aurora_hip_conditional_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int,
+                                              c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -945,6 +948,50 @@ def event_rowsums(pred: list[torch.Tensor], truth: list[torch.Tensor], threshold
             _check(load().aurora_hip_event_scores(base, base + 8 * n, n, n_lat, n_lon, _ptr(thresholds), T, host_scales, S,
                                                   1 if below else 0, _ptr(rowsums), _ptr(valid), None, 0, _stream()))
     return rowsums, valid
+
+
+# ---- conditional sums: the error sums per bin of the truth (aurora_hip_conditional_scores) ------------------------------
+def conditional_scores_workspace_bytes(n_planes: int, n_lat: int, n_lon: int, n_edges: int) -> int:
+    return int(load().aurora_hip_conditional_scores_workspace_bytes(n_planes, n_lat, n_lon, n_edges))
+
+
+def conditional_sums(pred: list[torch.Tensor], truth: list[torch.Tensor], centre: Optional[list[torch.Tensor]],
+                     scale: Optional[list[torch.Tensor]], edges: torch.Tensor, by_pred: bool, row_w: torch.Tensor) -> torch.Tensor:
+    """The five sums of include/aurora_hip.h (count, w, w d, w d^2, w |d|) per bin of every plane of `pred` against the same
+    plane of `truth`, binned by the rule there with the planes of `centre` and `scale` (each a list or None), as an
+    (n_planes, E + 1, 5) fp64 tensor on the device, in ONE aurora_hip_conditional_scores call.
+
+    pred / truth / centre / scale: lists of fp32 (..., n_lat, n_lon) tensors on one device with row-major contiguous planes
+    (any leading strides -- a leading stride of 0 repeats a plane's address, nothing is copied -- and any 4-byte plane
+    alignment), the same leading shapes in each list; edges: contiguous (n_planes, E) fp32 on that device, 1 <= E <= 8 (NaN:
+    no edge); row_w: (n_lat,) fp64 on that device.  The plane-pointer table is cached by address as in `scores_sums`.
+    Nothing of plane size is allocated and the host does not wait for the device."""
+    assert row_w.is_cuda and row_w.dtype == torch.float64 and row_w.dim() == 1 and row_w.is_contiguous(), \
+        "conditional_sums: row_w must be a contiguous fp64 vector on the device"
+    assert edges.is_cuda and edges.dtype == torch.float32 and edges.dim() == 2 and edges.is_contiguous(), \
+        "conditional_sums: edges must be a contiguous (n_planes, E) fp32 matrix on the device"
+    dev, n_lat, (n_edge_planes, E) = row_w.device, row_w.shape[0], edges.shape
+    assert edges.device == dev, "conditional_sums: every tensor must be on the device of row_w"
+    assert 1 <= E <= EVENT_MAX_THRESHOLDS, f"conditional_sums: 1..{EVENT_MAX_THRESHOLDS} edges, got {E}"
+    lists = [("prediction", pred), ("truth", truth)] + [(what, fs) for what, fs in (("centre", centre), ("scale", scale))
+                                                        if fs is not None]
+    n_lon = pred[0].shape[-1] if pred else 1
+    n, addresses = _plane_lists("conditional_sums", lists, dev, "row_w", n_lat, n_lon)
+    assert n == n_edge_planes, f"conditional_sums: {n} planes but edges for {n_edge_planes}"
+    sums = torch.empty(n, E + 1, 5, dtype=torch.float64, device=dev)
+    if n == 0:
+        return sums
+    with torch.cuda.device(dev):
+        table = _plane_table("conditional_sums", tuple(addresses), dev)
+        workspace = torch.empty(conditional_scores_workspace_bytes(n, n_lat, n_lon, E), dtype=torch.uint8, device=dev)
+        base = table.data_ptr()
+        centre_at = base + 16 * n if centre is not None else None
+        scale_at = base + 8 * n * (len(lists) - 1) if scale is not None else None
+        with _Timed("conditional_scores", float(n * n_lat * n_lon * 4 * len(lists))):   # bytes read
+            _check(load().aurora_hip_conditional_scores(base, base + 8 * n, centre_at, scale_at, n, n_lat, n_lon, _ptr(edges), E,
+                                                        1 if by_pred else 0, _ptr(row_w), _ptr(sums), _ptr(workspace),
+                                                        _stream()))
+    return sums
 
 
 # ---- event probabilities of an ensemble (aurora_hip_probability_scores) -----------------------------------------------

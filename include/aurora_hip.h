@@ -846,6 +846,37 @@ int aurora_hip_probability_scores(const float* const* member_planes, const float
                                   int n_planes, int n_lat, int n_lon, const float* thresholds, int n_thresholds, int below,
                                   int32_t* rows, void* stream);
 
+/* ---- conditional scores on the device (aurora_amd.conditional_scores: error by truth bin, thresholded RMSE of the tails; not
+ * in the reference) -----------------------------------------------------------------------------------------------------------
+ * Planes as above.  For every plane k < n_planes the prediction p, the truth t and, unless its array is NULL, a centre map c and
+ * a scale map s are read once.  With v the binned field (t, or p with by_pred != 0) and e_j = edges[k n_edges + j] (fp32):
+ *   a   = (double)v - (double)c                      (one fp64 subtraction; c = 0 without centre_planes)
+ *   bin = #{ j < n_edges : a >= (double)e_j * (double)s }   (one fp64 product per edge, alone on its side of the comparison;
+ *                                                     s = 1 without scale_planes; a NaN edge is never passed)
+ * so a plane has n_edges + 1 bins, and with ascending edges bin b holds the points between edge b - 1 and edge b.  A point is
+ * VALID where p and t are finite, every map that is present is finite, and s >= 0 (s = 0 is legal: the products are +-0 and
+ * the point falls by the sign of a).  Over the valid points of bin b, with w = row_w[i] of the point's row i and d = p - t:
+ *   sums[(k (n_edges + 1) + b) 5 + slot]:  slot 0  1 (the count, exact)   slot 1  w   slot 2  w d   slot 3  w d^2   slot 4  w |d|
+ * -- the first five slots of aurora_hip_scores, per bin.  An empty bin gives zeros.  Differences and products are formed in
+ * fp64 from the fp32 inputs and accumulated in fp64.
+ * Determinism: the reduction tree of aurora_hip_scores (lane -> wavefront -> workgroup -> one partial per plane, row chunk and
+ * bin in `workspace` -> partials added in chunk order by a second launch; no atomics).  A point enters every bin but its own
+ * as exactly +0, so the five sums of a bin are repeatable bit for bit and depend on the points of THAT bin, row_w, n_lat and
+ * n_lon alone: not on n_planes, on the other planes, on pointer alignment, or on how many other edges the call has (the bin
+ * [e1, e2) of a 2-edge call has the bits of that bin in an 8-edge call).
+ * The four plane arrays are DEVICE arrays of n_planes plane pointers (4-byte aligned; 16-byte loads are used where all of a
+ * plane's pointers and n_lon allow; an array may name the same plane for several k); edges: n_planes x n_edges DEVICE floats,
+ * 1 <= n_edges <= 8; row_w: n_lat device doubles; sums: n_planes x (n_edges + 1) x 5 device doubles; workspace:
+ * aurora_hip_conditional_scores_workspace_bytes(n_planes, n_lat, n_lon, n_edges) device bytes, 8-byte aligned, no
+ * initialisation needed (0 bytes for an argument out of range).  Arguments are checked before anything is enqueued
+ * (AURORA_E_ARG and aurora_hip_last_error()).  n_planes = 0 is a no-op.  The inputs are not modified.  Two launches, no host
+ * synchronisation, no allocation, no environment variable: capturable in a hipGraph. */
+size_t aurora_hip_conditional_scores_workspace_bytes(int n_planes, int n_lat, int n_lon, int n_edges);
+int aurora_hip_conditional_scores(const float* const* pred_planes, const float* const* truth_planes,
+                                  const float* const* centre_planes, const float* const* scale_planes, int n_planes, int n_lat,
+                                  int n_lon, const float* edges, int n_edges, int by_pred, const double* row_w, double* sums,
+                                  void* workspace, void* stream);
+
 /* ---- derived fields on the device (aurora_amd.diagnostics: relative vorticity, divergence, wind speed, total column water
  * vapour, integrated vapour transport; not in the reference) -----------------------------------------------------------------
  * Planes as above (n_lat x n_lon fp32, row-major), n_lat >= 2, n_lon >= 2.  Constants of the caller's tables: the Earth's
