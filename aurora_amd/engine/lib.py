@@ -453,8 +453,10 @@ def window_attention(qkv: torch.Tensor, qkv_bias: Optional[torch.Tensor], out: t
         assert qkv.is_contiguous() and qkv.shape == (heads, B * L, 3, 64) and qkv.dtype == torch.bfloat16
         assert out.numel() == B * L_out * D and out.dtype == qkv.dtype and tok.dtype == torch.int32 and tok.dim() == 2
         n_windows, n_tok = tok.shape
+        # (the stride of a dimension of size 1 is arbitrary: a contiguous single plane may report 64)
+        plane_stride = qkv.stride(0) if heads > 1 else B * L * 192
         with _Timed("window_attention_bf16", 4.0 * B * n_windows * n_tok * D * 2):
-            _check(load().aurora_hip_window_attention_planes(_ptr(qkv), qkv.stride(0), _ptr(qkv_bias), _ptr(out), _ptr(tok), _ptr(grp),
+            _check(load().aurora_hip_window_attention_planes(_ptr(qkv), plane_stride, _ptr(qkv_bias), _ptr(out), _ptr(tok), _ptr(grp),
                                                              B, L, L_out, D, heads, n_windows, n_tok, dtype_code(qkv.dtype),
                                                              _stream()))
         return out
