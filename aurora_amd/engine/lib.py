@@ -608,13 +608,14 @@ def perceiver_probs_scores(vs: torch.Tensor, s_off: int, B: int, cols_per_b: int
 
 def perceiver_out(Vp: torch.Tensor, w_pairs: torch.Tensor, P: torch.Tensor, out: torch.Tensor, n_cols: int, Lq: int,
                   Lk: int, heads: int, head_dim: int, bias: Optional[torch.Tensor] = None, guard=None) -> torch.Tensor:
-    """out[col * Lq + l] = sum_h sum_j P[col, h, l, j] W[:, h] Vp[col * Lk + j, h] (aurora_hip_perceiver_out)."""
-    assert Vp.is_contiguous() and w_pairs.is_contiguous() and P.is_contiguous() and out.is_contiguous()
-    N = out.shape[1]
+    """out[col * Lq + l] = sum_h sum_j P[col, h, l, j] W[:, h] Vp[col * Lk + j, h] (aurora_hip_perceiver_out).
+    `out` may be a column block of wider rows; `w_pairs` rows may be longer than heads * head_dim."""
+    assert Vp.is_contiguous() and w_pairs.is_contiguous() and P.is_contiguous()
+    ldo, N = _rows(out)
     word, limit = guard if guard is not None else (None, 0.0)
     with _Timed("perceiver_out", 2.0 * n_cols * Lk * N * heads * head_dim):
         _check(load().aurora_hip_perceiver_out(_ptr(Vp), _ptr(w_pairs), w_pairs.shape[1], _ptr(P), _ptr(bias), _ptr(out),
-                                               out.stride(0), n_cols, Lq, Lk, heads, head_dim, N, _ptr(word), float(limit),
+                                               ldo, n_cols, Lq, Lk, heads, head_dim, N, _ptr(word), float(limit),
                                                _stream()))
     return out
 

@@ -147,11 +147,7 @@ def test_linear_layernorm_fused_equals_the_two_kernels(M, K, in_place):
         L.linear_layernorm(a, w[:256], b, gain, shift, x_in, x_in, None)   # only N = 512 rows fit one workgroup
 
 
-def _unsplit(t):
-    """fp16-pair layout -> (high halves, remainders) as fp32 tensors of the logical shape."""
-    M, K = t.shape
-    h16 = t.contiguous().view(torch.float16).view(M, K // 32, 2, 32)
-    return h16[:, :, 0].reshape(M, K).float(), h16[:, :, 1].reshape(M, K).float()
+from tests.perceiver_reference import unsplit as _unsplit  # noqa: E402  (fp16-pair layout -> high halves, remainders)
 
 
 def test_split_f16_layout_and_values():
