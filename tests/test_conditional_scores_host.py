@@ -17,8 +17,7 @@ import torch
 import aurora_amd
 from aurora_amd import Batch, FieldStats, Metadata, conditional_scores, scores
 from aurora_amd.conditional import ConditionalScores
-from tests.test_scores_host import cos_weights
-from tests.test_spectra_host import red_noise
+from tests.verification_inputs import cos_weights, red_noise, weights
 
 REL = 1e-9
 UNIT_EDGES = (-1.5, -0.5, 0.5, 1.5)                    # in units of the scale
@@ -98,10 +97,6 @@ def assert_rates_match(got_bias, got_rmse, got_mae, y: np.ndarray, what: str):
 
 
 # ---- inputs ------------------------------------------------------------------------------------------------------------
-def weights(n_lat):
-    return cos_weights(np.linspace(90, -90, n_lat)) if n_lat > 1 else np.ones(1)
-
-
 def planes(n_planes, n_lat, n_lon, seed):
     """(pred, truth, centre, scale), each (n_planes, n_lat, n_lon) float32.  Truth: red noise about 0 (amplitude 500);
     centre: a smooth map of amplitude 350; scale: a positive map about 200 that holds a few exact zeros; pred: truth + noise

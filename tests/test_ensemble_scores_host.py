@@ -18,7 +18,7 @@ import aurora_amd
 from aurora_amd import Batch, Metadata, ensemble_scores
 from aurora_amd.batch import BandBatch
 from aurora_amd.ensemble import EnsembleScores, _ensemble_sums_host
-from tests.test_scores_host import cos_weights, every, make_batch, shifted
+from tests.verification_inputs import cos_weights, every, randn_batch, shifted
 
 REL = 1e-9
 
@@ -71,10 +71,10 @@ def pressure_ensemble(M, n_planes, n_lat, n_lon, seed):
 
 
 def lagged(M, n_lat=17, n_lon=32, seed=0, B=2, dtype=torch.float32):
-    truth = make_batch(n_lat, n_lon, seed=seed, B=B, offset=280.0, scale=15.0, dtype=dtype)
+    truth = randn_batch(n_lat, n_lon, seed=seed, B=B, offset=280.0, scale=15.0, dtype=dtype)
     members = []
     for m in range(M):
-        err = make_batch(n_lat, n_lon, seed=seed + 1 + m, B=B, offset=0.3, scale=1.5, dtype=dtype)
+        err = randn_batch(n_lat, n_lon, seed=seed + 1 + m, B=B, offset=0.3, scale=1.5, dtype=dtype)
         members.append(Batch({k: v + err.surf_vars[k] for k, v in truth.surf_vars.items()}, truth.static_vars,
                              {k: v + err.atmos_vars[k] for k, v in truth.atmos_vars.items()}, truth.metadata))
     return members, truth
@@ -130,7 +130,7 @@ def test_public_names():
 def test_two_members_on_constant_differences(d1, d2):
     """M = 2: a = (|d1| + |d2|) / 2, g = |d1 - d2| / 2, crps = a - g / 2, fair CRPS = a - |d1 - d2| / 2,
     e = (d1 + d2) / 2, v = (d1 - d2)^2 / 2."""
-    truth = make_batch(17, 32, seed=1, offset=280.0, scale=10.0, dtype=torch.float64)
+    truth = randn_batch(17, 32, seed=1, offset=280.0, scale=10.0, dtype=torch.float64)
     s = ensemble_scores([shifted(truth, lambda v: v + d1), shifted(truth, lambda v: v + d2)], truth)
     assert isinstance(s, EnsembleScores) and s.members == 2
     assert s.crps["2t"].shape == (2,) and s.crps["z"].shape == (2, 3) and s.crps["z"].dtype == torch.float64
@@ -157,8 +157,8 @@ def test_two_members_on_constant_differences(d1, d2):
 
 @pytest.mark.parametrize("M", (2, 5))
 def test_equal_members_give_the_deterministic_scores(M):
-    truth = make_batch(17, 32, seed=2, offset=280.0, scale=10.0)
-    member = make_batch(17, 32, seed=3, offset=280.5, scale=10.0)
+    truth = randn_batch(17, 32, seed=2, offset=280.0, scale=10.0)
+    member = randn_batch(17, 32, seed=3, offset=280.5, scale=10.0)
     s = ensemble_scores([member] * M, truth)
     d = aurora_amd.scores(member, truth)
     np.testing.assert_allclose(every(s.crps), every(s.mae), rtol=1e-14)
@@ -265,7 +265,7 @@ def test_only_common_variables_and_the_last_history_entry_are_scored():
 
 
 def test_float64_fields_are_scored_on_the_host():
-    truth = make_batch(17, 32, seed=60, dtype=torch.float64, offset=1e5)
+    truth = randn_batch(17, 32, seed=60, dtype=torch.float64, offset=1e5)
     s = ensemble_scores([shifted(truth, lambda v: v + 1e-3), shifted(truth, lambda v: v + 3e-3)], truth)
     np.testing.assert_allclose(every(s.bias), 2e-3, rtol=1e-6)    # offsets an fp32 field could not hold at 1e5
     np.testing.assert_allclose(every(s.crps), 2e-3 - 0.5e-3, rtol=1e-6)

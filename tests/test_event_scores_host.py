@@ -20,7 +20,7 @@ from aurora_amd import Batch, Metadata, event_scores
 from aurora_amd.batch import BandBatch
 from aurora_amd.events import EventScores
 from aurora_amd.scores import latitude_weights
-from tests.test_spectra_host import make_batch, planes_of, red_noise
+from tests.verification_inputs import planes_of, quantile_thresholds, red_noise, red_noise_batch
 
 
 def yardstick_rowsums(p, t, thr, scales, below):
@@ -73,12 +73,6 @@ def brute_rowsums(p, t, th, n, below):
                         co += ev(t, i + di, (j + dj) % n_lon)
             out[i] += ((cf - co) ** 2, cf ** 2, co ** 2)
     return out
-
-
-def quantile_thresholds(x, extra=()):
-    """About the 0.5, 0.9 and 0.99 quantiles of the finite values, as float32, plus `extra`."""
-    v = np.asarray(x, dtype=np.float64)
-    return np.concatenate([np.quantile(v[np.isfinite(v)], [0.5, 0.9, 0.99]), np.asarray(extra, dtype=np.float64)]).astype(np.float32)
 
 
 def test_public_names():
@@ -141,7 +135,7 @@ def assert_equals_yardstick(s: EventScores, pred, truth, thresholds, below=False
 @pytest.mark.parametrize("n_lat,n_lon,scales", [(17, 32, (1, 3, 5)), (9, 45, (45, 3)), (3, 64, (9, 63, 1))])
 @pytest.mark.parametrize("below", (False, True))
 def test_cpu_event_scores_equal_the_yardstick(n_lat, n_lon, scales, below):
-    pred, truth = make_batch(n_lat, n_lon, seed=1), make_batch(n_lat, n_lon, seed=2)
+    pred, truth = red_noise_batch(n_lat, n_lon, seed=1), red_noise_batch(n_lat, n_lon, seed=2)
     pred.surf_vars["2t"][0, -1, 1, 0] = float("nan")
     truth.atmos_vars["z"][1, -1, 2, n_lat - 1, n_lon - 1] = float("inf")
     thr = thresholds_for(pred, truth)
@@ -181,7 +175,7 @@ def test_cpu_event_scores_equal_the_yardstick(n_lat, n_lon, scales, below):
 
 def test_identities():
     n_lat, n_lon = 17, 32
-    pred, truth = make_batch(n_lat, n_lon, seed=3), make_batch(n_lat, n_lon, seed=4)
+    pred, truth = red_noise_batch(n_lat, n_lon, seed=3), red_noise_batch(n_lat, n_lon, seed=4)
     x = truth.surf_vars["2t"][:, -1].numpy()
     hi, lo = np.float32(x.max() + 1000), np.float32(min(x.min(), pred.surf_vars["2t"].min().item()) - 1000)
     thr = {"2t": [*quantile_thresholds(x)[:2], hi, lo]}
@@ -218,7 +212,7 @@ def test_identities():
 
 
 def test_argument_errors():
-    truth, pred = make_batch(17, 32, seed=10), make_batch(17, 32, seed=11)
+    truth, pred = red_noise_batch(17, 32, seed=10), red_noise_batch(17, 32, seed=11)
     md = truth.metadata
     thr = {"2t": [5e4]}
     for bad, word in (((1, 4), "odd"), ((65,), "63"), ((33,), "32 longitudes"), ((3, 3), "distinct"), ((2.5,), "whole"),
@@ -244,7 +238,7 @@ def test_argument_errors():
     with pytest.raises(ValueError, match=r"lat.*truth\.crop\(model\.patch_size\)"):
         event_scores(pred.crop(4), truth, thr)
     with pytest.raises(ValueError, match="lon"):
-        event_scores(pred, make_batch(17, 16, seed=10), thr)
+        event_scores(pred, red_noise_batch(17, 16, seed=10), thr)
     lat2, lon2 = md.lat[:, None].expand(17, 32), md.lon[None, :].expand(17, 32)
     with pytest.raises(ValueError, match="matrices"):
         event_scores(Batch(pred.surf_vars, {}, pred.atmos_vars, Metadata(lat=lat2, lon=lon2, time=md.time, atmos_levels=md.atmos_levels)),

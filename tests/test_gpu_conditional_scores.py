@@ -18,20 +18,12 @@ from aurora_amd.engine import lib
 from tests import helpers
 from tests.golden_cases import CASES
 from tests.test_conditional_scores_host import (GRIDS, REL, UNIT_EDGES, assert_not_trivial, assert_sums_match,
-                                                check_against_yardstick, make_batches, planes, weights,
-                                                yardstick_sums)
+                                                check_against_yardstick, make_batches, planes, yardstick_sums)
+from tests.verification_inputs import DEV, carve, weights
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 EIGHT = (-2.0, -1.5, -1.0, -0.5, 0.5, 1.0, 1.5, 2.0)
 NAN = float("nan")
-
-
-def to_dev(a: np.ndarray, offset_floats=0) -> torch.Tensor:
-    """The planes of `a` on the device, carved out of a flat buffer `offset_floats` past its (256-byte aligned) start."""
-    flat = torch.zeros(offset_floats + a.size, dtype=torch.float32)
-    flat[offset_floats:] = torch.from_numpy(a).reshape(-1)
-    return flat.to(DEV)[offset_floats:].view(*a.shape)
 
 
 def edge_tables(n_planes, unit):
@@ -82,7 +74,7 @@ def check_tables(host, dev, n_lat, maps, what):
 def test_raw_table_equals_the_yardstick(n_planes, n_lat, n_lon, maps):
     host = grid_inputs(n_planes, n_lat, n_lon)
     offset = 3 if (n_lat, n_lon) == (33, 90) else 0                              # planes 3 floats past a 16-byte boundary
-    dev = [to_dev(a, offset) for a in host]
+    dev = [carve(a, offset) for a in host]
     if offset:
         assert all(x[k].data_ptr() % 16 != 0 for x in dev for k in range(n_planes))
     elif n_lon % 4 == 0:
@@ -92,7 +84,7 @@ def test_raw_table_equals_the_yardstick(n_planes, n_lat, n_lon, maps):
 
 def small(seed=7, n_planes=3, n_lat=33, n_lon=64, offset=0):
     host = planes(n_planes, n_lat, n_lon, seed)
-    return host, [to_dev(a, offset) for a in host], torch.from_numpy(weights(n_lat)).to(DEV)
+    return host, [carve(a, offset) for a in host], torch.from_numpy(weights(n_lat)).to(DEV)
 
 
 def test_two_calls_agree_and_a_plane_alone_equals_it_among_three():
@@ -166,7 +158,7 @@ def test_invalid_points():
     host = [a.copy() for a in planes(4, n_lat, n_lon, seed=31)]
     w = weights(n_lat)
     assert_not_trivial(*host, w)
-    clean = [to_dev(a) for a in host]
+    clean = [carve(a) for a in host]
     w_dev = torch.from_numpy(w).to(DEV)
     edges = np.array([UNIT_EDGES] * 4)
     before = call(*clean, edges, "truth", w_dev)
@@ -175,7 +167,7 @@ def test_invalid_points():
     c[0, 9, 0], c[0, 9, -1], s[0, 11, 0], s[0, 11, -1], s[0, 13, 20] = np.nan, np.inf, np.inf, np.nan, -1.0
     t[1, 10:19] = np.nan                                                         # rows of all four waves, two turns
     p[2] = np.nan
-    dev = [to_dev(a) for a in host]
+    dev = [carve(a) for a in host]
     got = call(*dev, edges, "truth", w_dev)
     counts = got[:, :, 0].sum(dim=1).tolist()
     assert counts == [n_lat * n_lon - 9, n_lat * n_lon - 9 * n_lon, 0, n_lat * n_lon]

@@ -20,20 +20,12 @@ from tests import helpers
 from tests.golden_cases import CASES
 from tests.test_diagnostics_host import (ALL, GRIDS, U, assert_bit_equal, assert_within, check_batch, gamma, longitude_factor,
                                          make_batch, yardstick_columns, yardstick_wind)
+from tests.verification_inputs import DEV, carve
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 SHAPES = [(2, 2), (3, 5), (17, 32), (33, 130), (64, 1030)]
 WIND_OUTPUTS = [("vo", "div", "ws"), ("vo",), ("div", "ws"), ("ws",), ("vo", "div")]
 COLUMN_OUTPUTS = [("tcwv", "ivtu", "ivtv", "ivt"), ("tcwv",), ("ivt",), ("ivtu", "ivtv"), ("tcwv", "ivtv")]
-
-
-def carve(values: torch.Tensor, offset_floats: int, fill: float = 0.0) -> torch.Tensor:
-    """A device copy of `values` (..., n_lat, n_lon) as fp32, carved out of a flat buffer `offset_floats` past its start (the
-    planes of an odd-sized grid follow each other unpadded), as tests/test_gpu_field_stats.py:carve does."""
-    flat = torch.full((offset_floats + values.numel(),), fill, dtype=torch.float32)
-    flat[offset_floats:] = values.float().reshape(-1)
-    return flat.to(DEV)[offset_floats:].view(values.shape)
 
 
 def grid(n_lat, n_lon, wrap):

@@ -24,7 +24,6 @@ spread through the square root: u = S3 / S1 is known to du = 2 REL q_bar (u <= q
 (`assert_ensemble_sums_match` and `assert_finalised_match` of tests/test_ensemble_scores_host.py hold these.)"""
 from datetime import datetime
 
-import numpy as np
 import pytest
 import torch
 
@@ -35,29 +34,16 @@ from tests import helpers
 from tests.golden_cases import CASES
 from tests.test_ensemble_scores_host import (REL, assert_batch_matches_yardstick, assert_ensemble_sums_match, lagged,
                                              pressure_ensemble, yardstick_ensemble)
-from tests.test_scores_host import cos_weights
+from tests.verification_inputs import DEV, carve, weights
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-
-
-def on_device(x, offset_floats=0):
-    """A (..., n_lat, n_lon) host tensor on the device, carved out of a flat buffer `offset_floats` past its start (so that,
-    with 1, no plane pointer is 16-byte aligned where the planes are whole multiples of 16 bytes)."""
-    flat = torch.zeros(offset_floats + x.numel(), dtype=torch.float32)
-    flat[offset_floats:] = x.reshape(-1)
-    return flat.to(DEV)[offset_floats:].view(x.shape)
-
-
-def weights(n_lat):
-    return cos_weights(np.linspace(90, -90, n_lat)) if n_lat > 1 else np.ones(1)
 
 
 def check_raw(x, t, what, offset=0):
     """x (M, n_planes, n_lat, n_lon), t (n_planes, n_lat, n_lon) on the host: one call, every plane against the yardstick."""
     M, n_planes, n_lat, _ = x.shape
     w = weights(n_lat)
-    xd, td = [on_device(x[m], offset) for m in range(M)], on_device(t, offset)
+    xd, td = [carve(x[m], offset) for m in range(M)], carve(t, offset)
     if offset and x.shape[-1] % 4 == 0:
         assert td.data_ptr() % 16 != 0
     sums, hist = lib.ensemble_scores_sums([[v] for v in xd], [td], torch.from_numpy(w).to(DEV))
@@ -102,12 +88,12 @@ def test_alignment_does_not_change_a_single_bit():
     w = torch.from_numpy(weights(33)).to(DEV)
     for M in (3, 8, 13, 40):
         x, t = pressure_ensemble(M, 3, 33, 64, seed=5 + M)
-        a = lib.ensemble_scores_sums([[on_device(x[m])] for m in range(M)], [on_device(t)], w)
-        xb, tb = [on_device(x[m], 1) for m in range(M)], on_device(t, 1)
+        a = lib.ensemble_scores_sums([[carve(x[m])] for m in range(M)], [carve(t)], w)
+        xb, tb = [carve(x[m], 1) for m in range(M)], carve(t, 1)
         assert tb.data_ptr() % 16 == 4
         b = lib.ensemble_scores_sums([[v] for v in xb], [tb], w)
         # one member unaligned is enough to leave the 16-byte path
-        c = lib.ensemble_scores_sums([[on_device(x[m], int(m == M - 1))] for m in range(M)], [on_device(t)], w)
+        c = lib.ensemble_scores_sums([[carve(x[m], int(m == M - 1))] for m in range(M)], [carve(t)], w)
         for other in (b, c):
             assert torch.equal(a[0], other[0]) and torch.equal(a[1], other[1]), M
 
@@ -204,7 +190,7 @@ def test_member_order_changes_only_what_is_added_in_member_order():
     M = 17
     x, t = pressure_ensemble(M, 3, 33, 61, seed=60)
     w = torch.from_numpy(weights(33)).to(DEV)
-    xd, td = [on_device(x[m]) for m in range(M)], on_device(t)
+    xd, td = [carve(x[m]) for m in range(M)], carve(t)
     a = lib.ensemble_scores_sums([[v] for v in xd], [td], w)
     perm = torch.randperm(M, generator=torch.Generator().manual_seed(1)).tolist()
     b = lib.ensemble_scores_sums([[xd[m]] for m in perm], [td], w)
@@ -245,7 +231,7 @@ def test_scores_are_capturable_in_a_hip_graph():
 def test_a_cold_call_during_capture_is_refused(monkeypatch):
     x, t = pressure_ensemble(2, 1, 17, 32, seed=80)
     w = torch.from_numpy(weights(17)).to(DEV)
-    xd, td = [on_device(x[m]).clone() for m in range(2)], on_device(t).clone()     # addresses no call has seen
+    xd, td = [carve(x[m]).clone() for m in range(2)], carve(t).clone()     # addresses no call has seen
     monkeypatch.setattr(torch.cuda, "is_current_stream_capturing", lambda: True)
     with pytest.raises(RuntimeError, match="before capturing"):
         lib.ensemble_scores_sums([[v] for v in xd], [td], w)

@@ -28,37 +28,17 @@ from aurora_amd import Batch, Metadata, event_scores, rollout
 from aurora_amd.engine import lib
 from tests import helpers
 from tests.golden_cases import CASES
-from tests.test_event_scores_host import assert_equals_yardstick, quantile_thresholds, thresholds_for, yardstick_rowsums
-from tests.test_spectra_host import make_batch, red_noise
+from tests.test_event_scores_host import assert_equals_yardstick, thresholds_for, yardstick_rowsums
+from tests.verification_inputs import DEV, carve, quantile_thresholds, red_noise, red_noise_batch, thresholds_of
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
-
-
-def to_dev(a: np.ndarray, offset_floats=0):
-    flat = torch.zeros(offset_floats + a.size, dtype=torch.float32)
-    flat[offset_floats:] = torch.from_numpy(a.reshape(-1))
-    return flat.to(DEV)[offset_floats:].view(*a.shape)
-
-
-def thresholds_of(t: np.ndarray, T: int) -> np.ndarray:
-    """(n_planes, T) float32 from each truth plane: T = 5: three quantiles, above the maximum, NaN; T = 4: quantiles and NaN;
-    T = 8: the five, then three more quantiles."""
-    rows = []
-    for x in t:
-        v = x[np.isfinite(x)] if np.isfinite(x).any() else np.zeros(1, dtype=np.float32)
-        q = quantile_thresholds(v)
-        five = [*q, np.float32(v.max() + 1000), np.float32("nan")]
-        rows.append({4: [*q, np.float32("nan")], 5: five,
-                     8: five + list(np.quantile(v.astype(np.float64), [0.1, 0.75, 0.999]).astype(np.float32))}[T])
-    return np.asarray(rows, dtype=np.float32)
 
 
 def check_raw(p, t, thr, scales, what, below=False, offset_floats=0, planes=None):
     """(n_planes, n_lat, n_lon) host arrays through lib.event_rowsums; the planes in `planes` (default: all) against the
     yardstick, exactly."""
     n_planes, n_lat, n_lon = p.shape
-    pd, td = to_dev(p, offset_floats), to_dev(t, offset_floats)
+    pd, td = carve(p, offset_floats), carve(t, offset_floats)
     rowsums, valid = lib.event_rowsums([pd], [td], torch.from_numpy(thr).to(DEV), scales, below)
     assert rowsums.shape == (n_planes, thr.shape[1], len(scales), n_lat, 3) and rowsums.dtype == torch.int64
     assert valid.shape == (n_planes, n_lat) and valid.dtype == torch.int64 and rowsums.device == DEV
@@ -123,7 +103,7 @@ def test_invalid_points_as_on_the_host():
     assert not again[3].any() and not valid[3].any() and np.array_equal(again[:3], got[:3])
     md = Metadata(lat=torch.linspace(90, -90, n_lat, dtype=torch.float64), lon=torch.linspace(0, 360, n_lon + 1, dtype=torch.float64)[:-1],
                   time=(datetime(2023, 1, 1, 6),), atmos_levels=())
-    b = lambda a: Batch({"2t": to_dev(a[3][None, None])}, {}, {}, md)  # noqa: E731
+    b = lambda a: Batch({"2t": carve(a[3][None, None])}, {}, {}, md)  # noqa: E731
     s = event_scores(b(p), b(t), {"2t": thr[3, :3]}, scales=scales).cpu()
     assert torch.isnan(s.fss["2t"]).all() and (s.count["2t"] == 0).all() and (s.hits["2t"] == 0).all()
 
@@ -140,7 +120,7 @@ def test_event_scores_of_a_batch_equal_the_cpu_path(n_lat, n_lon, scales, below)
     """Surface and atmospheric variables through event_scores() on device batches (history slices passed as views) against the
     same call on the host batches and against the yardstick.  Every table is equal; so is every float64 score, because the
     finalisation adds the rows in a fixed tree of elementwise operations on either device."""
-    pred, truth = make_batch(n_lat, n_lon, seed=3), make_batch(n_lat, n_lon, seed=4)
+    pred, truth = red_noise_batch(n_lat, n_lon, seed=3), red_noise_batch(n_lat, n_lon, seed=4)
     pred.surf_vars["2t"][1, -1, n_lat // 2, 0] = float("nan")
     thr = thresholds_for(pred, truth)
     host = event_scores(pred, truth, thr, scales=scales, below=below)
@@ -157,8 +137,8 @@ def test_repeatable_independent_of_the_other_planes_and_of_alignment():
     p, t = red_noise((7, n_lat, n_lon), seed=5), red_noise((7, n_lat, n_lon), seed=6)
     p[2, 5, 100] = np.nan
     thr = torch.from_numpy(thresholds_of(t, 4)).to(DEV)
-    pd, td = to_dev(p), to_dev(t)
-    po, to = to_dev(p, 1), to_dev(t, 1)                                # the same values one float (4 bytes) further on
+    pd, td = carve(p), carve(t)
+    po, to = carve(p, 1), carve(t, 1)                                # the same values one float (4 bytes) further on
     assert pd.data_ptr() % 16 == 0 and po.data_ptr() % 16 == 4
     whole, again = lib.event_rowsums([pd], [td], thr, scales), lib.event_rowsums([pd], [td], thr, scales)
     single = [lib.event_rowsums([pd[k:k + 1]], [td[k:k + 1]], thr[k:k + 1].contiguous(), scales) for k in range(7)]
@@ -174,8 +154,8 @@ def test_repeatable_independent_of_the_other_planes_and_of_alignment():
 
 
 def test_event_scores_are_capturable_in_a_hip_graph():
-    pred, truth = (b.to(DEV) for b in (make_batch(33, 64, seed=7), make_batch(33, 64, seed=8)))
-    other = make_batch(33, 64, seed=9).to(DEV)
+    pred, truth = (b.to(DEV) for b in (red_noise_batch(33, 64, seed=7), red_noise_batch(33, 64, seed=8)))
+    other = red_noise_batch(33, 64, seed=9).to(DEV)
     thr = {"2t": [5e4, 5e4 + 50], "z": [5e4 - 20]}
     first = event_scores(pred, truth, thr, scales=(1, 5)).cpu()        # (the warm call: tables and weights are uploaded)
     torch.cuda.synchronize()
@@ -203,7 +183,7 @@ def test_the_call_needs_no_workspace():
     p, t = red_noise((n, n_lat, n_lon), seed=10), red_noise((n, n_lat, n_lon), seed=11)
     thr = thresholds_of(t, 5)
     assert lib.event_scores_workspace_bytes(n, n_lat, n_lon, 5, 3) == 0 and lib.event_scores_workspace_bytes(69, 721, 1440, 8, 8) == 0
-    pd, td, thr_d = to_dev(p), to_dev(t), torch.from_numpy(thr).to(DEV)
+    pd, td, thr_d = carve(p), carve(t), torch.from_numpy(thr).to(DEV)
     want = lib.event_rowsums([pd], [td], thr_d, scales)
     n_rs, n_v, guard = n * 5 * 3 * n_lat * 3, n * n_lat, 1 << 13
     buf = torch.full(((n_rs + n_v + 2 * guard) * 8,), 0xA5, dtype=torch.uint8, device=DEV)
@@ -248,7 +228,7 @@ def test_a_rollout_is_scored_step_by_step_and_read_once():
 
 
 def test_device_path_argument_errors():
-    pred, truth = make_batch(17, 32, seed=12), make_batch(17, 32, seed=13)
+    pred, truth = red_noise_batch(17, 32, seed=12), red_noise_batch(17, 32, seed=13)
     thr = {"2t": [5e4]}
     with pytest.raises(ValueError, match="cpu.*cuda|cuda.*cpu"):
         event_scores(pred.to(DEV), truth, thr)

@@ -25,18 +25,10 @@ from aurora_amd.engine import lib
 from tests import helpers
 from tests.golden_cases import CASES
 from tests.test_field_stats_host import U, assert_state_matches, make_batch, variable_state, yardstick
+from tests.verification_inputs import DEV, carve
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 INT = ("n", "argmin", "argmax", "exceed", "run", "longest")
-
-
-def carve(values: torch.Tensor, offset_floats: int) -> torch.Tensor:
-    """A device copy of fp64 `values` (..., n_lat, n_lon) as fp32, carved out of a flat buffer `offset_floats` past its start
-    (the planes of an odd-sized grid follow each other unpadded), as tests/test_gpu_scores.py:fields does."""
-    flat = torch.zeros(offset_floats + values.numel(), dtype=torch.float32)
-    flat[offset_floats:] = values.float().reshape(-1)
-    return flat.to(DEV)[offset_floats:].view(values.shape)
 
 
 def samples(S, n_planes, n_lat, n_lon, seed, offset=0, scale=300.0):

@@ -7,7 +7,7 @@ exact inputs and every floating-point sum in it is a fixed tree of elementwise o
 does not depend on a device's reduction order.
 
 Inputs are those of the host file: truth y = `red_noise`, members x_m = fp32(y + red noise of amplitude 250); thresholds are
-`thresholds_of` of tests/test_gpu_event_scores.py (T = 5: the data's 0.5 / 0.9 / 0.99 quantiles, one above the maximum, one NaN:
+`thresholds_of` of tests/verification_inputs.py (T = 5: the data's 0.5 / 0.9 / 0.99 quantiles, one above the maximum, one NaN:
 the kernel's two-register counter; T = 4: the quantiles and the NaN: its one-register counter; T = 8).  Every table test
 asserts `assert_not_trivial` on its own input.
 
@@ -25,14 +25,11 @@ from aurora_amd import Batch, Metadata, probability_scores, rollout
 from aurora_amd.engine import lib
 from tests import helpers
 from tests.golden_cases import CASES
-from tests.test_event_scores_host import quantile_thresholds
-from tests.test_gpu_event_scores import thresholds_of, to_dev
 from tests.test_probability_scores_host import (assert_equals_yardstick, assert_not_trivial, assert_same_scores, make_ensemble,
                                                 perturbed, thresholds_for, yardstick_rows)
-from tests.test_spectra_host import red_noise
+from tests.verification_inputs import DEV, carve, quantile_thresholds, red_noise, thresholds_of
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 
 
 def fields(n_planes, n_lat, n_lon, M, seed=None):
@@ -47,7 +44,7 @@ def fields(n_planes, n_lat, n_lon, M, seed=None):
 
 def run(x, y, thr, below=False, offset_floats=0):
     """Host arrays through lib.probability_rows: the (n_planes, n_lat, T, 2, M + 1) table as numpy, and the device inputs."""
-    xd, yd = to_dev(x, offset_floats), to_dev(y, offset_floats)
+    xd, yd = carve(x, offset_floats), carve(y, offset_floats)
     rows = lib.probability_rows([[xd[m]] for m in range(x.shape[0])], [yd], torch.from_numpy(thr).to(DEV), below)
     assert rows.shape == (*y.shape[:2], thr.shape[1], 2, x.shape[0] + 1) and rows.dtype == torch.int32 and rows.device == DEV
     return rows.cpu().numpy(), xd, yd
@@ -136,7 +133,7 @@ def test_invalid_points_as_on_the_host():
     assert not again[3].any() and np.array_equal(again[:3], got[:3])
     md = Metadata(lat=torch.linspace(90, -90, n_lat, dtype=torch.float64), lon=torch.linspace(0, 360, n_lon + 1, dtype=torch.float64)[:-1],
                   time=(datetime(2023, 1, 1, 6),), atmos_levels=())
-    b = lambda a: Batch({"2t": to_dev(a[3][None, None])}, {}, {}, md)  # noqa: E731
+    b = lambda a: Batch({"2t": carve(a[3][None, None])}, {}, {}, md)  # noqa: E731
     s = probability_scores([b(x[m]) for m in range(M)], b(y), {"2t": thr[3, :3]}).cpu()
     assert torch.isnan(s.brier["2t"]).all() and torch.isnan(s.roc_area["2t"]).all() and torch.isnan(s.hit_rate["2t"]).all()
     assert (s.count["2t"] == 0).all() and (s.counts["2t"] == 0).all()
@@ -148,7 +145,7 @@ def test_repeatable_independent_of_the_other_planes_and_of_the_member_order():
     x[3, 1, 5, 100] = np.nan
     thr = thresholds_of(y, 4)
     thr_d = torch.from_numpy(thr).to(DEV)
-    xd, yd = to_dev(x), to_dev(y)
+    xd, yd = carve(x), carve(y)
     members = [[xd[m]] for m in range(M)]
     whole, again = lib.probability_rows(members, [yd], thr_d), lib.probability_rows(members, [yd], thr_d)
     single = [lib.probability_rows([[v[0][k:k + 1]] for v in members], [yd[k:k + 1]], thr_d[k:k + 1].contiguous()) for k in range(3)]

@@ -24,30 +24,20 @@ from aurora_amd.engine import lib
 from aurora_amd.scores import latitude_weights
 from tests import helpers
 from tests.golden_cases import CASES
-from tests.test_scores_host import cos_weights, make_batch, yardstick_sums
+from tests.test_scores_host import yardstick_sums
+from tests.verification_inputs import DEV, carve, cos_weights, randn_batch, weights
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 REL = 1e-9
 
 
 def fields(n_planes, n_lat, n_lon, seed, offset_floats=0):
-    """Seeded pressure-like data, d small against p: p = 101325 + 300 randn, t = p + 2 randn + 0.5, c = 101325 + 100 randn.
-    With `offset_floats` every plane is carved out of a flat buffer that many floats past its start (and the planes of
-    an odd-sized grid follow each other unpadded), so the plane pointers are not 16-byte aligned."""
+    """Seeded pressure-like data, d small against p: p = 101325 + 300 randn, t = p + 2 randn + 0.5, c = 101325 + 100 randn,
+    each carved `offset_floats` past the start of its buffer."""
     g = torch.Generator().manual_seed(seed)
     r = lambda: torch.randn(n_planes, n_lat, n_lon, generator=g, dtype=torch.float64)  # noqa: E731
     p = 101325 + 300 * r()
-    out = []
-    for v in (p, p + 2 * r() + 0.5, 101325 + 100 * r()):
-        flat = torch.zeros(offset_floats + v.numel(), dtype=torch.float32)
-        flat[offset_floats:] = v.float().reshape(-1)
-        out.append(flat.to(DEV)[offset_floats:].view(n_planes, n_lat, n_lon))
-    return out
-
-
-def weights(n_lat):
-    return cos_weights(np.linspace(90, -90, n_lat)) if n_lat > 1 else np.ones(1)
+    return [carve(v, offset_floats) for v in (p, p + 2 * r() + 0.5, 101325 + 100 * r())]
 
 
 def assert_sums_match(got: np.ndarray, want: np.ndarray, what: str):
@@ -127,9 +117,9 @@ def test_nan_land_mask_and_stray_nans_count_exactly():
 
 
 def batches(n_lat, n_lon, seed, B=2, levels=(100, 500, 850)):
-    truth = make_batch(n_lat, n_lon, seed=seed, B=B, offset=280.0, scale=15.0, levels=levels)
-    err = make_batch(n_lat, n_lon, seed=seed + 1, B=B, offset=0.3, scale=1.5, levels=levels)
-    clim = make_batch(n_lat, n_lon, seed=seed + 2, B=B, offset=280.0, scale=5.0, levels=levels)
+    truth = randn_batch(n_lat, n_lon, seed=seed, B=B, offset=280.0, scale=15.0, levels=levels)
+    err = randn_batch(n_lat, n_lon, seed=seed + 1, B=B, offset=0.3, scale=1.5, levels=levels)
+    clim = randn_batch(n_lat, n_lon, seed=seed + 2, B=B, offset=280.0, scale=5.0, levels=levels)
     pred = Batch({k: v + err.surf_vars[k] for k, v in truth.surf_vars.items()}, truth.static_vars,
                  {k: v + err.atmos_vars[k] for k, v in truth.atmos_vars.items()}, truth.metadata)
     return pred, truth, clim

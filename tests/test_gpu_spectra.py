@@ -28,10 +28,10 @@ from aurora_amd.engine import lib
 from aurora_amd.spectra import band_weights
 from tests import helpers
 from tests.golden_cases import CASES
-from tests.test_spectra_host import make_batch, planes_of, red_noise, spectra_bound, yardstick_spectra
+from tests.test_spectra_host import spectra_bound, yardstick_spectra
+from tests.verification_inputs import DEV, carve, planes_of, red_noise, red_noise_batch
 
 pytestmark = pytest.mark.gpu
-DEV = torch.device("cuda:0")
 
 
 def lats(n_lat):
@@ -42,19 +42,13 @@ def bands_for(n):
     return (((-90, 90), (-30, 30), (20, 90), (-90, -60), (1.0, 1.5), (0, 0), (45, 90), (-10, 80)))[:n]
 
 
-def to_dev(a: np.ndarray, offset_floats=0):
-    flat = torch.zeros(offset_floats + a.size, dtype=torch.float32)
-    flat[offset_floats:] = torch.from_numpy(a.reshape(-1))
-    return flat.to(DEV)[offset_floats:].view(*a.shape)
-
-
 def check_raw(p: np.ndarray, t, n_bands, what, offset_floats=0):
     """(n_planes, n_lat, N) host arrays through lib.spectra_power against the yardstick under the bound."""
     n_planes, n_lat, N = p.shape
     lat, bands = lats(n_lat), bands_for(n_bands)
     bw = torch.from_numpy(band_weights(lat, bands)).to(DEV)
-    pd = to_dev(p, offset_floats)
-    td = None if t is None else to_dev(t, offset_floats)
+    pd = carve(p, offset_floats)
+    td = None if t is None else carve(t, offset_floats)
     power, rows = lib.spectra_power([pd], None if td is None else [td], bw)
     assert power.shape == (n_planes, 1 if t is None else 3, n_bands, N // 2 + 1) and power.dtype == torch.float64
     assert rows.shape == (n_planes, n_bands) and rows.dtype == torch.int64 and power.device == DEV
@@ -116,7 +110,7 @@ def test_invalid_rows_as_on_the_host():
 @pytest.mark.parametrize("n_lat,n_lon", [(17, 32), (33, 45)])
 def test_spectra_of_a_batch_equal_the_yardstick(n_lat, n_lon):
     """Surface and atmospheric variables through spectra() on a Batch; the history slice [:, -1] is passed as a view."""
-    pred, truth = make_batch(n_lat, n_lon, seed=3), make_batch(n_lat, n_lon, seed=4)
+    pred, truth = red_noise_batch(n_lat, n_lon, seed=3), red_noise_batch(n_lat, n_lon, seed=4)
     bands = bands_for(3)
     lat = lats(n_lat)
     for tr in (None, truth):
@@ -141,8 +135,8 @@ def test_repeatable_independent_of_the_other_planes_and_of_alignment():
     p, t = red_noise((7, n_lat, N), seed=5), red_noise((7, n_lat, N), seed=6)
     p[2, 5, 100] = np.nan
     bw = torch.from_numpy(band_weights(lats(n_lat), bands_for(3))).to(DEV)
-    pd, td = to_dev(p), to_dev(t)
-    po, to = to_dev(p, 1), to_dev(t, 1)                                # the same values one float (4 bytes) further on
+    pd, td = carve(p), carve(t)
+    po, to = carve(p, 1), carve(t, 1)                                # the same values one float (4 bytes) further on
     assert pd.data_ptr() % 16 == 0 and po.data_ptr() % 16 == 4
     for truth, truth_off in ((None, None), (td, to)):
         args = lambda sl=slice(None): ([pd[sl]], None if truth is None else [truth[sl]], bw)  # noqa: E731
@@ -160,8 +154,8 @@ def test_repeatable_independent_of_the_other_planes_and_of_alignment():
 
 
 def test_spectra_are_capturable_in_a_hip_graph():
-    pred, truth = (b.to(DEV) for b in (make_batch(33, 64, seed=7), make_batch(33, 64, seed=8)))
-    other = make_batch(33, 64, seed=9).to(DEV)
+    pred, truth = (b.to(DEV) for b in (red_noise_batch(33, 64, seed=7), red_noise_batch(33, 64, seed=8)))
+    other = red_noise_batch(33, 64, seed=9).to(DEV)
     bands = bands_for(2)
     first = spectra(pred, truth, bands=bands).cpu()                    # (the warm call: tables and weights are uploaded)
     torch.cuda.synchronize()
@@ -185,7 +179,7 @@ def test_spectra_are_capturable_in_a_hip_graph():
 def test_the_workspace_is_as_large_as_what_the_call_touches(with_truth):
     """The C call with exactly aurora_hip_spectra_workspace_bytes, inside a larger buffer whose remainder is a guard."""
     n, n_lat, N, nb = 3, 45, 90, 3
-    p, t = to_dev(red_noise((n, n_lat, N), seed=10)), to_dev(red_noise((n, n_lat, N), seed=11))
+    p, t = carve(red_noise((n, n_lat, N), seed=10)), carve(red_noise((n, n_lat, N), seed=11))
     bw = torch.from_numpy(band_weights(lats(n_lat), bands_for(nb))).to(DEV)
     want = lib.spectra_power([p], [t] if with_truth else None, bw)
     need = lib.spectra_workspace_bytes(n, n_lat, N, nb, with_truth)
@@ -240,7 +234,7 @@ def test_a_rollout_is_tracked_step_by_step_and_read_once():
 
 
 def test_device_path_argument_errors():
-    pred, truth = make_batch(17, 32, seed=12), make_batch(17, 32, seed=13)
+    pred, truth = red_noise_batch(17, 32, seed=12), red_noise_batch(17, 32, seed=13)
     with pytest.raises(ValueError, match="cpu.*cuda|cuda.*cpu"):
         spectra(pred.to(DEV), truth)
     with pytest.raises(TypeError, match="float64"):

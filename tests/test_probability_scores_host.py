@@ -21,8 +21,7 @@ from aurora_amd import Batch, Metadata, ensemble_scores, event_scores, probabili
 from aurora_amd.batch import BandBatch
 from aurora_amd.probability import ProbabilityScores
 from aurora_amd.scores import latitude_weights
-from tests.test_event_scores_host import quantile_thresholds
-from tests.test_spectra_host import make_batch, planes_of, red_noise
+from tests.verification_inputs import planes_of, quantile_thresholds, red_noise, red_noise_batch
 
 
 def yardstick_rows(x, y, thr, below):
@@ -62,7 +61,7 @@ def perturbed(y: np.ndarray, m: int, salt: int = 0) -> np.ndarray:
 
 def make_ensemble(n_lat, n_lon, M, seed=0, B=2):
     """(M member batches, truth) in the form of `make_batch`."""
-    truth = make_batch(n_lat, n_lon, seed=seed, B=B)
+    truth = red_noise_batch(n_lat, n_lon, seed=seed, B=B)
     members = []
     for m in range(M):
         f = lambda d, s: {k: torch.from_numpy(perturbed(v.numpy(), m, 100 * (s + i))) for i, (k, v) in enumerate(d.items())}  # noqa: E731
@@ -286,7 +285,7 @@ def test_one_batch_of_members_equals_the_sequence_form():
     assert a.brier["z"].shape == (1, 3, 4) and a.members == 4
     assert_same_scores(a, b)
     with pytest.raises(ValueError, match="probability_scores: members is ONE Batch.*batch size 1"):
-        probability_scores(one, make_batch(17, 32, seed=7, B=2), thr)
+        probability_scores(one, red_noise_batch(17, 32, seed=7, B=2), thr)
     with pytest.raises(ValueError, match="probability_scores: members is ONE Batch.*2 to 64"):
         probability_scores(truth, truth, thr)
 
@@ -324,9 +323,9 @@ def test_argument_errors():
     with pytest.raises(ValueError, match=r"probability_scores: members\[0\] and truth differ in lat"):
         probability_scores([b.crop(4) for b in members], truth, thr)
     with pytest.raises(ValueError, match=r"probability_scores: members\[0\] and truth differ in lon"):
-        probability_scores(members, make_batch(17, 16, seed=8), thr)
+        probability_scores(members, red_noise_batch(17, 16, seed=8), thr)
     with pytest.raises(ValueError, match=r"probability_scores: members\[0\] and truth differ in batch size"):
-        probability_scores(members, make_batch(17, 32, seed=8, B=3), thr)
+        probability_scores(members, red_noise_batch(17, 32, seed=8, B=3), thr)
     lat2, lon2 = md.lat[:, None].expand(17, 32), md.lon[None, :].expand(17, 32)
     matrices = Batch(truth.surf_vars, {}, truth.atmos_vars, Metadata(lat=lat2, lon=lon2, time=md.time, atmos_levels=md.atmos_levels))
     with pytest.raises(ValueError, match="probability_scores: .*matrices"):

@@ -5,7 +5,6 @@ The yardstick `yardstick_sums` is the table of include/aurora_hip.h written out 
 `aurora_amd.scores._sums_host` (which is code under test); tests/test_gpu_scores.py compares the kernel with the same
 function."""
 import ctypes
-from datetime import datetime
 
 import numpy as np
 import pytest
@@ -15,15 +14,9 @@ import aurora_amd
 from aurora_amd import Batch, Metadata, scores
 from aurora_amd.batch import BandBatch
 from aurora_amd.scores import Scores, _sums_host, latitude_weights
+from tests.verification_inputs import cos_weights, every, randn_batch, shifted
 
 GRIDS = ((17, 32), (33, 64))
-LEVELS = (100, 500, 850)
-
-
-def cos_weights(lat_deg: np.ndarray) -> np.ndarray:
-    """The test's own weights: cos(lat) / mean cos(lat)."""
-    c = np.cos(np.deg2rad(np.asarray(lat_deg, dtype=np.float64)))
-    return c / c.mean()
 
 
 def yardstick_sums(p, t, c, w) -> np.ndarray:
@@ -43,24 +36,6 @@ def yardstick_sums(p, t, c, w) -> np.ndarray:
     return np.array(out)
 
 
-def make_batch(n_lat, n_lon, seed=0, B=2, T=2, offset=0.0, scale=1.0, dtype=torch.float32, levels=LEVELS):
-    """2 surface variables + 1 three-level variable, B = 2, two history entries (only the last one is scored)."""
-    g = torch.Generator().manual_seed(seed)
-    r = lambda *s: (offset + scale * torch.randn(*s, n_lat, n_lon, generator=g, dtype=torch.float64)).to(dtype)  # noqa: E731
-    md = Metadata(lat=torch.linspace(90, -90, n_lat, dtype=torch.float64), lon=torch.linspace(0, 360, n_lon + 1)[:-1],
-                  time=tuple(datetime(2023, 1, 1, 6) for _ in range(B)), atmos_levels=tuple(levels))
-    return Batch({"2t": r(B, T), "msl": r(B, T)}, {"lsm": r()}, {"z": r(B, T, len(levels))}, md)
-
-
-def shifted(b: Batch, f) -> Batch:
-    return Batch({k: f(v.clone()) for k, v in b.surf_vars.items()}, b.static_vars,
-                 {k: f(v.clone()) for k, v in b.atmos_vars.items()}, b.metadata)
-
-
-def every(d: dict) -> np.ndarray:
-    return np.concatenate([v.numpy().reshape(-1) for v in d.values()])
-
-
 def test_public_names():
     assert aurora_amd.scores is scores and aurora_amd.Scores is Scores
     assert "scores" in aurora_amd.__all__ and "Scores" in aurora_amd.__all__
@@ -69,7 +44,7 @@ def test_public_names():
 @pytest.mark.parametrize("n_lat,n_lon", GRIDS)
 @pytest.mark.parametrize("k", (2.5, -0.75))
 def test_constant_offset_gives_bias_k_rmse_and_mae_abs_k(n_lat, n_lon, k):
-    truth = make_batch(n_lat, n_lon, offset=280.0, scale=10.0, dtype=torch.float64)
+    truth = randn_batch(n_lat, n_lon, offset=280.0, scale=10.0, dtype=torch.float64)
     s = scores(shifted(truth, lambda v: v + k), truth)
     assert isinstance(s, Scores) and s.acc is None
     assert s.rmse["2t"].shape == (2,) and s.rmse["z"].shape == (2, 3) and s.rmse["2t"].dtype == torch.float64
@@ -82,13 +57,13 @@ def test_constant_offset_gives_bias_k_rmse_and_mae_abs_k(n_lat, n_lon, k):
 
 @pytest.mark.parametrize("n_lat,n_lon", GRIDS)
 def test_perfect_forecast_and_mirrored_anomaly(n_lat, n_lon):
-    truth, clim = make_batch(n_lat, n_lon, seed=1), make_batch(n_lat, n_lon, seed=2)
+    truth, clim = randn_batch(n_lat, n_lon, seed=1), randn_batch(n_lat, n_lon, seed=2)
     s = scores(truth, truth, clim)
     for d in (s.rmse, s.bias, s.mae):
         assert (every(d) == 0).all()
     np.testing.assert_allclose(every(s.acc), 1.0, rtol=1e-14)
     # p' = -t'  <=>  p = 2 c - t (exact in fp64 fields)
-    t64, c64 = make_batch(n_lat, n_lon, seed=1, dtype=torch.float64), make_batch(n_lat, n_lon, seed=2, dtype=torch.float64)
+    t64, c64 = randn_batch(n_lat, n_lon, seed=1, dtype=torch.float64), randn_batch(n_lat, n_lon, seed=2, dtype=torch.float64)
     mirrored = Batch({k: 2 * c64.surf_vars[k] - v for k, v in t64.surf_vars.items()}, {},
                      {k: 2 * c64.atmos_vars[k] - v for k, v in t64.atmos_vars.items()}, t64.metadata)
     np.testing.assert_allclose(every(scores(mirrored, t64, c64).acc), -1.0, rtol=1e-14)
@@ -96,7 +71,7 @@ def test_perfect_forecast_and_mirrored_anomaly(n_lat, n_lon):
 
 @pytest.mark.parametrize("n_lat,n_lon", GRIDS)
 def test_an_error_on_one_row_weighs_as_that_row(n_lat, n_lon):
-    truth = make_batch(n_lat, n_lon, seed=3)
+    truth = randn_batch(n_lat, n_lon, seed=3)
     w = cos_weights(np.linspace(90, -90, n_lat))
     e = 3.0
     for i in (0, 1, n_lat // 2, n_lat - 2):
@@ -109,7 +84,7 @@ def test_an_error_on_one_row_weighs_as_that_row(n_lat, n_lon):
 
 
 def test_history_only_the_last_entry_is_scored():
-    truth = make_batch(17, 32, seed=4)
+    truth = randn_batch(17, 32, seed=4)
     pred = shifted(truth, lambda v: v)
     pred.surf_vars["2t"][:, 0] += 100.0
     pred.atmos_vars["z"][:, 0] += 100.0
@@ -117,7 +92,7 @@ def test_history_only_the_last_entry_is_scored():
 
 
 def test_only_common_variables_are_scored():
-    truth = make_batch(17, 32, seed=5)
+    truth = randn_batch(17, 32, seed=5)
     pred = Batch({"2t": truth.surf_vars["2t"] + 1, "10u": truth.surf_vars["msl"]}, {}, {"z": truth.atmos_vars["z"] + 1,
                  "q": truth.atmos_vars["z"]}, truth.metadata)
     s = scores(pred, truth)
@@ -159,7 +134,7 @@ def test_host_sums_equal_the_yardstick():
 
 def test_nan_masks():
     n_lat, n_lon = 17, 32
-    truth, clim = make_batch(n_lat, n_lon, seed=7, offset=5.0), make_batch(n_lat, n_lon, seed=8, offset=5.0)
+    truth, clim = randn_batch(n_lat, n_lon, seed=7, offset=5.0), randn_batch(n_lat, n_lon, seed=8, offset=5.0)
     pred = shifted(truth, lambda v: v + 1.0)
     full = n_lat * n_lon
     base = scores(pred, truth, clim)
@@ -201,25 +176,25 @@ def test_nan_masks():
 
 
 def test_zero_anomaly_gives_nan_acc():
-    truth = make_batch(17, 32, seed=9)
+    truth = randn_batch(17, 32, seed=9)
     s = scores(truth, truth, truth)
     assert torch.isnan(s.acc["2t"]).all() and (s.rmse["2t"] == 0).all()
 
 
 def test_cpu_returns_host_scores():
-    truth = make_batch(17, 32, seed=10)
+    truth = randn_batch(17, 32, seed=10)
     s = scores(shifted(truth, lambda v: v + 1), truth).cpu()
     assert isinstance(s, Scores) and s.rmse["2t"].device.type == "cpu"
 
 
 def test_float64_fields_are_scored_on_the_host():
-    truth = make_batch(17, 32, seed=11, dtype=torch.float64, offset=1e5)
+    truth = randn_batch(17, 32, seed=11, dtype=torch.float64, offset=1e5)
     s = scores(shifted(truth, lambda v: v + 1e-3), truth)
     np.testing.assert_allclose(every(s.bias), 1e-3, rtol=1e-6)    # an offset an fp32 field could not hold at 1e5
 
 
 def test_argument_errors():
-    truth = make_batch(17, 32, seed=12)
+    truth = randn_batch(17, 32, seed=12)
     pred = shifted(truth, lambda v: v)
     md = truth.metadata
 
@@ -234,7 +209,7 @@ def test_argument_errors():
         scores(cropped, truth)
     assert (every(scores(cropped, truth.crop(4)).rmse) == 0).all()
     with pytest.raises(ValueError, match="lon"):
-        scores(pred, make_batch(17, 16, seed=12))
+        scores(pred, randn_batch(17, 16, seed=12))
     with pytest.raises(ValueError, match="lon"):
         scores(pred, with_md(truth, lon=md.lon + 0.5))
     with pytest.raises(ValueError, match="lat"):
@@ -242,7 +217,7 @@ def test_argument_errors():
     with pytest.raises(ValueError, match="atmos_levels"):
         scores(pred, with_md(truth, atmos_levels=(100, 500, 900)))
     with pytest.raises(ValueError, match="batch size"):
-        scores(pred, make_batch(17, 32, seed=12, B=3))
+        scores(pred, randn_batch(17, 32, seed=12, B=3))
     with pytest.raises(ValueError, match="climatology.*atmos_levels"):
         scores(pred, truth, with_md(truth, atmos_levels=(1, 2, 3)))
     with pytest.raises(ValueError, match="climatology has no"):

@@ -15,13 +15,9 @@ import aurora_amd
 from aurora_amd import Batch, Metadata, scores, spectra
 from aurora_amd.batch import BandBatch
 from aurora_amd.spectra import Spectra
+from tests.verification_inputs import cos_weights, planes_of, red_noise, red_noise_batch
 
 U = 2.0 ** -53
-
-
-def cos_weights(lat_deg) -> np.ndarray:
-    c = np.cos(np.deg2rad(np.asarray(lat_deg, dtype=np.float64)))
-    return c / c.mean()
 
 
 def ck(N: int) -> np.ndarray:
@@ -84,34 +80,6 @@ def spectra_bound(p, t, lat, bands, want):
     return out
 
 
-def red_noise(shape, seed, mean=5e4, amp=500.0):
-    """Rows with a realistic offset and tail: `mean` plus noise with a k^-3 amplitude spectrum, rounded to fp32."""
-    g = np.random.default_rng(seed)
-    N = shape[-1]
-    K = N // 2 + 1
-    a = np.zeros(K)
-    a[1:] = amp * np.arange(1, K, dtype=np.float64) ** -3.0
-    X = a * np.exp(2j * np.pi * g.random((*shape[:-1], K))) * N / 2
-    return (mean + np.fft.irfft(X, n=N, axis=-1)).astype(np.float32)
-
-
-def make_batch(n_lat, n_lon, seed=0, B=2, T=2, levels=(100, 500, 850), mean=5e4, dtype=torch.float32):
-    r = lambda k, *s: torch.from_numpy(red_noise((*s, n_lat, n_lon), seed * 10 + k, mean=mean)).to(dtype)  # noqa: E731
-    md = Metadata(lat=torch.linspace(90, -90, n_lat, dtype=torch.float64) if n_lat > 1 else torch.zeros(1, dtype=torch.float64),
-                  lon=torch.linspace(0, 360, n_lon + 1, dtype=torch.float64)[:-1],
-                  time=tuple(datetime(2023, 1, 1, 6) for _ in range(B)), atmos_levels=tuple(levels))
-    return Batch({"2t": r(0, B, T), "msl": r(1, B, T)}, {"lsm": r(2)}, {"z": r(3, B, T, len(levels))}, md)
-
-
-def planes_of(b: Batch):
-    """(name, index, plane) of every scored plane of a batch, in the order of the result's layout."""
-    for grp in ("surf_vars", "atmos_vars"):
-        for k, v in getattr(b, grp).items():
-            last = v[:, -1].cpu().numpy()
-            for idx in np.ndindex(*last.shape[:-2]):
-                yield k, idx, last[idx]
-
-
 def assert_matches_yardstick(s: Spectra, pred: Batch, truth, bands, rel=1e-12):
     s = s.cpu()
     lat = pred.metadata.lat.double().cpu().numpy()
@@ -164,7 +132,7 @@ def test_the_yardstick_against_a_direct_long_double_transform(N):
 @pytest.mark.parametrize("n_lat,n_lon", [(17, 32), (9, 45), (33, 64)])
 @pytest.mark.parametrize("with_truth", (False, True))
 def test_cpu_spectra_equal_the_yardstick(n_lat, n_lon, with_truth):
-    pred, truth = make_batch(n_lat, n_lon, seed=1), make_batch(n_lat, n_lon, seed=2)
+    pred, truth = red_noise_batch(n_lat, n_lon, seed=1), red_noise_batch(n_lat, n_lon, seed=2)
     bands = ((-90, 90), (-30, 30), (20, 90))
     s = spectra(pred, truth if with_truth else None, bands=bands)
     K = n_lon // 2 + 1
@@ -182,7 +150,7 @@ def test_cpu_spectra_equal_the_yardstick(n_lat, n_lon, with_truth):
 @pytest.mark.parametrize("n_lon", (32, 45, 1440))
 def test_parseval_and_the_error_spectrum_adds_up_to_rmse_squared(n_lon):
     n_lat = 17
-    pred, truth = make_batch(n_lat, n_lon, seed=3, mean=280.0), make_batch(n_lat, n_lon, seed=4, mean=281.0)
+    pred, truth = red_noise_batch(n_lat, n_lon, seed=3, mean=280.0), red_noise_batch(n_lat, n_lon, seed=4, mean=281.0)
     s = spectra(pred, truth)
     sc = scores(pred, truth)
     w = cos_weights(np.linspace(90, -90, n_lat))[:, None]
@@ -206,7 +174,7 @@ def test_a_pure_cosine_has_one_bin(n_lon):
 
 def test_bands_an_empty_one_and_a_single_row():
     n_lat, n_lon = 17, 32
-    pred = make_batch(n_lat, n_lon, seed=5)
+    pred = red_noise_batch(n_lat, n_lon, seed=5)
     lat = np.linspace(90, -90, n_lat)
     bands = ((-90, 90), (1.0, 2.0), (lat[3], lat[3]), (-90, 0), (0, 0), (-11.25, 33.75), (89, 90), (-90, -90))
     s = spectra(pred, bands=bands)
@@ -220,7 +188,7 @@ def test_bands_an_empty_one_and_a_single_row():
 
 def test_invalid_rows_are_left_out_and_counted():
     n_lat, n_lon = 17, 32
-    pred, truth = make_batch(n_lat, n_lon, seed=6), make_batch(n_lat, n_lon, seed=7)
+    pred, truth = red_noise_batch(n_lat, n_lon, seed=6), red_noise_batch(n_lat, n_lon, seed=7)
     bands = ((-90, 90), (0, 90), (-90, -1), (1.0, 2.0))
     base = spectra(pred, truth, bands=bands)
     pred.surf_vars["2t"][0, -1, 2, 7] = float("nan")                     # northern rows of 2t, batch element 0
@@ -242,8 +210,8 @@ def test_invalid_rows_are_left_out_and_counted():
 
 
 def test_float64_fields_and_common_variables():
-    pred = make_batch(9, 16, seed=8, dtype=torch.float64)
-    truth = make_batch(9, 16, seed=9, dtype=torch.float64)
+    pred = red_noise_batch(9, 16, seed=8, dtype=torch.float64)
+    truth = red_noise_batch(9, 16, seed=9, dtype=torch.float64)
     del truth.surf_vars["msl"]
     s = spectra(pred, truth)
     assert list(s.power) == ["2t", "z"]
@@ -252,8 +220,8 @@ def test_float64_fields_and_common_variables():
 
 
 def test_argument_errors():
-    truth = make_batch(17, 32, seed=10)
-    pred = make_batch(17, 32, seed=11)
+    truth = red_noise_batch(17, 32, seed=10)
+    pred = red_noise_batch(17, 32, seed=11)
     md = truth.metadata
 
     def with_md(b, **kw):
@@ -283,11 +251,11 @@ def test_argument_errors():
     with pytest.raises(ValueError, match=r"lat.*truth\.crop\(model\.patch_size\)"):
         spectra(pred.crop(4), truth)
     with pytest.raises(ValueError, match="lon"):
-        spectra(pred, make_batch(17, 16, seed=10))
+        spectra(pred, red_noise_batch(17, 16, seed=10))
     with pytest.raises(ValueError, match="atmos_levels"):
         spectra(pred, with_md(truth, atmos_levels=(100, 500, 900)))
     with pytest.raises(ValueError, match="batch size"):
-        spectra(pred, make_batch(17, 32, seed=10, B=3))
+        spectra(pred, red_noise_batch(17, 32, seed=10, B=3))
     with pytest.raises(ValueError, match="in common"):
         spectra(Batch({"10u": truth.surf_vars["2t"]}, {}, {}, md), truth)
     lat2, lon2 = md.lat[:, None].expand(17, 32), md.lon[None, :].expand(17, 32)

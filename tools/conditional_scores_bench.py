@@ -4,34 +4,35 @@ variables = 69 planes, 286 MB per input), with E = 4 and E = 8 edges, with and w
 
     python tools/conditional_scores_bench.py [--calls 30] [--repeats 5]
 
-Kernel: the ONE aurora_hip_conditional_scores call over all 69 planes (`lib.conditional_sums`: two launches), --calls of them
-captured back to back in a hipGraph and replayed between a HIP event pair after warm-up: device time per call = window /
-calls, free of the host's enqueue time; repeated --repeats times (median and spread).  Bytes read = planes x 721 x 1440 x
-(8 or 16 per point), counted here from the shapes.  Yardstick: `lib.scores_sums` without a climatology, timed the same way in
-the same session; its rate says what one read of the conditional call's inputs takes, and `x_read` is the conditional call
-over that time.  Also `conditional_scores()` issued eagerly, end to end (checks, cached tables, the call, the finalising
-torch operations), and torch: what a user would write on the same device without this kernel -- per variable, fp64, a bin
-index from comparisons and one masked sum per bin and slot -- in eager windows, alternating with the kernel inside each
-repeat.  Check: kernel and torch expression against each other on every plane and bin (integers equal, the bound of
-tests/test_gpu_conditional_scores.py), and the kernel repeatable bit for bit.
+State and timing: tools/verification_bench.py.  Kernel arm: the ONE aurora_hip_conditional_scores call over all 69 planes
+(`lib.conditional_sums`: two launches), --calls of them per graph.  Bytes read = planes x 721 x 1440 x (8 or 16 per point),
+counted here from the shapes.  Yardstick: `lib.scores_sums` without a climatology, a graph arm too; its rate says what one
+read of the conditional call's inputs takes, and `x_read` is the conditional call over that time.  Eager arms:
+`lib.conditional_sums` and `conditional_scores()` end to end (checks, cached tables, the call, the finalising torch
+operations).  Torch: what a user would write on the same device without this kernel -- per variable, fp64, a bin index from
+comparisons and one masked sum per bin and slot -- in eager windows.  Check: kernel and torch expression against each other
+on every plane and bin (integers equal, the bound of tests/test_gpu_conditional_scores.py), and the kernel repeatable bit
+for bit.
 """
 import argparse
 import json
-import statistics
-import sys
-from pathlib import Path
 
 import numpy as np
 import torch
+from verification_bench import N_LAT, N_LON, N_PLANES, alternate, captured, med_min_max, planes, state, window_ms
 
-sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
-sys.path.insert(0, str(Path(__file__).resolve().parent))
-from aurora_amd import Batch, conditional_scores  # noqa: E402
-from aurora_amd.engine import lib  # noqa: E402
-from aurora_amd.scores import latitude_weights  # noqa: E402
-from scores_bench import N_LAT, N_LON, N_PLANES, batch, planes, window_ms  # noqa: E402
+from aurora_amd import Batch, conditional_scores  # (verification_bench has put the repository on sys.path)
+from aurora_amd.engine import lib
+from aurora_amd.scores import latitude_weights
 
 EDGES = {4: (-1.5, -0.5, 0.5, 1.5), 8: (-2.0, -1.5, -1.0, -0.5, 0.5, 1.0, 1.5, 2.0)}
+
+
+def batch(seed: int, base: Batch | None = None, spread: float = 1.0) -> Batch:
+    """Seeded synthetic fields about 280 (those of tools/scores_bench.py); with `base`, base + spread x noise."""
+    g = torch.Generator(device="cuda").manual_seed(seed)
+    r = lambda *s: spread * torch.randn(*s, N_LAT, N_LON, device="cuda", generator=g)  # noqa: E731
+    return state(r, base) if base is not None else state(lambda *s: r(*s) + 280.0)
 
 
 def torch_sums(p, t, c, s, edges, w) -> torch.Tensor:
@@ -60,17 +61,6 @@ def torch_sums(p, t, c, s, edges, w) -> torch.Tensor:
     return torch.stack(out, dim=-2).reshape(-1, len(edges) + 1, 5)
 
 
-def timed(fn, calls: int, graph: bool):
-    if not graph:
-        return lambda: window_ms(fn, calls)
-    g = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(g):
-        for _ in range(calls):
-            fn()
-    window_ms(g.replay, 2)
-    return lambda: window_ms(g.replay, 1) / calls
-
-
 def case(pred: Batch, truth: Batch, centre, scale, E: int, calls: int, repeats: int) -> dict:
     w = torch.from_numpy(latitude_weights(pred.metadata.lat.numpy())).cuda()
     P, T = planes(pred), planes(truth)
@@ -95,23 +85,19 @@ def case(pred: Batch, truth: Batch, centre, scale, E: int, calls: int, repeats: 
     assert worst <= 1e-9, worst
     for f in (kernel, yard, whole, plain):
         window_ms(f, 3)
-    arms = {"kernel": timed(kernel, calls, True), "yardstick": timed(yard, calls, True), "eager": timed(kernel, calls, False),
-            "whole": timed(whole, calls, False), "torch": timed(plain, max(3, calls // 10), False)}
-    ms = {k: [] for k in arms}
-    for _ in range(repeats):                                  # alternate the arms inside every repeat
-        for k, f in arms.items():
-            ms[k].append(f())
+    ms = alternate({"kernel": captured(kernel, calls), "yardstick": captured(yard, calls), "eager": lambda: window_ms(kernel, calls),
+                    "whole": lambda: window_ms(whole, calls), "torch": lambda: window_ms(plain, max(3, calls // 10))}, repeats)
     n_in = 2 + (centre is not None) + (scale is not None)
     read = N_PLANES * N_LAT * N_LON * 4 * n_in
-    med = {k: statistics.median(v) for k, v in ms.items()}
+    med, span = ({k: med_min_max(v)[i] for k, v in ms.items()} for i in (0, 1))
     yard_rate = N_PLANES * N_LAT * N_LON * 8 / med["yardstick"] / 1e9                   # TB/s
     one_read_ms = read / yard_rate / 1e9
     return {"edges": E, "maps": centre is not None, "planes": N_PLANES, "grid": [N_LAT, N_LON], "bytes_per_point": 4 * n_in,
             "read_GB": read / 1e9, "calls_per_window": calls, "repeats": repeats, "kernel_ms": med["kernel"],
-            "kernel_ms_min_max": [min(ms["kernel"]), max(ms["kernel"])], "kernel_TBps": read / med["kernel"] / 1e9,
-            "scores_ms": med["yardstick"], "scores_ms_min_max": [min(ms["yardstick"]), max(ms["yardstick"])], "scores_TBps": yard_rate,
+            "kernel_ms_min_max": span["kernel"], "kernel_TBps": read / med["kernel"] / 1e9,
+            "scores_ms": med["yardstick"], "scores_ms_min_max": span["yardstick"], "scores_TBps": yard_rate,
             "one_read_ms": one_read_ms, "x_read": med["kernel"] / one_read_ms, "eager_call_ms": med["eager"],
-            "conditional_scores_call_ms": med["whole"], "torch_ms": med["torch"], "torch_ms_min_max": [min(ms["torch"]), max(ms["torch"])],
+            "conditional_scores_call_ms": med["whole"], "torch_ms": med["torch"], "torch_ms_min_max": span["torch"],
             "torch_over_kernel": med["torch"] / med["kernel"], "worst_error_over_bound_1e-9": worst / 1e-9}
 
 

@@ -4,47 +4,39 @@ same quantities as a torch expression.
 
     python tools/diagnostics_bench.py [--calls 20] [--repeats 5]
 
-Kernel: the ONE aurora_hip_diagnostics call (`lib.diagnostics`: the wind launch and the column launch) on preallocated
-outputs, --calls of them captured back to back in a hipGraph and replayed between a HIP event pair after warm-up: device
-time per call = window / calls, free of the host's enqueue time; repeated --repeats times (median and spread).  Bytes = 4 x
-721 x 1440 x (14 x (2 + 3) + 13 x 3 + 4) planes: every input plane a group reads once and every output written once,
-counted here from the shapes (u and v on levels are read by both launches and counted twice); TB/s = bytes / that time.
-Beside it, in the same session and by the same method, aurora_hip_scores over 69 prediction and 69 truth planes (bytes = 4 x
-721 x 1440 x 138): the streaming rate a reduction kernel of this library reaches here.  Also `diagnostics(batch, ALL)`
-issued eagerly (checks, cached tables, output allocation, the call), in windows of --calls.  Torch: the formulas of
-include/aurora_hip.h as `torch.roll` expressions in fp64 on the device (what a user would write without this kernel), in
-eager windows, alternating with the kernel inside each repeat.  Check: the call and `diagnostics()` give the same bits, the
-wind speed and the NaN pattern of the torch expression are equal, and the largest difference of the other fields relative
-to the result is reported (the bound, which is relative to the terms and not to the result, is tests/test_gpu_diagnostics.py's).
+Grid and timing: tools/verification_bench.py; the state is this bench's own (winds and humidity on real pressure levels).
+Kernel arm: the ONE aurora_hip_diagnostics call (`lib.diagnostics`: the wind launch and the column launch) on preallocated
+outputs, --calls of them per graph.  Bytes = 4 x 721 x 1440 x (14 x (2 + 3) + 13 x 3 + 4) planes: every input plane a group
+reads once and every output written once, counted here from the shapes (u and v on levels are read by both launches and
+counted twice); TB/s = bytes / that time.  Beside it, a graph arm too, aurora_hip_scores over 69 prediction and 69 truth
+planes (bytes = 4 x 721 x 1440 x 138): the streaming rate a reduction kernel of this library reaches here.  Eager arm:
+`diagnostics(batch, ALL)` (checks, cached tables, output allocation, the call).  Torch: the formulas of include/aurora_hip.h
+as `torch.roll` expressions in fp64 on the device (what a user would write without this kernel), in eager windows.
+Check: the call and `diagnostics()` give the same bits, the wind speed and the NaN pattern of the torch expression are equal,
+and the largest difference of the other fields relative to the result is reported (the bound, which is relative to the terms
+and not to the result, is tests/test_gpu_diagnostics.py's).
 """
 import argparse
 import json
-import statistics
-import sys
-from datetime import datetime
-from pathlib import Path
 
 import torch
+from verification_bench import N_LAT, N_LON, N_PLANES as SCORE_PLANES, alternate, captured, med_min_max, metadata, window_ms
 
-sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
-from aurora_amd import Batch, Metadata, diagnostics  # noqa: E402
-from aurora_amd.diagnostics import NAMES, _grid, level_weights, row_table  # noqa: E402
-from aurora_amd.engine import lib  # noqa: E402
+from aurora_amd import Batch, diagnostics  # (verification_bench has put the repository on sys.path)
+from aurora_amd.diagnostics import NAMES, _grid, level_weights, row_table
+from aurora_amd.engine import lib
 
-N_LAT, N_LON = 721, 1440
 LEVELS = (50, 100, 150, 200, 250, 300, 400, 500, 600, 700, 850, 925, 1000)
 C = len(LEVELS)
 ALL = tuple(NAMES)
-SCORE_PLANES = 69
 
 
 def state(seed: int) -> Batch:
     g = torch.Generator(device="cuda").manual_seed(seed)
     r = lambda off, sc, *s: off + sc * torch.randn(*s, N_LAT, N_LON, device="cuda", generator=g)  # noqa: E731
-    md = Metadata(lat=torch.linspace(90, -90, N_LAT, dtype=torch.float64), lon=torch.linspace(0, 360, N_LON + 1, dtype=torch.float64)[:-1],
-                  time=(datetime(2022, 5, 11, 12),), atmos_levels=LEVELS)
     return Batch({"10u": r(40, 5, 1, 1), "10v": r(-30, 5, 1, 1)}, {},
-                 {"u": r(40, 5, 1, 1, C), "v": r(-30, 5, 1, 1, C), "q": (0.005 * (1 + 0.3 * r(0, 1, 1, 1, C))).abs()}, md)
+                 {"u": r(40, 5, 1, 1, C), "v": r(-30, 5, 1, 1, C), "q": (0.005 * (1 + 0.3 * r(0, 1, 1, 1, C))).abs()},
+                 metadata(atmos_levels=LEVELS))
 
 
 def torch_diagnostics(b: Batch, rows: torch.Tensor, L: float, w: torch.Tensor) -> dict:
@@ -67,16 +59,6 @@ def torch_diagnostics(b: Batch, rows: torch.Tensor, L: float, w: torch.Tensor) -
     t, iu, iv = wq.sum(1), (wq * u).sum(1), (wq * v).sum(1)
     out.update(tcwv=fin(t), ivtu=fin(iu), ivtv=fin(iv), ivt=fin(torch.sqrt(iu * iu + iv * iv)))
     return out
-
-
-def window_ms(fn, calls: int) -> float:
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(calls):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / calls
 
 
 def main() -> None:
@@ -127,28 +109,16 @@ def main() -> None:
     score = lambda: lib.scores_sums(pred, truth, None, row_w)  # noqa: E731
     for f in (kernel, whole, plain, score):
         window_ms(f, 3)
-    graphs = []
-    for f in (kernel, score):
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            for _ in range(args.calls):
-                f()
-        window_ms(g.replay, 2)
-        graphs.append(g)
-    ms = {"kernel": [], "scores": [], "call": [], "torch": []}
-    for _ in range(args.repeats):                                # alternate the arms inside every repeat
-        ms["kernel"].append(window_ms(graphs[0].replay, 1) / args.calls)
-        ms["scores"].append(window_ms(graphs[1].replay, 1) / args.calls)
-        ms["torch"].append(window_ms(plain, 3))
-        ms["call"].append(window_ms(whole, args.calls))
-    med = {k: statistics.median(v) for k, v in ms.items()}
+    ms = alternate({"kernel": captured(kernel, args.calls), "scores": captured(score, args.calls),
+                    "torch": lambda: window_ms(plain, 3), "call": lambda: window_ms(whole, args.calls)}, args.repeats)
+    med, span = ({k: med_min_max(v)[i] for k, v in ms.items()} for i in (0, 1))
     scores_moved = 4 * P * 2 * SCORE_PLANES
     rec = {"grid": [N_LAT, N_LON], "levels": C, "names": len(ALL), "moved_GB": moved / 1e9, "calls_per_window": args.calls,
-           "repeats": args.repeats, "kernel_ms": med["kernel"], "kernel_ms_min_max": [min(ms["kernel"]), max(ms["kernel"])],
+           "repeats": args.repeats, "kernel_ms": med["kernel"], "kernel_ms_min_max": span["kernel"],
            "kernel_TBps": moved / med["kernel"] / 1e9, "scores_moved_GB": scores_moved / 1e9, "scores_ms": med["scores"],
-           "scores_ms_min_max": [min(ms["scores"]), max(ms["scores"])], "scores_TBps": scores_moved / med["scores"] / 1e9,
-           "diagnostics_call_ms": med["call"], "diagnostics_call_ms_min_max": [min(ms["call"]), max(ms["call"])],
-           "torch_ms": med["torch"], "torch_ms_min_max": [min(ms["torch"]), max(ms["torch"])],
+           "scores_ms_min_max": span["scores"], "scores_TBps": scores_moved / med["scores"] / 1e9,
+           "diagnostics_call_ms": med["call"], "diagnostics_call_ms_min_max": span["call"],
+           "torch_ms": med["torch"], "torch_ms_min_max": span["torch"],
            "torch_over_kernel": med["torch"] / med["kernel"], "worst_relative_difference_to_torch": worst}
     print(f"every name of a {C}-level 0.25-degree state: {rec['moved_GB']:.3f} GB moved: kernel call {rec['kernel_ms']:.3f} ms (device "
           f"time, median of {args.repeats} graph replays of {args.calls} calls; {rec['kernel_ms_min_max'][0]:.3f}-"

@@ -3,61 +3,39 @@
 
     python tools/ensemble_scores_bench.py [--members 8 16 51] [--calls 20] [--repeats 5]
 
-Data: seeded on the device, truth = 101325 + 300 randn per plane, member = truth + 0.5 + 2 randn.
-Kernel: the ONE aurora_hip_ensemble_scores call over all 69 planes (`lib.ensemble_scores_sums`: two launches), --calls of
-them captured back to back in a hipGraph and replayed between a HIP event pair after warm-up: device time per call =
-window / calls, free of the host's enqueue time; repeated --repeats times (median and spread).  Bytes read = (M + 1) x
-planes x 721 x 1440 x 4, counted here from the shapes; TB/s = bytes / that time; `x bytes / 5.0 TB/s` is that time over what
-the read alone would take at the rate scores.hip reaches (1.0 = bandwidth-bound as that kernel is; above it the bucket is
-bound by its arithmetic).  Also `ensemble_scores()` end to end, issued eagerly (checks, cached tables, the call, the
-finalising torch operations).
+State and timing: tools/verification_bench.py.  Data: seeded on the device, truth = 101325 + 300 randn per plane,
+member = truth + 0.5 + 2 randn.
+Kernel arm: the ONE aurora_hip_ensemble_scores call over all 69 planes (`lib.ensemble_scores_sums`: two launches), --calls of
+them per graph.  Bytes read = (M + 1) x planes x 721 x 1440 x 4, counted here from the shapes; TB/s = bytes / that time;
+`x bytes / 5.0 TB/s` is that time over what the read alone would take at the rate scores.hip reaches (1.0 = bandwidth-bound
+as that kernel is; above it the bucket is bound by its arithmetic).  Eager arm: `ensemble_scores()` end to end (checks,
+cached tables, the call, the finalising torch operations).
 Torch: what a user would write on the same device without this kernel -- fp64 differences, a finite mask, `torch.sort`
 over the members for g and the ranks -- evaluated VARIABLE BY VARIABLE (13 planes at a time), and for M > 16 plane by plane,
 because the (M, planes, 721, 1440) fp64 temporaries of the whole state (M = 51: 29 GB each, several alive at once) do not
-fit beside the members; one evaluation per repeat, alternating with the kernel inside each repeat.
+fit beside the members; one evaluation per repeat.
 Check: both against each other on every plane within the bound of tests/test_gpu_ensemble_scores.py (Q taken from the torch
 side), and the kernel repeatable bit for bit.
 """
 import argparse
 import json
-import statistics
-import sys
-from datetime import datetime
-from pathlib import Path
 
 import numpy as np
 import torch
+from verification_bench import N_LAT, N_LON, N_PLANES, alternate, captured, med_min_max, planes, state, window_ms
 
-sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
-from aurora_amd import Batch, Metadata, ensemble_scores  # noqa: E402
-from aurora_amd.engine import lib  # noqa: E402
-from aurora_amd.scores import latitude_weights  # noqa: E402
+from aurora_amd import Batch, ensemble_scores  # (verification_bench has put the repository on sys.path)
+from aurora_amd.engine import lib
+from aurora_amd.scores import latitude_weights
 
-SURF, ATMOS, LEVELS = ("2t", "10u", "10v", "msl"), ("z", "u", "v", "t", "q"), 13
-N_LAT, N_LON = 721, 1440
-N_PLANES = len(SURF) + len(ATMOS) * LEVELS
 ROOF_TBPS = 5.0                                   # what scores.hip reaches on this state (profiles/scores_bench.log)
 REL = 1e-9
 
 
 def batch(g: torch.Generator, base: Batch | None = None) -> Batch:
     """Seeded synthetic fields: the truth, or with `base` a member = base + 0.5 + 2 randn."""
-    lat = torch.linspace(90, -90, N_LAT, dtype=torch.float64)
-    lon = torch.linspace(0, 360, N_LON + 1, dtype=torch.float64)[:-1]
-    md = base.metadata if base is not None else Metadata(lat=lat, lon=lon, time=(datetime(2022, 5, 11, 12),),
-                                                         atmos_levels=tuple(range(50, 50 + 75 * LEVELS, 75)))
-
-    def field(*lead, of=None):
-        r = torch.randn(*lead, N_LAT, N_LON, device="cuda", generator=g)
-        return r.mul_(300).add_(101325) if of is None else r.mul_(2).add_(0.5).add_(of)
-
-    surf = {k: field(1, 1, of=None if base is None else base.surf_vars[k]) for k in SURF}
-    atmos = {k: field(1, 1, LEVELS, of=None if base is None else base.atmos_vars[k]) for k in ATMOS}
-    return Batch(surf, {}, atmos, md)
-
-
-def planes(b: Batch) -> list[torch.Tensor]:
-    return [v[:, -1] for v in (*b.surf_vars.values(), *b.atmos_vars.values())]
+    r = lambda *lead: torch.randn(*lead, N_LAT, N_LON, device="cuda", generator=g)  # noqa: E731
+    return state(lambda *lead: r(*lead).mul_(300).add_(101325)) if base is None else state(lambda *lead: r(*lead).mul_(2).add_(0.5), base)
 
 
 def torch_sums(x: torch.Tensor, y: torch.Tensor, w: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
@@ -80,16 +58,6 @@ def torch_sums(x: torch.Tensor, y: torch.Tensor, w: torch.Tensor) -> tuple[torch
     below = (x < y).sum(dim=0)
     bins = torch.stack([total(ok & (below == b)) for b in range(M + 1)] + [total(ok & (x == y).any(dim=0))], dim=-1)
     return sums, bins, total(W * q)
-
-
-def window_ms(fn, calls: int) -> float:
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(calls):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / calls
 
 
 def case(M: int, calls: int, repeats: int) -> dict:
@@ -123,23 +91,15 @@ def case(M: int, calls: int, repeats: int) -> dict:
     assert worst <= REL, worst
     for f in (kernel, whole):
         window_ms(f, 3)
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        for _ in range(calls):
-            kernel()
-    window_ms(graph.replay, 2)
-    ms = {"kernel": [], "scores": [], "torch": []}
-    for _ in range(repeats):                                  # alternate the arms inside every repeat
-        ms["kernel"].append(window_ms(graph.replay, 1) / calls)
-        ms["torch"].append(window_ms(plain, 1))
-        ms["scores"].append(window_ms(whole, calls))
+    ms = alternate({"kernel": captured(kernel, calls), "torch": lambda: window_ms(plain, 1),
+                    "scores": lambda: window_ms(whole, calls)}, repeats)
     read = (M + 1) * N_PLANES * N_LAT * N_LON * 4
-    med = {k: statistics.median(v) for k, v in ms.items()}
+    med, span = ({k: med_min_max(v)[i] for k, v in ms.items()} for i in (0, 1))
     return {"members": M, "planes": N_PLANES, "grid": [N_LAT, N_LON], "read_GB": read / 1e9, "calls_per_window": calls,
-            "repeats": repeats, "kernel_ms": med["kernel"], "kernel_ms_min_max": [min(ms["kernel"]), max(ms["kernel"])],
+            "repeats": repeats, "kernel_ms": med["kernel"], "kernel_ms_min_max": span["kernel"],
             "kernel_TBps": read / med["kernel"] / 1e9, "roof_ms_at_5TBps": read / ROOF_TBPS / 1e9,
             "kernel_over_roof": med["kernel"] / (read / ROOF_TBPS / 1e9), "ensemble_scores_call_ms": med["scores"],
-            "torch_ms": med["torch"], "torch_ms_min_max": [min(ms["torch"]), max(ms["torch"])],
+            "torch_ms": med["torch"], "torch_ms_min_max": span["torch"],
             "torch_planes_per_evaluation": group, "torch_over_kernel": med["torch"] / med["kernel"],
             "worst_error_over_bound_1e-9": worst / REL}
 

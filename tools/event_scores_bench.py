@@ -3,34 +3,26 @@
 
     python tools/event_scores_bench.py [--calls 10] [--repeats 5]
 
-Kernel: the ONE aurora_hip_event_scores call over all 69 planes (`lib.event_rowsums`: two launches), --calls of
-them captured back to back in a hipGraph and replayed between a HIP event pair after warm-up: device time per call = window /
-calls; repeated --repeats times (median and spread).  Also `event_scores()` issued eagerly, end to end (the call plus the
+State and timing: tools/verification_bench.py.  Kernel arm: the ONE aurora_hip_event_scores call over all 69 planes
+(`lib.event_rowsums`: two launches), --calls of them per graph.  Eager arm: `event_scores()` end to end (the call plus the
 finalisation).  Read floor: the time a single read of both inputs (2 x 69 x 721 x 1440 x 4 bytes) takes at the rate
 `aurora_hip_scores` reaches on this device, measured here the same way (it reads the same two inputs once).
 Torch: what a user would write on the same device without this kernel -- per threshold the two masks, then per window size
 F.avg_pool2d with circular longitude / zero latitude padding and divisor 1 in fp32 (counts <= 33^2 are exact), the three
-squares summed per row in fp64 -- batched over all 69 planes, in eager windows alternating with the kernel inside each repeat:
-a yardstick only.  Check: the torch expression and the kernel must be equal on every integer, and the kernel repeatable.
+squares summed per row in fp64 -- batched over all 69 planes, in eager windows: a yardstick only.
+Check: the torch expression and the kernel must be equal on every integer, and the kernel repeatable.
 """
 import argparse
 import json
-import statistics
-import sys
-from datetime import datetime
-from pathlib import Path
 
 import torch
 import torch.nn.functional as F
+from verification_bench import N_LAT, N_LON, N_PLANES, alternate, captured, med_min_max, planes, state, window_ms
 
-sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
-from aurora_amd import Batch, Metadata, event_scores  # noqa: E402
-from aurora_amd.engine import lib  # noqa: E402
-from aurora_amd._fields import device_weights  # noqa: E402
+from aurora_amd import Batch, event_scores  # (verification_bench has put the repository on sys.path)
+from aurora_amd._fields import device_weights
+from aurora_amd.engine import lib
 
-SURF, ATMOS, LEVELS = ("2t", "10u", "10v", "msl"), ("z", "u", "v", "t", "q"), 13
-N_LAT, N_LON = 721, 1440
-N_PLANES = len(SURF) + len(ATMOS) * LEVELS
 SCALES = (1, 5, 9, 17, 33)
 QUANTILES = (0.5, 0.9, 0.99)
 
@@ -38,23 +30,13 @@ QUANTILES = (0.5, 0.9, 0.99)
 def batch(seed: int, base: Batch | None = None, spread: float = 1.0) -> Batch:
     """Smooth fields (white noise box-filtered over 15 x 15 points, so that events cluster), 5e4 + O(1)."""
     g = torch.Generator(device="cuda").manual_seed(seed)
-    lat = torch.linspace(90, -90, N_LAT, dtype=torch.float64)
-    lon = torch.linspace(0, 360, N_LON + 1, dtype=torch.float64)[:-1]
 
     def r(*s):
         x = torch.randn(int(torch.tensor(s).prod()), 1, N_LAT, N_LON, device="cuda", generator=g)
         x = F.avg_pool2d(F.pad(x, (7, 7, 7, 7), mode="circular"), 15, stride=1) * 15.0
         return (spread * x).reshape(*s, N_LAT, N_LON)
 
-    md = base.metadata if base is not None else Metadata(lat=lat, lon=lon, time=(datetime(2022, 5, 11, 12),),
-                                                         atmos_levels=tuple(range(50, 50 + 75 * LEVELS, 75)))
-    surf = {k: (r(1, 1) + (base.surf_vars[k] if base is not None else 5e4)).contiguous() for k in SURF}
-    atmos = {k: (r(1, 1, LEVELS) + (base.atmos_vars[k] if base is not None else 5e4)).contiguous() for k in ATMOS}
-    return Batch(surf, {}, atmos, md)
-
-
-def planes(b: Batch) -> list[torch.Tensor]:
-    return [v[:, -1] for v in (*b.surf_vars.values(), *b.atmos_vars.values())]
+    return state(r, base) if base is not None else state(lambda *s: r(*s) + 5e4)
 
 
 def torch_rowsums(p: torch.Tensor, t: torch.Tensor, thr: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
@@ -75,24 +57,6 @@ def torch_rowsums(p: torch.Tensor, t: torch.Tensor, thr: torch.Tensor) -> tuple[
             out[:, ti, si, :, 1] = ((cf ** 2) * okd).sum(dim=-1).long()
             out[:, ti, si, :, 2] = ((co ** 2) * okd).sum(dim=-1).long()
     return out, ok.sum(dim=-1)
-
-
-def window_ms(fn, calls: int) -> float:
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(calls):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / calls
-
-
-def graph_of(fn, calls: int) -> torch.cuda.CUDAGraph:
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        for _ in range(calls):
-            fn()
-    return graph
 
 
 def main() -> None:
@@ -127,24 +91,17 @@ def main() -> None:
     assert torch.equal(s.rowsums_table, got[0])
     fss = s.cpu().fss["2t"][0]
     for f in (kernel, whole, plain, reader):
-        window_ms(f, 2)
-    g_kernel, g_reader = graph_of(kernel, args.calls), graph_of(reader, args.calls)
-    window_ms(g_kernel.replay, 1)
-    window_ms(g_reader.replay, 1)
-    ms = {"kernel": [], "event_scores": [], "torch": [], "scores": []}
-    for _ in range(args.repeats):                              # alternate the arms inside every repeat
-        ms["kernel"].append(window_ms(g_kernel.replay, 1) / args.calls)
-        ms["scores"].append(window_ms(g_reader.replay, 1) / args.calls)
-        ms["torch"].append(window_ms(plain, 2))
-        ms["event_scores"].append(window_ms(whole, args.calls))
-    med = {k: statistics.median(v) for k, v in ms.items()}
+        window_ms(f, 3)
+    ms = alternate({"kernel": captured(kernel, args.calls), "scores": captured(reader, args.calls),
+                    "torch": lambda: window_ms(plain, 2), "event_scores": lambda: window_ms(whole, args.calls)}, args.repeats)
+    med, span = ({k: med_min_max(v)[i] for k, v in ms.items()} for i in (0, 1))
     gbytes = 2 * N_PLANES * N_LAT * N_LON * 4 / 1e9
     rec = {"planes": N_PLANES, "grid": [N_LAT, N_LON], "thresholds": len(QUANTILES), "scales": list(SCALES),
            "calls_per_window": args.calls, "repeats": args.repeats, "kernel_ms": med["kernel"],
-           "kernel_ms_min_max": [min(ms["kernel"]), max(ms["kernel"])], "event_scores_call_ms": med["event_scores"],
+           "kernel_ms_min_max": span["kernel"], "event_scores_call_ms": med["event_scores"],
            "input_GB": gbytes, "scores_read_ms": med["scores"], "scores_read_TBps": gbytes / med["scores"],
            "kernel_over_one_read": med["kernel"] / med["scores"], "torch_ms": med["torch"],
-           "torch_ms_min_max": [min(ms["torch"]), max(ms["torch"])], "kernel_over_torch": med["kernel"] / med["torch"],
+           "torch_ms_min_max": span["torch"], "kernel_over_torch": med["kernel"] / med["torch"],
            "torch_over_kernel": med["torch"] / med["kernel"], "integers_equal": True,
            "fss_2t_first_threshold": [round(float(x), 4) for x in fss[0]]}
     print(f"kernel call {rec['kernel_ms']:.3f} ms (device time, median of {args.repeats} graph replays of {args.calls} calls; "

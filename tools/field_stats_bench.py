@@ -3,46 +3,33 @@ planes) with T = 2 thresholds: M = 16 ensemble members in ONE update, beside the
 
     python tools/field_stats_bench.py [--calls 20] [--repeats 5]
 
-Kernel: the ONE aurora_hip_field_stats_update call over all 69 planes and 16 samples (`lib.field_stats_update`: the main
-launch and the one-thread launch that advances the sample index), --calls of them captured back to back in a hipGraph and
-replayed between a HIP event pair after warm-up: device time per update = window / calls, free of the host's enqueue time;
-repeated --repeats times (median and spread).  Bytes = planes x 721 x 1440 x (4 M + 2 (36 + 12 T)): every sample read once,
-the state read once and written once, counted here from the shapes; TB/s = bytes / that time.  Also the same window issued
-eagerly through `FieldStats.update(members, over="batch")` (checks, cached tables, the call), and a one-sample update (a
-roll-out step: 4 + 2 (36 + 12 T) bytes per point).  Torch: the same state advanced sample by sample with elementwise torch
-operations on the device (what a user would write without this kernel), in eager windows, alternating with the kernel inside
-each repeat.  Check: the integers, origin, minimum and maximum of both are equal and the sums agree to the bound of
-tests/test_gpu_field_stats.py.  The share of a step is the one-sample `update` issued eagerly over the 124 ms of the
+State (here with B members as its batch elements) and timing: tools/verification_bench.py.  Kernel arms: the ONE
+aurora_hip_field_stats_update call over all 69 planes and 16 samples (`lib.field_stats_update`: the main launch and the
+one-thread launch that advances the sample index), --calls of them per graph, and a one-sample update (a roll-out step).
+Bytes = planes x 721 x 1440 x (4 M + 2 (36 + 12 T)): every sample read once, the state read once and written once, counted
+here from the shapes (one sample: 4 + 2 (36 + 12 T) bytes per point); TB/s = bytes / that time.  Eager arms:
+`FieldStats.update(members, over="batch")` (checks, cached tables, the call) and the one-sample `update`.  Torch: the same
+state advanced sample by sample with elementwise torch operations on the device (what a user would write without this
+kernel), in eager windows.  Check: the integers, origin, minimum and maximum of both are equal and the sums agree to the
+bound of tests/test_gpu_field_stats.py.  The share of a step is the one-sample `update` issued eagerly over the 124 ms of the
 0.25-degree step.
 """
 import argparse
 import json
-import statistics
-import sys
-from datetime import datetime
-from pathlib import Path
 
 import torch
+from verification_bench import ATMOS, N_LAT, N_LON, N_PLANES, STEP_MS, SURF, alternate, captured, med_min_max, planes, state, window_ms
 
-sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
-from aurora_amd import Batch, FieldStats, Metadata  # noqa: E402
-from aurora_amd.engine import lib  # noqa: E402
+from aurora_amd import Batch, FieldStats  # (verification_bench has put the repository on sys.path)
+from aurora_amd.engine import lib
 
-SURF, ATMOS, LEVELS = ("2t", "10u", "10v", "msl"), ("z", "u", "v", "t", "q"), 13
-N_LAT, N_LON, M, T = 721, 1440, 16, 2
-N_PLANES = len(SURF) + len(ATMOS) * LEVELS
-STEP_MS = 124.0
+M, T = 16, 2
 THRESHOLDS = {k: [280.5, 281.5] for k in (*SURF, *ATMOS)}
 
 
 def members(seed: int, B: int) -> Batch:
     g = torch.Generator(device="cuda").manual_seed(seed)
-    lat = torch.linspace(90, -90, N_LAT, dtype=torch.float64)
-    lon = torch.linspace(0, 360, N_LON + 1, dtype=torch.float64)[:-1]
-    r = lambda *s: 280.0 + torch.randn(*s, N_LAT, N_LON, device="cuda", generator=g)  # noqa: E731
-    md = Metadata(lat=lat, lon=lon, time=tuple(datetime(2022, 5, 11, 12) for _ in range(B)),
-                  atmos_levels=tuple(range(50, 50 + 75 * LEVELS, 75)))
-    return Batch({k: r(B, 1) for k in SURF}, {}, {k: r(B, 1, LEVELS) for k in ATMOS}, md)
+    return state(lambda *s: 280.0 + torch.randn(*s, N_LAT, N_LON, device="cuda", generator=g), B=B)
 
 
 def new_state() -> dict:
@@ -70,16 +57,6 @@ def torch_update(s: dict, x: torch.Tensor, thr: torch.Tensor, index: int) -> Non
     s["n"] += ok
 
 
-def window_ms(fn, calls: int) -> float:
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(calls):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / calls
-
-
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--calls", type=int, default=20, help="back-to-back updates per timed window")
@@ -90,12 +67,11 @@ def main() -> None:
           f"{N_PLANES * P * (36 + 12 * T) / 1e9:.2f} GB, members {N_PLANES * P * 4 * M / 1e9:.2f} GB", flush=True)
     ens = members(0, M)
     one = members(1, 1)
-    fields = lambda b: [v[:, -1] for v in (*b.surf_vars.values(), *b.atmos_vars.values())]  # noqa: E731
-    samples = [[f[m:m + 1] for f in fields(ens)] for m in range(M)]
+    samples = [[f[m:m + 1] for f in planes(ens)] for m in range(M)]
     thr = torch.tensor([[280.5, 281.5]] * N_PLANES, dtype=torch.float32, device="cuda")
     state, index = new_state(), torch.zeros(1, dtype=torch.int64, device="cuda")
     kernel = lambda: lib.field_stats_update(samples, None, None, thr, False, index, state)  # noqa: E731
-    single = lambda: lib.field_stats_update([fields(one)], None, None, thr, False, index, state)  # noqa: E731
+    single = lambda: lib.field_stats_update([planes(one)], None, None, thr, False, index, state)  # noqa: E731
     plain_state = new_state()
     stack = torch.stack([torch.cat([f.reshape(-1, P) for f in fs]) for fs in samples])          # (M, n_planes, P): a copy
 
@@ -120,31 +96,19 @@ def main() -> None:
     whole_one = lambda: acc_one.update(one)  # noqa: E731
     for f in (kernel, single, whole, whole_one):
         window_ms(f, 3)
-    graphs = []
-    for f in (kernel, single):
-        g = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(g):
-            for _ in range(args.calls):
-                f()
-        window_ms(g.replay, 2)
-        graphs.append(g)
-    ms = {"kernel": [], "single": [], "update": [], "update_one": [], "torch": []}
-    for _ in range(args.repeats):                                # alternate the arms inside every repeat
-        ms["kernel"].append(window_ms(graphs[0].replay, 1) / args.calls)
-        ms["single"].append(window_ms(graphs[1].replay, 1) / args.calls)
-        ms["torch"].append(window_ms(plain, 2))
-        ms["update"].append(window_ms(whole, args.calls))
-        ms["update_one"].append(window_ms(whole_one, args.calls))
-    med = {k: statistics.median(v) for k, v in ms.items()}
+    ms = alternate({"kernel": captured(kernel, args.calls), "single": captured(single, args.calls),
+                    "torch": lambda: window_ms(plain, 2), "update": lambda: window_ms(whole, args.calls),
+                    "update_one": lambda: window_ms(whole_one, args.calls)}, args.repeats)
+    med, span = ({k: med_min_max(v)[i] for k, v in ms.items()} for i in (0, 1))
     moved = N_PLANES * P * (4 * M + 2 * (36 + 12 * T))
     moved_one = N_PLANES * P * (4 + 2 * (36 + 12 * T))
     rec = {"planes": N_PLANES, "grid": [N_LAT, N_LON], "members": M, "thresholds": T, "moved_GB": moved / 1e9,
            "calls_per_window": args.calls, "repeats": args.repeats, "kernel_ms": med["kernel"],
-           "kernel_ms_min_max": [min(ms["kernel"]), max(ms["kernel"])], "kernel_TBps": moved / med["kernel"] / 1e9,
+           "kernel_ms_min_max": span["kernel"], "kernel_TBps": moved / med["kernel"] / 1e9,
            "one_sample_moved_GB": moved_one / 1e9, "one_sample_kernel_ms": med["single"],
-           "one_sample_kernel_ms_min_max": [min(ms["single"]), max(ms["single"])], "one_sample_TBps": moved_one / med["single"] / 1e9,
+           "one_sample_kernel_ms_min_max": span["single"], "one_sample_TBps": moved_one / med["single"] / 1e9,
            "update_call_ms": med["update"], "one_sample_update_call_ms": med["update_one"], "torch_ms": med["torch"],
-           "torch_ms_min_max": [min(ms["torch"]), max(ms["torch"])], "torch_over_kernel": med["torch"] / med["kernel"],
+           "torch_ms_min_max": span["torch"], "torch_over_kernel": med["torch"] / med["kernel"],
            "share_of_step_percent": 100 * med["update_one"] / STEP_MS, "worst_error_over_bound": worst}
     print(f"{M} members in one update: {rec['moved_GB']:.3f} GB moved: kernel call {rec['kernel_ms']:.3f} ms (device time, median of "
           f"{args.repeats} graph replays of {args.calls} calls; {rec['kernel_ms_min_max'][0]:.3f}-{rec['kernel_ms_min_max'][1]:.3f}) = "

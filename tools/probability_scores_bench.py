@@ -8,12 +8,11 @@ Data: seeded on the device, truth = 101325 + 300 randn per plane, member = truth
 climatological deviation); thresholds 101325, 101709 and 102024 on every plane (about the 0.5, 0.9 and 0.99 quantiles of the
 truth).  The share of valid points outside the two corner bins (o = 0, k = 0) and (o = 1, k = M) is printed per threshold: those
 are the points that reach an LDS atomic in the kernel's ballot form.
-Kernel: the ONE aurora_hip_probability_scores call over all 69 planes (`lib.probability_rows`: one launch), --calls of them
-captured back to back in a hipGraph and replayed between a HIP event pair after warm-up: device time per call = window / calls,
-free of the host's enqueue time; repeated --repeats times (median and spread).  Bytes read = (M + 1) x planes x 721 x 1440 x 4,
-counted here from the shapes; TB/s = bytes / that time.  Yardstick: the same bytes at the rate aurora_hip_ensemble_scores
-reaches on the same members in the same session (timed the same way, alternating with the kernel inside each repeat):
-`x ensemble_scores` is this call's time over that call's time, both reading the same bytes.
+State and timing: tools/verification_bench.py.  Kernel arm: the ONE aurora_hip_probability_scores call over all 69 planes
+(`lib.probability_rows`: one launch), --calls of them per graph.  Bytes read = (M + 1) x planes x 721 x 1440 x 4, counted here
+from the shapes; TB/s = bytes / that time.  Yardstick: the same bytes at the rate aurora_hip_ensemble_scores reaches on the
+same members in the same session (a graph arm too): `x ensemble_scores` is this call's time over that call's time, both
+reading the same bytes.
 --plain-lib: a second build of the library whose kernel sends EVERY valid lane through an LDS atomic instead of taking the two
 corner bins by ballot and popcount:
     AURORA_BUILD_FLAGS=-DAURORA_PROBABILITY_PLAIN_ATOMICS python -m aurora_amd.build --force, the library then copied aside
@@ -28,42 +27,22 @@ Check: kernel, plain form and torch expression equal on every entry (integers), 
 import argparse
 import ctypes
 import json
-import statistics
-import sys
-from datetime import datetime
 from pathlib import Path
 
 import torch
+from verification_bench import ATMOS, N_LAT, N_LON, N_PLANES, SURF, alternate, captured, med_min_max, planes, state, window_ms
 
-sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
-from aurora_amd import Batch, Metadata, probability_scores  # noqa: E402
-from aurora_amd.engine import lib  # noqa: E402
-from aurora_amd.scores import latitude_weights  # noqa: E402
+from aurora_amd import Batch, probability_scores  # (verification_bench has put the repository on sys.path)
+from aurora_amd.engine import lib
+from aurora_amd.scores import latitude_weights
 
-SURF, ATMOS, LEVELS = ("2t", "10u", "10v", "msl"), ("z", "u", "v", "t", "q"), 13
-N_LAT, N_LON = 721, 1440
-N_PLANES = len(SURF) + len(ATMOS) * LEVELS
 THRESHOLDS = (101325.0, 101709.0, 102024.0)
 
 
 def batch(g: torch.Generator, base: Batch | None = None) -> Batch:
     """Seeded synthetic fields: the truth, or with `base` a member = base + 60 randn."""
-    lat = torch.linspace(90, -90, N_LAT, dtype=torch.float64)
-    lon = torch.linspace(0, 360, N_LON + 1, dtype=torch.float64)[:-1]
-    md = base.metadata if base is not None else Metadata(lat=lat, lon=lon, time=(datetime(2022, 5, 11, 12),),
-                                                         atmos_levels=tuple(range(50, 50 + 75 * LEVELS, 75)))
-
-    def field(*lead, of=None):
-        r = torch.randn(*lead, N_LAT, N_LON, device="cuda", generator=g)
-        return r.mul_(300).add_(101325) if of is None else r.mul_(60).add_(of)
-
-    surf = {k: field(1, 1, of=None if base is None else base.surf_vars[k]) for k in SURF}
-    atmos = {k: field(1, 1, LEVELS, of=None if base is None else base.atmos_vars[k]) for k in ATMOS}
-    return Batch(surf, {}, atmos, md)
-
-
-def planes(b: Batch) -> list[torch.Tensor]:
-    return [v[:, -1] for v in (*b.surf_vars.values(), *b.atmos_vars.values())]
+    r = lambda *lead: torch.randn(*lead, N_LAT, N_LON, device="cuda", generator=g)  # noqa: E731
+    return state(lambda *lead: r(*lead).mul_(300).add_(101325)) if base is None else state(lambda *lead: r(*lead).mul_(60), base)
 
 
 def torch_rows(x: torch.Tensor, y: torch.Tensor, thr: torch.Tensor) -> torch.Tensor:
@@ -77,25 +56,6 @@ def torch_rows(x: torch.Tensor, y: torch.Tensor, thr: torch.Tensor) -> torch.Ten
         k, o = (x >= th).sum(dim=0), y >= th
         out[:, :, t].scatter_add_(-1, torch.where(ok, o * (M + 1) + k, 2 * (M + 1)), one)     # (the last bin: invalid points)
     return out[..., :-1].reshape(P, n_lat, thr.shape[1], 2, M + 1)
-
-
-def window_ms(fn, calls: int) -> float:
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(calls):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / calls
-
-
-def captured(fn, calls: int) -> torch.cuda.CUDAGraph:
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        for _ in range(calls):
-            fn()
-    window_ms(graph.replay, 2)
-    return graph
 
 
 def case(M: int, calls: int, repeats: int, plain_lib) -> dict:
@@ -147,26 +107,20 @@ def case(M: int, calls: int, repeats: int, plain_lib) -> dict:
         arms["plain_atomics"] = plain
     for f in (*arms.values(), whole):
         window_ms(f, 3)
-    graphs = {k: captured(f, calls) for k, f in arms.items()}
-    ms = {k: [] for k in (*arms, "scores", "torch")}
-    for _ in range(repeats):                                  # alternate the arms inside every repeat
-        for k, graph in graphs.items():
-            ms[k].append(window_ms(graph.replay, 1) / calls)
-        ms["torch"].append(window_ms(plain_torch, 1))
-        ms["scores"].append(window_ms(whole, calls))
+    ms = alternate({**{k: captured(f, calls) for k, f in arms.items()}, "torch": lambda: window_ms(plain_torch, 1),
+                    "scores": lambda: window_ms(whole, calls)}, repeats)
     read = (M + 1) * N_PLANES * N_LAT * N_LON * 4
-    med = {k: statistics.median(v) for k, v in ms.items()}
+    med, span = ({k: med_min_max(v)[i] for k, v in ms.items()} for i in (0, 1))
     rec = {"members": M, "thresholds": len(THRESHOLDS), "planes": N_PLANES, "grid": [N_LAT, N_LON], "read_GB": read / 1e9,
            "calls_per_window": calls, "repeats": repeats, "off_corner_share_per_threshold": off_corner,
-           "kernel_ms": med["kernel"], "kernel_ms_min_max": [min(ms["kernel"]), max(ms["kernel"])],
+           "kernel_ms": med["kernel"], "kernel_ms_min_max": span["kernel"],
            "kernel_TBps": read / med["kernel"] / 1e9, "ensemble_scores_ms": med["ensemble"],
-           "ensemble_scores_ms_min_max": [min(ms["ensemble"]), max(ms["ensemble"])],
+           "ensemble_scores_ms_min_max": span["ensemble"],
            "ensemble_scores_TBps": read / med["ensemble"] / 1e9, "kernel_over_ensemble_scores": med["kernel"] / med["ensemble"],
-           "probability_scores_call_ms": med["scores"], "torch_ms": med["torch"], "torch_ms_min_max": [min(ms["torch"]), max(ms["torch"])],
+           "probability_scores_call_ms": med["scores"], "torch_ms": med["torch"], "torch_ms_min_max": span["torch"],
            "torch_planes_per_evaluation": group, "torch_over_kernel": med["torch"] / med["kernel"]}
     if plain_lib is not None:
-        rec.update({"plain_atomics_ms": med["plain_atomics"],
-                    "plain_atomics_ms_min_max": [min(ms["plain_atomics"]), max(ms["plain_atomics"])],
+        rec.update({"plain_atomics_ms": med["plain_atomics"], "plain_atomics_ms_min_max": span["plain_atomics"],
                     "plain_atomics_over_ballot": med["plain_atomics"] / med["kernel"]})
     return rec
 

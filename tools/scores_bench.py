@@ -3,52 +3,31 @@
 
     python tools/scores_bench.py [--calls 30] [--repeats 5]
 
-Kernel: the ONE aurora_hip_scores call over all 69 planes (`lib.scores_sums`: two launches), --calls of them captured back
-to back in a hipGraph and replayed between a HIP event pair after warm-up: device time per call = window / calls, free of
-the host's enqueue time; repeated --repeats times (median and spread).  Bytes read = planes x 721 x 1440 x 4 x (2 or 3
-inputs), counted here from the shapes; TB/s = bytes / that time.  Also the same window issued eagerly, for `lib.scores_sums`
-and for `scores()` end to end (checks, cached tables, the call, the finalising torch operations): there the host's enqueue
-rate counts too.  Torch: what a user would write on the same device without this kernel -- per variable, fp64 differences
-and accumulation, a finite mask -- in eager windows (it is device-bound), alternating with the kernel inside each repeat.
+State and timing: tools/verification_bench.py.  Kernel arm: the ONE aurora_hip_scores call over all 69 planes
+(`lib.scores_sums`: two launches), --calls of them per graph.  Bytes read = planes x 721 x 1440 x 4 x (2 or 3 inputs), counted
+here from the shapes; TB/s = bytes / that time.  Eager arms: `lib.scores_sums` and `scores()` end to end (checks, cached
+tables, the call, the finalising torch operations).  Torch: what a user would write on the same device without this kernel
+-- per variable, fp64 differences and accumulation, a finite mask -- in eager windows (it is device-bound).
 Check: both against each other on every plane (the bound of tests/test_gpu_scores.py), and the kernel repeatable bit for
 bit.  The share of a step is `scores()` issued eagerly over the 124 ms of the 0.25-degree step.
 """
 import argparse
 import json
-import statistics
-import sys
-from datetime import datetime
-from pathlib import Path
 
 import numpy as np
 import torch
+from verification_bench import N_LAT, N_LON, N_PLANES, STEP_MS, alternate, captured, med_min_max, planes, state, window_ms
 
-sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
-from aurora_amd import Batch, Metadata, scores  # noqa: E402
-from aurora_amd.engine import lib  # noqa: E402
-from aurora_amd.scores import latitude_weights  # noqa: E402
-
-SURF, ATMOS, LEVELS = ("2t", "10u", "10v", "msl"), ("z", "u", "v", "t", "q"), 13
-N_LAT, N_LON = 721, 1440
-N_PLANES = len(SURF) + len(ATMOS) * LEVELS
-STEP_MS = 124.0
+from aurora_amd import Batch, scores  # (verification_bench has put the repository on sys.path)
+from aurora_amd.engine import lib
+from aurora_amd.scores import latitude_weights
 
 
 def batch(seed: int, base: Batch | None = None, spread: float = 1.0) -> Batch:
-    """Seeded synthetic fields; with `base`, base + spread x noise (a forecast near its truth)."""
+    """Seeded synthetic fields about 280; with `base`, base + spread x noise (a forecast near its truth)."""
     g = torch.Generator(device="cuda").manual_seed(seed)
-    lat = torch.linspace(90, -90, N_LAT, dtype=torch.float64)
-    lon = torch.linspace(0, 360, N_LON + 1, dtype=torch.float64)[:-1]
     r = lambda *s: spread * torch.randn(*s, N_LAT, N_LON, device="cuda", generator=g)  # noqa: E731
-    md = base.metadata if base is not None else Metadata(lat=lat, lon=lon, time=(datetime(2022, 5, 11, 12),),
-                                                         atmos_levels=tuple(range(50, 50 + 75 * LEVELS, 75)))
-    surf = {k: r(1, 1) + (base.surf_vars[k] if base is not None else 280.0) for k in SURF}
-    atmos = {k: r(1, 1, LEVELS) + (base.atmos_vars[k] if base is not None else 280.0) for k in ATMOS}
-    return Batch(surf, {}, atmos, md)
-
-
-def planes(b: Batch) -> list[torch.Tensor]:
-    return [v[:, -1] for v in (*b.surf_vars.values(), *b.atmos_vars.values())]
+    return state(r, base) if base is not None else state(lambda *s: r(*s) + 280.0)
 
 
 def torch_sums(p: torch.Tensor, t: torch.Tensor, c: torch.Tensor | None, w: torch.Tensor) -> torch.Tensor:
@@ -71,16 +50,6 @@ def torch_sums(p: torch.Tensor, t: torch.Tensor, c: torch.Tensor | None, w: torc
     return torch.stack(out, dim=-1).reshape(-1, 8)
 
 
-def window_ms(fn, calls: int) -> float:
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(calls):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / calls
-
-
 def case(pred: Batch, truth: Batch, clim: Batch | None, calls: int, repeats: int) -> dict:
     w = torch.from_numpy(latitude_weights(pred.metadata.lat.numpy())).cuda()
     P, T, C = planes(pred), planes(truth), None if clim is None else planes(clim)
@@ -100,24 +69,15 @@ def case(pred: Batch, truth: Batch, clim: Batch | None, calls: int, repeats: int
     assert worst <= 1e-9, worst
     for f in (kernel, whole, plain):
         window_ms(f, 3)
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        for _ in range(calls):
-            kernel()
-    window_ms(graph.replay, 2)
-    ms = {"kernel": [], "eager": [], "scores": [], "torch": []}
-    for _ in range(repeats):                                  # alternate the arms inside every repeat
-        ms["kernel"].append(window_ms(graph.replay, 1) / calls)
-        ms["eager"].append(window_ms(kernel, calls))
-        ms["torch"].append(window_ms(plain, max(3, calls // 10)))
-        ms["scores"].append(window_ms(whole, calls))
+    ms = alternate({"kernel": captured(kernel, calls), "eager": lambda: window_ms(kernel, calls),
+                    "torch": lambda: window_ms(plain, max(3, calls // 10)), "scores": lambda: window_ms(whole, calls)}, repeats)
     n_in = 2 if clim is None else 3
     read = N_PLANES * N_LAT * N_LON * 4 * n_in
-    med = {k: statistics.median(v) for k, v in ms.items()}
+    med, span = ({k: med_min_max(v)[i] for k, v in ms.items()} for i in (0, 1))
     return {"climatology": clim is not None, "planes": N_PLANES, "grid": [N_LAT, N_LON], "read_GB": read / 1e9,
-            "calls_per_window": calls, "repeats": repeats, "kernel_ms": med["kernel"], "kernel_ms_min_max": [min(ms["kernel"]), max(ms["kernel"])],
+            "calls_per_window": calls, "repeats": repeats, "kernel_ms": med["kernel"], "kernel_ms_min_max": span["kernel"],
             "kernel_TBps": read / med["kernel"] / 1e9, "eager_call_ms": med["eager"], "scores_call_ms": med["scores"], "torch_ms": med["torch"],
-            "torch_ms_min_max": [min(ms["torch"]), max(ms["torch"])], "torch_over_kernel": med["torch"] / med["kernel"],
+            "torch_ms_min_max": span["torch"], "torch_over_kernel": med["torch"] / med["kernel"],
             "share_of_step_percent": 100 * med["scores"] / STEP_MS, "worst_error_over_bound_1e-9": worst / 1e-9}
 
 

@@ -3,52 +3,35 @@
 
     python tools/spectra_bench.py [--calls 20] [--repeats 5]
 
-Kernel: the ONE aurora_hip_spectra call over all 69 planes (`lib.spectra_power`: two launches), --calls of them captured
-back to back in a hipGraph and replayed between a HIP event pair after warm-up: device time per call = window / calls;
-repeated --repeats times (median and spread).  FLOP of the folded transform = 2 x rows x K x 2 K per field with
-K = 721 (rows = 69 x 721; the direct form would be twice that), counted here from the shapes; the fp64 rate is FLOP / that
-time.  Also `spectra()` issued eagerly, end to end.  Torch: what a user would write on the same device without this kernel
+State and timing: tools/verification_bench.py.  Kernel arm: the ONE aurora_hip_spectra call over all 69 planes
+(`lib.spectra_power`: two launches), --calls of them per graph.  FLOP of the folded transform = 2 x rows x K x 2 K per field
+with K = 721 (rows = 69 x 721; the direct form would be twice that), counted here from the shapes; the fp64 rate is FLOP /
+that time.  Eager arm: `spectra()` end to end.  Torch: what a user would write on the same device without this kernel
 -- per variable, the fp64 cast, torch.fft.rfft, |X|^2, the band-weighted row mean; the error spectrum from the difference of
-the two transforms -- in eager windows (it is device-bound), alternating with the kernel inside each repeat: a yardstick
-only.  Check: both against each other on every value (pred and truth relative to the plane's largest; the error field, a
-difference of two transforms on both sides, under the derived bound), and the kernel repeatable bit for bit.  The share of a step is `spectra()` issued eagerly over the 124 ms of the 0.25-degree step.
+the two transforms -- in eager windows (it is device-bound): a yardstick only.  Check: both against each other on every value
+(pred and truth relative to the plane's largest; the error field, a difference of two transforms on both sides, under the
+derived bound), and the kernel repeatable bit for bit.  The share of a step is `spectra()` issued eagerly over the 124 ms of
+the 0.25-degree step.
 """
 import argparse
 import json
-import statistics
-import sys
-from datetime import datetime
-from pathlib import Path
 
 import numpy as np
 import torch
+from verification_bench import N_LAT, N_LON, N_PLANES, STEP_MS, alternate, captured, med_min_max, planes, state, window_ms
 
-sys.path.insert(0, str(Path(__file__).resolve().parents[1]))
-from aurora_amd import Batch, Metadata, spectra  # noqa: E402
-from aurora_amd.engine import lib  # noqa: E402
-from aurora_amd.spectra import band_weights  # noqa: E402
+from aurora_amd import Batch, spectra  # (verification_bench has put the repository on sys.path)
+from aurora_amd.engine import lib
+from aurora_amd.spectra import band_weights
 
-SURF, ATMOS, LEVELS = ("2t", "10u", "10v", "msl"), ("z", "u", "v", "t", "q"), 13
-N_LAT, N_LON = 721, 1440
 K = N_LON // 2 + 1
-N_PLANES = len(SURF) + len(ATMOS) * LEVELS
-STEP_MS = 124.0
 
 
 def batch(seed: int, base: Batch | None = None, spread: float = 1.0) -> Batch:
+    """Seeded synthetic fields about 5e4; with `base`, base + spread x noise."""
     g = torch.Generator(device="cuda").manual_seed(seed)
-    lat = torch.linspace(90, -90, N_LAT, dtype=torch.float64)
-    lon = torch.linspace(0, 360, N_LON + 1, dtype=torch.float64)[:-1]
     r = lambda *s: spread * torch.randn(*s, N_LAT, N_LON, device="cuda", generator=g)  # noqa: E731
-    md = base.metadata if base is not None else Metadata(lat=lat, lon=lon, time=(datetime(2022, 5, 11, 12),),
-                                                         atmos_levels=tuple(range(50, 50 + 75 * LEVELS, 75)))
-    surf = {k: r(1, 1) + (base.surf_vars[k] if base is not None else 5e4) for k in SURF}
-    atmos = {k: r(1, 1, LEVELS) + (base.atmos_vars[k] if base is not None else 5e4) for k in ATMOS}
-    return Batch(surf, {}, atmos, md)
-
-
-def planes(b: Batch) -> list[torch.Tensor]:
-    return [v[:, -1] for v in (*b.surf_vars.values(), *b.atmos_vars.values())]
+    return state(r, base) if base is not None else state(lambda *s: r(*s) + 5e4)
 
 
 def torch_power(p: torch.Tensor, t: torch.Tensor | None, bw: torch.Tensor, ck: torch.Tensor) -> torch.Tensor:
@@ -61,16 +44,6 @@ def torch_power(p: torch.Tensor, t: torch.Tensor | None, bw: torch.Tensor, ck: t
     w = bw * ok[..., None, :]                                                                  # (..., n_bands, n_lat)
     out = [torch.einsum("...bi,...ik->...bk", w, (x.real ** 2 + x.imag ** 2) * ck) / w.sum(dim=-1, keepdim=True) for x in X]
     return torch.stack(out, dim=-3).reshape(-1, len(X), bw.shape[0], K)
-
-
-def window_ms(fn, calls: int) -> float:
-    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    e0.record()
-    for _ in range(calls):
-        fn()
-    e1.record()
-    e1.synchronize()
-    return e0.elapsed_time(e1) / calls
 
 
 def case(pred: Batch, truth: Batch | None, calls: int, repeats: int) -> dict:
@@ -97,24 +70,16 @@ def case(pred: Batch, truth: Batch | None, calls: int, repeats: int) -> dict:
         X = N_LON * np.sqrt(y[:, 2].max(axis=-1, keepdims=True) / 2)
         assert (np.abs(g - y)[:, 2] <= 4 * (2 * X * E + E * E) / N_LON ** 2).all()
     for f in (kernel, whole, plain):
-        window_ms(f, 2)
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph):
-        for _ in range(calls):
-            kernel()
-    window_ms(graph.replay, 1)
-    ms = {"kernel": [], "spectra": [], "torch": []}
-    for _ in range(repeats):                                  # alternate the arms inside every repeat
-        ms["kernel"].append(window_ms(graph.replay, 1) / calls)
-        ms["torch"].append(window_ms(plain, max(3, calls // 4)))
-        ms["spectra"].append(window_ms(whole, calls))
+        window_ms(f, 3)
+    ms = alternate({"kernel": captured(kernel, calls), "torch": lambda: window_ms(plain, max(3, calls // 4)),
+                    "spectra": lambda: window_ms(whole, calls)}, repeats)
     n_fields = 1 if truth is None else 2
     flop = 2.0 * n_fields * N_PLANES * N_LAT * K * (2 * K)
-    med = {k: statistics.median(v) for k, v in ms.items()}
+    med, span = ({k: med_min_max(v)[i] for k, v in ms.items()} for i in (0, 1))
     return {"truth": truth is not None, "planes": N_PLANES, "grid": [N_LAT, N_LON], "folded_GFLOP": flop / 1e9,
             "calls_per_window": calls, "repeats": repeats, "kernel_ms": med["kernel"],
-            "kernel_ms_min_max": [min(ms["kernel"]), max(ms["kernel"])], "fp64_TFLOPs": flop / med["kernel"] / 1e9,
-            "spectra_call_ms": med["spectra"], "torch_ms": med["torch"], "torch_ms_min_max": [min(ms["torch"]), max(ms["torch"])],
+            "kernel_ms_min_max": span["kernel"], "fp64_TFLOPs": flop / med["kernel"] / 1e9,
+            "spectra_call_ms": med["spectra"], "torch_ms": med["torch"], "torch_ms_min_max": span["torch"],
             "torch_over_kernel": med["torch"] / med["kernel"], "share_of_step_percent": 100 * med["spectra"] / STEP_MS,
             "worst_difference_over_plane_max": worst}
 
