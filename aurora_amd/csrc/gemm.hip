@@ -5,7 +5,8 @@
 //   linear_kernel_256<T,4,4>    256 x 256 tile, 4-stage LDS ring     -- native-fp32 mode, bf16 with K < 128
 //   linear_kernel_256pp         the same tile, ping-pong schedule    -- the backbone linears (bf16)
 // and elsewhere: the operand-splitting fp32 kernels (gemm_f32.hip), the fused linear + AdaLN kernel (gemm_ln512.hip), the
-// four-wave hand-scheduled tile (gemm_a4.hip); LinearArgs, swizzles, tile order and epilogue_256* are shared (gemm_tile.h).
+// four-wave hand-scheduled tile (gemm_a4.hip); LinearArgs, swizzles, the preamble's pieces (piece_x / piece_w, dma16, zero_acc),
+// tile order, the epilogue core (biased16, activate16) and epilogue_256* are shared (gemm_tile.h).
 // The description below is the 128 x 128 kernel; the others document their differences in place.
 //
 // One kernel template serves bf16 (v_mfma_f32_16x16x32_bf16) and fp32
@@ -89,12 +90,8 @@ __global__ __launch_bounds__(THREADS, 2) void linear_kernel(const LinearArgs p_i
     for (int r = 0; r < 4; ++r) {
       // wave-uniform LDS base; the hardware adds lane * 16.
       const int base = (r * 256 + wave * 64) * 16;
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)(src_x[r] + koff),
-          (lds_ptr_t)(lds_x(buf) + base), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds(
-          (const __attribute__((address_space(1))) void*)(src_w[r] + koff),
-          (lds_ptr_t)(lds_w(buf) + base), 16, 0, 0);
+      dma16(src_x[r] + koff, lds_x(buf) + base);
+      dma16(src_w[r] + koff, lds_w(buf) + base);
     }
   };
 
@@ -114,10 +111,7 @@ __global__ __launch_bounds__(THREADS, 2) void linear_kernel(const LinearArgs p_i
   }
 
   f32x4 acc[4][4];  // [fn][fm]
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
 
   stage(0, 0);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -160,23 +154,8 @@ __global__ __launch_bounds__(THREADS, 2) void linear_kernel(const LinearArgs p_i
     const int64_t m = m0 + wm * 64 + 16 * fm + i16;
     if (m >= p.M) continue;
     float v[16];
-#pragma unroll
-    for (int fn = 0; fn < 4; ++fn) {
-      v[4 * fn + 0] = acc[fn][fm].x + bias_v[4 * fn + 0];
-      v[4 * fn + 1] = acc[fn][fm].y + bias_v[4 * fn + 1];
-      v[4 * fn + 2] = acc[fn][fm].z + bias_v[4 * fn + 2];
-      v[4 * fn + 3] = acc[fn][fm].w + bias_v[4 * fn + 3];
-    }
-    if (p.act == AURORA_ACT_GELU) {
-#pragma unroll
-      for (int t = 0; t < 16; ++t) v[t] = gelu_for<T>(v[t]);
-    } else if (p.act == ACT_GELU_FAST) {
-#pragma unroll
-      for (int t = 0; t < 16; ++t) v[t] = gelu_erf_fast(v[t]);
-    } else if (p.act == AURORA_ACT_SILU) {
-#pragma unroll
-      for (int t = 0; t < 16; ++t) v[t] = v[t] / (1.0f + expf(-v[t]));
-    }
+    biased16(acc, fm, bias_v, v);
+    activate16<T>(p.act, v);
     if (p.res) {
       const float* rp = p.res + m * p.ldr + nbase;
       if (vec && n_left >= 16) {
@@ -219,9 +198,15 @@ __global__ __launch_bounds__(THREADS, 2) void linear_kernel(const LinearArgs p_i
 // with f = 0,0,3,3 over (r >> 2) & 3 (activations) / (r >> 4) & 3 (interleaved weight rows): the
 // 16 rows of one ds_read_b128 lane group then hit 16 distinct 16-byte slots of the 256-byte bank row.
 // =================================================================================================
-// WN = number of wave columns: 4 -> 256 x 256 tile, 512 threads, one workgroup per CU (4-stage ring, 128 KiB) -- the
-// one in use.  (WN = 2, NST = 3 is a 256 x 128 tile with two workgroups per CU; measured 5-15 % slower on every
-// backbone shape -- co-resident workgroups start together and stay in phase -- and not instantiated.)
+// WN = number of wave columns, NST = ring depth.  Two forms are instantiated, and plan_linear picks between them:
+//   WN = 4, NST = 4: 256 x 256 tile, 512 threads, one workgroup per CU (128 KiB ring) -- K_RING: native-fp32 mode, and
+//                    bf16 launches with fewer than four K-stages;
+//   WN = 2, NST = 3: 256 x 128 tile, 256 threads, two workgroups per CU (three stages of 24 KiB each) -- K_RING_MID, bf16
+//                    only: the few-tile problems where plan_linear's cost model has the smaller tiles fill the chip better.
+//                    (On the full-size backbone shapes this form is 5-15 % slower -- co-resident workgroups start
+//                    together and stay in phase --, which is what the model's per-round costs say.)
+constexpr int RING_LDS = NSTAGE2 * STAGE2;          // WN = 4, NST = 4
+constexpr int MID_LDS = 3 * (BM2 + 128) * ROW2;     // WN = 2, NST = 3
 // (Two co-resident 8-wave workgroups per CU -- a two-stage 64 KiB ring each -- do not fit: the 128 x 64 wave tile alone
 // holds 128 accumulator registers, the kernel needs ~250 of the 256 a wave gets at two waves per SIMD.)
 // PRIO: static s_setprio(1) for the second-dispatched half of the waves (the arbitration loser of every K-stage).
@@ -256,7 +241,7 @@ __global__ __launch_bounds__(128 * WN, 2) void linear_kernel_256(const LinearArg
     const int row = id >> 2, c = id & 3;
     int64_t gm = m0 + row;
     gm = gm < p.M ? gm : p.M - 1;
-    src_x[r] = p.A + gm * p.lda_b + ((c ^ swz2_x(row)) << 4);
+    src_x[r] = p.A + gm * p.lda_b + piece_x(row, c);
   }
 #pragma unroll
   for (int r = 0; r < WP; ++r) {
@@ -264,8 +249,10 @@ __global__ __launch_bounds__(128 * WN, 2) void linear_kernel_256(const LinearArg
     const int row = id >> 2, c = id & 3;
     int gn = n0 + row;
     gn = gn < p.N ? gn : p.N - 1;
-    src_w[r] = p.W + (int64_t)gn * p.ldw_b + ((c ^ swz2_w(row)) << 4);
+    src_w[r] = p.W + (int64_t)gn * p.ldw_b + piece_w(row, c);
   }
+  // (The LDS-DMA builtin spelled out, not dma16: through the helper two s_add of this kernel's prologue trade places, and
+  // the kernel's machine code is pinned -- gemm_tile.h, top.)
   auto stage = [&](int kt) {
     const int64_t koff = (int64_t)kt * ROW2;
     char* base = smem + (kt % NST) * STAGE;
@@ -284,15 +271,15 @@ __global__ __launch_bounds__(128 * WN, 2) void linear_kernel_256(const LinearArg
 #pragma unroll
   for (int f = 0; f < 8; ++f) {
     const int row = wm * 128 + 16 * f + i16;
-    off_x[f] = row * ROW2 + ((g ^ swz2_x(row)) << 4);
+    off_x[f] = row * ROW2 + piece_x(row, g);
   }
 #pragma unroll
   for (int f = 0; f < 4; ++f) {
     const int row = wn * 64 + 16 * (i16 >> 2) + 4 * f + (i16 & 3);
-    off_w[f] = OPER_X + row * ROW2 + ((g ^ swz2_w(row)) << 4);
+    off_w[f] = OPER_X + row * ROW2 + piece_w(row, g);
   }
 
-  f32x4 acc[4][8];  // [fn][fm]
+  f32x4 acc[4][8];  // [fn][fm]  (zeroed in place, not by zero_acc: the helper changes this kernel's register assignment)
 #pragma unroll
   for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -457,38 +444,33 @@ __global__ __launch_bounds__(THREADS2, 2) void linear_kernel_256pp(const LinearA
     gm = gm < p.M ? gm : p.M - 1;
     int gn = n0 + row;
     gn = gn < p.N ? gn : p.N - 1;
-    src_x[r] = p.A + gm * p.lda_b + ((c ^ swz2_x(row)) << 4) + (int64_t)kb * ROW2;
-    src_w[r] = p.W + (int64_t)gn * p.ldw_b + ((c ^ swz2_w(row)) << 4) + (int64_t)kb * ROW2;
+    src_x[r] = p.A + gm * p.lda_b + piece_x(row, c) + (int64_t)kb * ROW2;
+    src_w[r] = p.W + (int64_t)gn * p.ldw_b + piece_w(row, c) + (int64_t)kb * ROW2;
   }
   auto stage = [&](int kt) {
     const int64_t koff = (int64_t)kt * ROW2;
     char* base = smem + (kt & (NSTAGE2 - 1)) * STAGE2;
 #pragma unroll
     for (int r = 0; r < 2; ++r)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src_x[r] + koff),
-                                       (lds_ptr_t)(base + (r * THREADS2 + wave * 64) * 16), 16, 0, 0);
+      dma16(src_x[r] + koff, base + (r * THREADS2 + wave * 64) * 16);
 #pragma unroll
     for (int r = 0; r < 2; ++r)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src_w[r] + koff),
-                                       (lds_ptr_t)(base + OPER2 + (r * THREADS2 + wave * 64) * 16), 16, 0, 0);
+      dma16(src_w[r] + koff, base + OPER2 + (r * THREADS2 + wave * 64) * 16);
   };
   const int i16 = lane & 15, g = lane >> 4;
   int off_x[8], off_w[4];
 #pragma unroll
   for (int f = 0; f < 8; ++f) {
     const int row = wm * 128 + 16 * f + i16;
-    off_x[f] = row * ROW2 + ((g ^ swz2_x(row)) << 4);
+    off_x[f] = row * ROW2 + piece_x(row, g);
   }
 #pragma unroll
   for (int f = 0; f < 4; ++f) {
     const int row = wn * 64 + 16 * (i16 >> 2) + 4 * f + (i16 & 3);
-    off_w[f] = OPER2 + row * ROW2 + ((g ^ swz2_w(row)) << 4);
+    off_w[f] = OPER2 + row * ROW2 + piece_w(row, g);
   }
   f32x4 acc[4][8];  // [fn][fm]
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 8; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   // The lane's 16 bias values, for the epilogue: requested NOW, in front of (and so older than) every piece the counted waits
   // below leave in flight; 16 registers the main loop does not need (201 of 256 before).  In the step 127.6 -> 127.3 ms
   // (profiles/r06_ab_epilogue_parts.log).
@@ -596,8 +578,6 @@ __global__ __launch_bounds__(THREADS2, 2) void linear_kernel_256pp(const LinearA
   epilogue_256<bf16_t>(p, acc, m0, n0, wm, wn, i16, g);
 }
 
-constexpr int MID_LDS = 3 * (BM2 + 128) * ROW2;   // 256 x 128 tiles: three stages of 24 KiB, two workgroups per CU
-
 }  // namespace
 
 }  // namespace aurora
@@ -666,40 +646,36 @@ struct LinearPlan {
 };
 
 int check_call(LinearCall& c) {
-  const int64_t M = c.M, lda = c.lda, ldw = c.ldw, ldc = c.ldc, ldc2 = c.ldc2, ldr = c.ldr, plane_stride = c.plane_stride;
-  const int N = c.N, K = c.K, dtype = c.dtype, act = c.act, plane_heads = c.plane_heads, batch = c.batch;
-  const void *const A = c.A, *const W = c.W, *const C = c.C, *const C2 = c.C2, *const residual = c.residual;
-  int& f32_gemm = c.f32_gemm;
-  AURORA_CHECK_ARG(dtype == AURORA_F32 || dtype == AURORA_BF16, "linear: bad dtype %d", dtype);
-  AURORA_CHECK_ARG(plane_stride == 0 || (dtype == AURORA_BF16 && plane_heads > 0 && N % (64 * plane_heads) == 0 &&
-                                         N <= 192 * plane_heads && plane_stride >= M * 192 && plane_stride % 8 == 0 &&
-                                         C2 == nullptr && residual == nullptr && batch == 1),
+  AURORA_CHECK_ARG(c.dtype == AURORA_F32 || c.dtype == AURORA_BF16, "linear: bad dtype %d", c.dtype);
+  AURORA_CHECK_ARG(c.plane_stride == 0 || (c.dtype == AURORA_BF16 && c.plane_heads > 0 && c.N % (64 * c.plane_heads) == 0 &&
+                                           c.N <= 192 * c.plane_heads && c.plane_stride >= c.M * 192 &&
+                                           c.plane_stride % 8 == 0 && c.C2 == nullptr && c.residual == nullptr && c.batch == 1),
                    "linear: head planes need bf16, N = 64 heads x (1, 2 or 3), planes of >= M rows, one output, no residual");
-  const int pre = c.pre = f32_gemm < 0 ? 0 : f32_gemm & (AURORA_F32_A_SPLIT | AURORA_F32_W_SPLIT | AURORA_F32_C_SPLIT);
-  if (pre) f32_gemm &= ~pre;
-  AURORA_CHECK_ARG(f32_gemm >= -1 && f32_gemm <= 2, "linear: bad fp32 GEMM mode %d", f32_gemm);
-  const int mode = c.mode = f32_gemm < 0 ? default_f32_mode() : f32_gemm;
+  c.pre = c.f32_gemm < 0 ? 0 : c.f32_gemm & (AURORA_F32_A_SPLIT | AURORA_F32_W_SPLIT | AURORA_F32_C_SPLIT);
+  if (c.pre) c.f32_gemm &= ~c.pre;
+  AURORA_CHECK_ARG(c.f32_gemm >= -1 && c.f32_gemm <= 2, "linear: bad fp32 GEMM mode %d", c.f32_gemm);
+  c.mode = c.f32_gemm < 0 ? default_f32_mode() : c.f32_gemm;
   // pre-split operands / output: the two-term ping-pong kernel only.  An A-split launch cannot fall back to three terms
   // (they need the fp32 values), so it takes no guard; a W-split launch with a guard runs iff the guard holds and the
   // caller pairs it with a mode-1 launch on the fp32 weights carrying the same guard, which runs iff it does not.
-  AURORA_CHECK_ARG(!pre || (dtype == AURORA_F32 && mode == 2 && N % 128 == 0 && K % 32 == 0 && K >= 96),
-                   "linear: fp16-pair operands need fp32, mode 2, N %% 128 == 0, K %% 32 == 0, K >= 96 (N=%d K=%d)", N, K);
+  AURORA_CHECK_ARG(!c.pre || (c.dtype == AURORA_F32 && c.mode == 2 && c.N % 128 == 0 && c.K % 32 == 0 && c.K >= 96),
+                   "linear: fp16-pair operands need fp32, mode 2, N %% 128 == 0, K %% 32 == 0, K >= 96 (N=%d K=%d)", c.N, c.K);
   // (an A-split launch WITH a guard is for buffers whose format was itself decided by that guard on the device -- written
   // as pairs by a guarded two-term producer iff it holds, as fp32 by its three-term twin otherwise)
-  AURORA_CHECK_ARG(!(pre & AURORA_F32_A_SPLIT) || (pre & AURORA_F32_W_SPLIT),
+  AURORA_CHECK_ARG(!(c.pre & AURORA_F32_A_SPLIT) || (c.pre & AURORA_F32_W_SPLIT),
                    "linear: a pre-split activation operand needs pre-split weights");
-  AURORA_CHECK_ARG(!(pre & AURORA_F32_C_SPLIT) || (C2 == nullptr && ldc % 32 == 0 && ((uintptr_t)C % 16) == 0),
+  AURORA_CHECK_ARG(!(c.pre & AURORA_F32_C_SPLIT) || (c.C2 == nullptr && c.ldc % 32 == 0 && ((uintptr_t)c.C % 16) == 0),
                    "linear: fp16-pair output needs ldc %% 32 == 0, 16-byte alignment and no second output");
-  if (!(mode == 2 || (mode == 1 && dtype == AURORA_F32))) c.guard = nullptr;
-  AURORA_CHECK_ARG(M > 0 && N > 0 && K > 0, "linear: empty problem M=%lld N=%d K=%d", (long long)M, N, K);
+  if (!(c.mode == 2 || (c.mode == 1 && c.dtype == AURORA_F32))) c.guard = nullptr;
+  AURORA_CHECK_ARG(c.M > 0 && c.N > 0 && c.K > 0, "linear: empty problem M=%lld N=%d K=%d", (long long)c.M, c.N, c.K);
   const int es = c.es();
-  AURORA_CHECK_ARG(((int64_t)K * es) % ROW_BYTES == 0,
-                   "linear: K=%d must be a multiple of %d elements", K, ROW_BYTES / es);
-  AURORA_CHECK_ARG((lda * es) % 16 == 0 && (ldw * es) % 16 == 0 && lda >= K && ldw >= K,
+  AURORA_CHECK_ARG(((int64_t)c.K * es) % ROW_BYTES == 0,
+                   "linear: K=%d must be a multiple of %d elements", c.K, ROW_BYTES / es);
+  AURORA_CHECK_ARG((c.lda * es) % 16 == 0 && (c.ldw * es) % 16 == 0 && c.lda >= c.K && c.ldw >= c.K,
                    "linear: operand strides must be 16-byte multiples >= K");
-  AURORA_CHECK_ARG(((uintptr_t)A % 16) == 0 && ((uintptr_t)W % 16) == 0, "linear: unaligned operand");
-  AURORA_CHECK_ARG(act >= AURORA_ACT_NONE && act <= AURORA_ACT_SILU, "linear: bad activation %d", act);
-  AURORA_CHECK_ARG(C != nullptr && ldc >= N && (!C2 || ldc2 >= N) && (!residual || ldr >= N || ldr == 0),
+  AURORA_CHECK_ARG(((uintptr_t)c.A % 16) == 0 && ((uintptr_t)c.W % 16) == 0, "linear: unaligned operand");
+  AURORA_CHECK_ARG(c.act >= AURORA_ACT_NONE && c.act <= AURORA_ACT_SILU, "linear: bad activation %d", c.act);
+  AURORA_CHECK_ARG(c.C != nullptr && c.ldc >= c.N && (!c.C2 || c.ldc2 >= c.N) && (!c.residual || c.ldr >= c.N || c.ldr == 0),
                    "linear: bad output strides");
   return AURORA_OK;
 }
@@ -772,6 +748,16 @@ LinearPlan plan_linear(const LinearCall& c, int64_t cus) {
   return plan;
 }
 
+// This file's kernels by plan id (from K_TILE_128 on) and dtype (bf16 | fp32; a kernel of one dtype leaves the other
+// empty).  K_A4 lives in gemm_a4.hip and launches itself.
+constexpr LinearKernel KERNELS[K_A4 - K_TILE_128][2] = {
+    /* K_TILE_128  */ {{linear_kernel<bf16_t>, THREADS, 4 * TILE_BYTES}, {linear_kernel<float>, THREADS, 4 * TILE_BYTES}},
+    /* K_RING      */ {{linear_kernel_256<bf16_t, 4, 4>, THREADS2, RING_LDS}, {linear_kernel_256<float, 4, 4>, THREADS2, RING_LDS}},
+    /* K_RING_MID  */ {{linear_kernel_256<bf16_t, 2, 3>, 256, MID_LDS}, {}},
+    /* K_PP        */ {{linear_kernel_256pp<false>, THREADS2, PP_LDS}, {}},
+    /* K_PP_SPLITK */ {{linear_kernel_256pp<true>, THREADS2, PP_LDS}, {}},
+};
+
 int launch_linear(const LinearCall& c, const LinearPlan& plan) {
   const int64_t M = c.M;
   const int N = c.N, K = c.K, es = c.es(), es2 = es == 4 ? 2 : 4;
@@ -799,16 +785,10 @@ int launch_linear(const LinearCall& c, const LinearPlan& plan) {
   p.split = plan.ksplit; p.slabs = plan.ksplit > 1 ? c.ws->slabs : nullptr; p.tickets = plan.ksplit > 1 ? c.ws->tickets : nullptr;
   p.plane_stride = c.plane_stride; p.plane_heads = c.plane_heads;
   if (c.plane_stride) p.vec_store = ((uintptr_t)c.C % 16) == 0 ? 1 : 0;   // (rows of a plane are 128 bytes: ldc plays no part)
-  const dim3 grid((unsigned)p.n_blocks, (unsigned)c.batch);
-  const hipStream_t stream = as_stream(c.stream);
   once_per_device([] {
-    (void)hipFuncSetAttribute((const void*)linear_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TILE_BYTES);
-    (void)hipFuncSetAttribute((const void*)linear_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 4 * TILE_BYTES);
-    (void)hipFuncSetAttribute((const void*)linear_kernel_256<float, 4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, NSTAGE2 * STAGE2);
-    (void)hipFuncSetAttribute((const void*)linear_kernel_256<bf16_t, 4, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, NSTAGE2 * STAGE2);
-    (void)hipFuncSetAttribute((const void*)linear_kernel_256<bf16_t, 2, 3, 0>, hipFuncAttributeMaxDynamicSharedMemorySize, MID_LDS);
-    (void)hipFuncSetAttribute((const void*)linear_kernel_256pp<false>, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS);
-    (void)hipFuncSetAttribute((const void*)linear_kernel_256pp<true>, hipFuncAttributeMaxDynamicSharedMemorySize, PP_LDS);
+    for (const auto& row : KERNELS)
+      for (const LinearKernel& k : row)
+        if (k.fn) (void)hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds_bytes);
   });
   if (plan.kernel < F32_KERNELS) {   // gemm_f32.hip
     if (plan.kernel >= F32_PP) {   // linear_kernel_f32pp counts its own tiles: 128 x 256 (tall: 256 x 128), K-stages of 32
@@ -817,28 +797,19 @@ int launch_linear(const LinearCall& c, const LinearPlan& plan) {
       q.k_tiles = K / 32;
       q.tiles_n = tall ? N / 128 : N / VN;
       q.n_blocks = tall ? ((M + 255) / 256) * q.tiles_n : ((M + VM - 1) / VM) * q.tiles_n;
-      (void)aurora_f32_launch(plan.kernel, &q, (unsigned)q.n_blocks, (unsigned)c.batch, c.stream);
+      if (const int err = aurora_f32_launch(plan.kernel, &q, (unsigned)q.n_blocks, (unsigned)c.batch, c.stream)) return err;
     } else {
-      (void)aurora_f32_launch(plan.kernel, &p, (unsigned)p.n_blocks, (unsigned)c.batch, c.stream);
+      if (const int err = aurora_f32_launch(plan.kernel, &p, (unsigned)p.n_blocks, (unsigned)c.batch, c.stream)) return err;
     }
     if (plan.twin) (void)aurora_f32_launch(F32_THREE, &p, (unsigned)p.n_blocks, (unsigned)c.batch, c.stream);
-    return check_launch("linear");
-  }
-  const bool f32 = c.dtype == AURORA_F32;
-  switch (plan.kernel) {
-    case K_RING_MID: hipLaunchKernelGGL((linear_kernel_256<bf16_t, 2, 3, 0>), grid, dim3(256), MID_LDS, stream, p); break;
-    case K_PP_SPLITK:
-      hipLaunchKernelGGL(linear_kernel_256pp<true>, dim3((unsigned)(p.n_blocks * plan.ksplit)), dim3(THREADS2), PP_LDS, stream, p);
-      break;
-    case K_A4: (void)aurora_a4_launch(&p, (unsigned)p.n_blocks, (unsigned)c.batch, c.stream); break;
-    case K_PP: hipLaunchKernelGGL(linear_kernel_256pp<false>, grid, dim3(THREADS2), PP_LDS, stream, p); break;
-    case K_RING:
-      if (f32) hipLaunchKernelGGL((linear_kernel_256<float, 4, 4>), grid, dim3(THREADS2), NSTAGE2 * STAGE2, stream, p);
-      else hipLaunchKernelGGL((linear_kernel_256<bf16_t, 4, 4>), grid, dim3(THREADS2), NSTAGE2 * STAGE2, stream, p);
-      break;
-    default:
-      if (f32) hipLaunchKernelGGL(linear_kernel<float>, grid, dim3(THREADS), 4 * TILE_BYTES, stream, p);
-      else hipLaunchKernelGGL(linear_kernel<bf16_t>, grid, dim3(THREADS), 4 * TILE_BYTES, stream, p);
+  } else if (plan.kernel == K_A4) {   // gemm_a4.hip
+    (void)aurora_a4_launch(&p, (unsigned)p.n_blocks, (unsigned)c.batch, c.stream);
+  } else {
+    const LinearKernel& k = KERNELS[plan.kernel - K_TILE_128][c.dtype == AURORA_F32];
+    // K_PP_SPLITK (batch 1): one workgroup per K-slice of a tile.  (Any other plan may carry a ksplit of 0 or 1.)
+    const int64_t slices = plan.kernel == K_PP_SPLITK ? plan.ksplit : 1;
+    const dim3 grid((unsigned)(p.n_blocks * slices), (unsigned)c.batch);
+    hipLaunchKernelGGL(k.fn, grid, dim3(k.threads), k.lds_bytes, as_stream(c.stream), p);
   }
   return check_launch("linear");
 }
@@ -847,6 +818,14 @@ int launch_linear(const LinearCall& c, const LinearPlan& plan) {
 int linear_impl(LinearCall c) {
   if (const int err = check_call(c)) return err;
   return launch_linear(c, plan_linear(c, device_cus()));
+}
+
+// The call aurora_hip_linear's arguments describe; the other entry points add what is their own to it.
+LinearCall plain_call(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* C, int64_t ldc, void* C2,
+                      int64_t ldc2, const float* residual, int64_t ldr, int64_t M, int N, int K, int dtype, int act, void* stream) {
+  LinearCall c{A, lda, W, ldw, bias, C, ldc, M, N, K, dtype, stream, act};
+  c.C2 = C2; c.ldc2 = ldc2; c.residual = residual; c.ldr = ldr;
+  return c;
 }
 }  // namespace
 
@@ -871,8 +850,7 @@ extern "C" int aurora_hip_linear_ex(const void* A, int64_t lda, const void* W, i
                                     const float* residual, int64_t ldr, int64_t M, int N, int K,
                                     int dtype, int act, int f32_gemm, const float* guard, float guard_limit,
                                     void* stream) {
-  LinearCall c{A, lda, W, ldw, bias, C, ldc, M, N, K, dtype, stream, act};
-  c.C2 = C2; c.ldc2 = ldc2; c.residual = residual; c.ldr = ldr;
+  LinearCall c = plain_call(A, lda, W, ldw, bias, C, ldc, C2, ldc2, residual, ldr, M, N, K, dtype, act, stream);
   c.f32_gemm = f32_gemm; c.guard = guard; c.guard_limit = guard_limit;
   return linear_impl(c);
 }
@@ -880,7 +858,7 @@ extern "C" int aurora_hip_linear_ex(const void* A, int64_t lda, const void* W, i
 extern "C" int aurora_hip_linear_planes(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* C,
                                         int64_t plane_stride, int heads, int64_t M, int N, int K, int dtype, void* stream) {
   AURORA_CHECK_ARG(plane_stride > 0 && heads > 0, "linear_planes: plane_stride=%lld heads=%d", (long long)plane_stride, heads);
-  LinearCall c{A, lda, W, ldw, bias, C, N, M, N, K, dtype, stream};
+  LinearCall c = plain_call(A, lda, W, ldw, bias, C, N, nullptr, 0, nullptr, 0, M, N, K, dtype, AURORA_ACT_NONE, stream);
   c.plane_stride = plane_stride; c.plane_heads = heads;
   return linear_impl(c);
 }
@@ -892,8 +870,7 @@ extern "C" int aurora_hip_linear_ws(const void* A, int64_t lda, const void* W, i
   AURORA_CHECK_ARG(workspace_bytes >= 0 && n_tickets >= 0 && split >= 0 && ((uintptr_t)workspace % 16) == 0,
                    "linear_ws: bad workspace arguments");
   const SplitWs ws{(float*)workspace, workspace ? workspace_bytes : 0, tickets, tickets ? n_tickets : 0, split};
-  LinearCall c{A, lda, W, ldw, bias, C, ldc, M, N, K, dtype, stream, act};
-  c.C2 = C2; c.ldc2 = ldc2; c.residual = residual; c.ldr = ldr;
+  LinearCall c = plain_call(A, lda, W, ldw, bias, C, ldc, C2, ldc2, residual, ldr, M, N, K, dtype, act, stream);
   c.ws = &ws;
   return linear_impl(c);
 }
@@ -906,7 +883,7 @@ extern "C" int aurora_hip_linear_batched(const void* A, int64_t lda, const void*
   const int es = dtype == AURORA_F32 ? 4 : 2;
   AURORA_CHECK_ARG((stride_a * es) % 16 == 0 && (stride_w * es) % 16 == 0 && (stride_c * es) % 16 == 0 && stride_bias % 4 == 0,
                    "linear_batched: batch strides must keep every problem 16-byte aligned");
-  LinearCall c{A, lda, W, ldw, bias, C, ldc, M, N, K, dtype, stream, act};
+  LinearCall c = plain_call(A, lda, W, ldw, bias, C, ldc, nullptr, 0, nullptr, 0, M, N, K, dtype, act, stream);
   c.f32_gemm = f32_gemm; c.guard = guard; c.guard_limit = guard_limit;
   c.batch = batch; c.stride_a = stride_a; c.stride_w = stride_w; c.stride_bias = stride_bias; c.stride_c = stride_c;
   return linear_impl(c);

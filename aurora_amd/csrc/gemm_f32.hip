@@ -119,8 +119,8 @@ __global__ __launch_bounds__(THREADS2, 2) void linear_kernel_256_f32x3(const Lin
     gm = gm < p.M ? gm : p.M - 1;
     int gn = n0 + row;
     gn = gn < p.N ? gn : p.N - 1;
-    src_x[r] = p.A + gm * p.lda_b + ((c ^ swz2_x(row)) << 4);
-    src_w[r] = p.W + (int64_t)gn * p.ldw_b + ((c ^ swz2_w(row)) << 4);
+    src_x[r] = p.A + gm * p.lda_b + piece_x(row, c);
+    src_w[r] = p.W + (int64_t)gn * p.ldw_b + piece_w(row, c);
   }
   auto stage = [&](int kt) {
     const int64_t koff = (int64_t)kt * ROW2;
@@ -128,10 +128,8 @@ __global__ __launch_bounds__(THREADS2, 2) void linear_kernel_256_f32x3(const Lin
 #pragma unroll
     for (int r = 0; r < 2; ++r) {
       const int off = (r * THREADS2 + wave * 64) * 16;
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src_x[r] + koff),
-                                       (lds_ptr_t)(base + off), 16, 0, 0);
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src_w[r] + koff),
-                                       (lds_ptr_t)(base + OPER2 + off), 16, 0, 0);
+      dma16(src_x[r] + koff, base + off);
+      dma16(src_w[r] + koff, base + OPER2 + off);
     }
   };
 
@@ -140,15 +138,15 @@ __global__ __launch_bounds__(THREADS2, 2) void linear_kernel_256_f32x3(const Lin
 #pragma unroll
   for (int f = 0; f < 8; ++f) {
     const int row = wm * 128 + 16 * f + i16;
-    off_x[f] = row * ROW2 + ((g ^ swz2_x(row)) << 4);
+    off_x[f] = row * ROW2 + piece_x(row, g);
   }
 #pragma unroll
   for (int f = 0; f < 4; ++f) {
     const int row = wn * 64 + 16 * (i16 >> 2) + 4 * f + (i16 & 3);
-    off_w[f] = OPER2 + row * ROW2 + ((g ^ swz2_w(row)) << 4);
+    off_w[f] = OPER2 + row * ROW2 + piece_w(row, g);
   }
 
-  f32x4 acc[4][8];  // [fn][fm]
+  f32x4 acc[4][8];  // [fn][fm]  (zeroed in place, not by zero_acc: the helper changes the code of the three-term form)
 #pragma unroll
   for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -319,12 +317,10 @@ __global__ __launch_bounds__(VTHREADS, 2) void linear_kernel_f32pp(const LinearA
     char* base = smem + (kt % VNST) * VSTAGE;
 #pragma unroll
     for (int r = 0; r < XP; ++r)   // wave-uniform LDS address; the hardware adds lane * 16
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src_x[r] + koff),
-                                       (lds_ptr_t)(base + (r * VTHREADS + wave * 64) * 16), 16, 0, 0);
+      dma16(src_x[r] + koff, base + (r * VTHREADS + wave * 64) * 16);
 #pragma unroll
     for (int r = 0; r < WP; ++r)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src_w[r] + koff),
-                                       (lds_ptr_t)(base + OPX + (r * VTHREADS + wave * 64) * 16), 16, 0, 0);
+      dma16(src_w[r] + koff, base + OPX + (r * VTHREADS + wave * 64) * 16);
   };
   // fragment read offsets.  Lane group g multiplies k = 8g..8g+7 of the stage: as fp32 that is chunks 2g and 2g + 1 of the
   // row, in the fp16-pair layout chunk g (high halves) and chunk g + 4 (remainders) -- the same k order either way, so
@@ -343,10 +339,7 @@ __global__ __launch_bounds__(VTHREADS, 2) void linear_kernel_f32pp(const LinearA
     }
   }
   f32x4 acc[4][4];  // [fn][fm]
-#pragma unroll
-  for (int a = 0; a < 4; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
 
   const int nt = p.k_tiles;   // K / 32, >= 3 (dispatch)
   stage(0);
@@ -434,17 +427,8 @@ __global__ __launch_bounds__(VTHREADS, 2) void linear_kernel_f32pp(const LinearA
         v[4 * fn + 2] = fmaf(acc[fn][fm].z, 0.015625f, bias_v[4 * fn + 2]);
         v[4 * fn + 3] = fmaf(acc[fn][fm].w, 0.015625f, bias_v[4 * fn + 3]);
       }
-      if (p.act == AURORA_ACT_GELU || p.act == ACT_GELU_FAST) {
-#pragma unroll
-        for (int t = 0; t < 16; t += 2) {
-          const f32x2_hw r = gelu_erf_fast2(f32x2_hw{v[t], v[t + 1]});
-          v[t] = r.x;
-          v[t + 1] = r.y;
-        }
-      } else if (p.act == AURORA_ACT_SILU) {
-#pragma unroll
-        for (int t = 0; t < 16; ++t) v[t] = v[t] / (1.0f + expf(-v[t]));
-      }
+      if (p.act == AURORA_ACT_GELU || p.act == ACT_GELU_FAST) gelu_fast16x2(v);
+      else if (p.act == AURORA_ACT_SILU) silu16(v);
       const int row = 16 * fm + i16, sw = row & 7;
       char* lrow = mine + row * 256;
       if (p.out_split) {
@@ -485,17 +469,8 @@ __global__ __launch_bounds__(VTHREADS, 2) void linear_kernel_f32pp(const LinearA
       v[4 * fn + 2] = fmaf(acc[fn][fm].z, 0.015625f, bias_v[4 * fn + 2]);
       v[4 * fn + 3] = fmaf(acc[fn][fm].w, 0.015625f, bias_v[4 * fn + 3]);
     }
-    if (p.act == AURORA_ACT_GELU || p.act == ACT_GELU_FAST) {
-#pragma unroll
-      for (int t = 0; t < 16; t += 2) {
-        const f32x2_hw r = gelu_erf_fast2(f32x2_hw{v[t], v[t + 1]});
-        v[t] = r.x;
-        v[t + 1] = r.y;
-      }
-    } else if (p.act == AURORA_ACT_SILU) {
-#pragma unroll
-      for (int t = 0; t < 16; ++t) v[t] = v[t] / (1.0f + expf(-v[t]));
-    }
+    if (p.act == AURORA_ACT_GELU || p.act == ACT_GELU_FAST) gelu_fast16x2(v);
+    else if (p.act == AURORA_ACT_SILU) silu16(v);
     if (p.res) {
       const float* rp = p.res + m * p.ldr + nbase;
       if (vec) {
@@ -554,28 +529,28 @@ __global__ __launch_bounds__(256) void split_f16_kernel(const float* __restrict_
 
 using namespace aurora;
 
+namespace {
+// This file's GEMM kernels by F32Kernel id.
+constexpr LinearKernel F32_TABLE[F32_KERNELS] = {
+    /* F32_THREE      */ {linear_kernel_256_f32x3<3>, THREADS2, NSTAGE2 * STAGE2},
+    /* F32_TWO        */ {linear_kernel_256_f32x3<2>, THREADS2, NSTAGE2 * STAGE2},
+    /* F32_PP         */ {linear_kernel_f32pp<false, false>, VTHREADS, VNST * VSTAGE},
+    /* F32_PP_W       */ {linear_kernel_f32pp<false, true>, VTHREADS, VNST * VSTAGE},
+    /* F32_PP_AW      */ {linear_kernel_f32pp<true, true>, VTHREADS, VNST * VSTAGE},
+    /* F32_PP_W_TALL  */ {linear_kernel_f32pp<false, true, true>, VTHREADS, VNST * VSTAGE},
+    /* F32_PP_AW_TALL */ {linear_kernel_f32pp<true, true, true>, VTHREADS, VNST * VSTAGE},
+};
+}  // namespace
+
 extern "C" __attribute__((visibility("hidden"))) int aurora_f32_launch(int kernel, const void* linear_args, unsigned n_blocks,
                                                                       unsigned batch, void* stream) {
   const LinearArgs& p = *static_cast<const LinearArgs*>(linear_args);
+  AURORA_CHECK_ARG(kernel >= 0 && kernel < F32_KERNELS, "linear: no fp32 kernel %d", kernel);
   once_per_device([] {
-    (void)hipFuncSetAttribute((const void*)linear_kernel_256_f32x3<3>, hipFuncAttributeMaxDynamicSharedMemorySize, NSTAGE2 * STAGE2);
-    (void)hipFuncSetAttribute((const void*)linear_kernel_256_f32x3<2>, hipFuncAttributeMaxDynamicSharedMemorySize, NSTAGE2 * STAGE2);
-    (void)hipFuncSetAttribute((const void*)linear_kernel_f32pp<false, false>, hipFuncAttributeMaxDynamicSharedMemorySize, VNST * VSTAGE);
-    (void)hipFuncSetAttribute((const void*)linear_kernel_f32pp<false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, VNST * VSTAGE);
-    (void)hipFuncSetAttribute((const void*)linear_kernel_f32pp<true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, VNST * VSTAGE);
-    (void)hipFuncSetAttribute((const void*)linear_kernel_f32pp<true, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, VNST * VSTAGE);
-    (void)hipFuncSetAttribute((const void*)linear_kernel_f32pp<false, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, VNST * VSTAGE);
+    for (const LinearKernel& k : F32_TABLE) (void)hipFuncSetAttribute((const void*)k.fn, hipFuncAttributeMaxDynamicSharedMemorySize, k.lds_bytes);
   });
-  const dim3 g(n_blocks, batch), b(THREADS2), bv(VTHREADS);
-  switch (kernel) {
-    case F32_THREE: hipLaunchKernelGGL(linear_kernel_256_f32x3<3>, g, b, NSTAGE2 * STAGE2, as_stream(stream), p); break;
-    case F32_TWO: hipLaunchKernelGGL(linear_kernel_256_f32x3<2>, g, b, NSTAGE2 * STAGE2, as_stream(stream), p); break;
-    case F32_PP: hipLaunchKernelGGL((linear_kernel_f32pp<false, false>), g, bv, VNST * VSTAGE, as_stream(stream), p); break;
-    case F32_PP_W: hipLaunchKernelGGL((linear_kernel_f32pp<false, true>), g, bv, VNST * VSTAGE, as_stream(stream), p); break;
-    case F32_PP_AW: hipLaunchKernelGGL((linear_kernel_f32pp<true, true>), g, bv, VNST * VSTAGE, as_stream(stream), p); break;
-    case F32_PP_W_TALL: hipLaunchKernelGGL((linear_kernel_f32pp<false, true, true>), g, bv, VNST * VSTAGE, as_stream(stream), p); break;
-    default: hipLaunchKernelGGL((linear_kernel_f32pp<true, true, true>), g, bv, VNST * VSTAGE, as_stream(stream), p); break;
-  }
+  const LinearKernel& k = F32_TABLE[kernel];
+  hipLaunchKernelGGL(k.fn, dim3(n_blocks, batch), dim3(k.threads), k.lds_bytes, as_stream(stream), p);
   return 0;
 }
 

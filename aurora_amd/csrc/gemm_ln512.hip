@@ -56,41 +56,36 @@ __global__ __launch_bounds__(FTHREADS, 2) void linear_ln512_kernel(const LinearL
     const int row = tid >> 2, c = tid & 3;
     int64_t gm = m0 + row;
     gm = gm < p.M ? gm : p.M - 1;
-    src_x = p.A + gm * p.lda_b + ((c ^ swz2_x(row)) << 4);
+    src_x = p.A + gm * p.lda_b + piece_x(row, c);
   }
 #pragma unroll
   for (int r = 0; r < 4; ++r) {
     const int id = r * FTHREADS + tid;
     const int row = id >> 2, c = id & 3;
-    src_w[r] = p.W + (int64_t)row * p.ldw_b + ((c ^ swz2_w(row)) << 4);
+    src_w[r] = p.W + (int64_t)row * p.ldw_b + piece_w(row, c);
   }
   auto stage = [&](int kt) {
     const int64_t koff = (int64_t)kt * ROW2;
     char* base = smem + (kt % FNST) * FSTAGE;
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src_x + koff),
-                                     (lds_ptr_t)(base + (wave * 64) * 16), 16, 0, 0);
+    dma16(src_x + koff, base + (wave * 64) * 16);
 #pragma unroll
     for (int r = 0; r < 4; ++r)
-      __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(src_w[r] + koff),
-                                       (lds_ptr_t)(base + FOPER_X + (r * FTHREADS + wave * 64) * 16), 16, 0, 0);
+      dma16(src_w[r] + koff, base + FOPER_X + (r * FTHREADS + wave * 64) * 16);
   };
   const int i16 = lane & 15, g = lane >> 4;
   int off_x[4], off_w[8];
 #pragma unroll
   for (int f = 0; f < 4; ++f) {
     const int row = wm * 64 + 16 * f + i16;
-    off_x[f] = row * ROW2 + ((g ^ swz2_x(row)) << 4);
+    off_x[f] = row * ROW2 + piece_x(row, g);
   }
 #pragma unroll
   for (int f = 0; f < 8; ++f) {   // weight rows interleaved so that a lane ends up with 32 CONSECUTIVE output features
     const int row = wn * 128 + 32 * (i16 >> 2) + 4 * f + (i16 & 3);
-    off_w[f] = FOPER_X + row * ROW2 + ((g ^ swz2_w(row)) << 4);
+    off_w[f] = FOPER_X + row * ROW2 + piece_w(row, g);
   }
   f32x4 acc[8][4];  // [fn][fm]: features wn*128 + 32g + 4fn .. +3 of row wm*64 + 16fm + i16
-#pragma unroll
-  for (int a = 0; a < 8; ++a)
-#pragma unroll
-    for (int b = 0; b < 4; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+  zero_acc(acc);
   const int nt = p.k_tiles;   // >= 3 (dispatch)
   stage(0);
   stage(1);

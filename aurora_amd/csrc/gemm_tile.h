@@ -1,6 +1,11 @@
 // What the GEMM translation units share (gemm.hip, gemm_f32.hip, gemm_ln512.hip, gemm_a4.hip): the launch arguments, the LDS
-// images' swizzles, the tile order, the MFMA step and the epilogues of the 256 x 256 tiles.  Each kernel family documents its
-// own tile in its own file; the 128 x 128 kernel's description at the top of gemm.hip introduces the layouts used here.
+// images' swizzles, the pieces of the tile preamble (piece_x / piece_w: where a 16-byte piece lies in its row, for the staging
+// source and the fragment read alike; dma16; zero_acc), the tile order, the MFMA step, the core of every epilogue (biased16, the
+// activations over a lane's 16 values, activate16) and the epilogues of the 256 x 256 tiles.  Each kernel family documents
+// its own tile in its own file; the 128 x 128 kernel's description at the top of gemm.hip introduces the layouts used here.
+// Every helper here is held to "the kernels compile to the same machine code as with the text in place"
+// (tools/compare_isa.py): where one did not -- zero_acc and dma16 in linear_kernel_256, zero_acc in linear_kernel_256_f32x3 --
+// the kernel keeps the text; so does the packed ladder of epilogue_256_bf16_coalesced (the four-wave kernel's branch layout).
 #pragma once
 
 #include "common.h"
@@ -126,6 +131,24 @@ __device__ __forceinline__ int swz2(int a) { return ((a >> 1) & 1) * 3; }
 __device__ __forceinline__ int swz2_x(int row) { return swz2((row >> 2) & 3); }
 __device__ __forceinline__ int swz2_w(int row) { return swz2((row >> 4) & 3); }
 
+// ---- the tile preamble of the kernels that stage 64-byte rows (ROW2) by LDS-DMA ----
+// Byte offset of 16-byte piece c inside row `row` of an operand image (the swizzle of "Big-tile kernel", gemm.hip).  LDS-DMA
+// writes lane-linearly, so the thread that stages a piece applies it to its SOURCE address and the lane that multiplies the
+// piece to its fragment read: both sides through these two, or neither.
+__device__ __forceinline__ int piece_x(int row, int c) { return (c ^ swz2_x(row)) << 4; }
+__device__ __forceinline__ int piece_w(int row, int c) { return (c ^ swz2_w(row)) << 4; }
+// One LDS-DMA piece: 16 bytes per lane from `src` to the wave-uniform LDS address `dst` + lane * 16 (the hardware adds it).
+__device__ __forceinline__ void dma16(const char* src, char* dst) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)src, (lds_ptr_t)dst, 16, 0, 0);
+}
+template <int FN, int FM>
+__device__ __forceinline__ void zero_acc(f32x4 (&acc)[FN][FM]) {
+#pragma unroll
+  for (int a = 0; a < FN; ++a)
+#pragma unroll
+    for (int b = 0; b < FM; ++b) acc[a][b] = f32x4{0.f, 0.f, 0.f, 0.f};
+}
+
 // XCD-aware, L2-friendly tile order shared by both kernels: each XCD owns a contiguous range of
 // logical ids; inside it n-tiles are visited in groups of `GN` with the m-tile index in between,
 // so the workgroups that run together on one XCD share a few activation tiles AND a few weight
@@ -151,6 +174,44 @@ __device__ __forceinline__ void tile_of_block(uint32_t bid, uint32_t nb, uint32_
   }
 }
 
+// ---- what every epilogue starts with: the lane's 16 consecutive features of row fragment fm, and the activation ----
+template <int FMS>
+__device__ __forceinline__ void biased16(const f32x4 (&acc)[4][FMS], int fm, const float (&bias_v)[16], float (&v)[16]) {
+#pragma unroll
+  for (int fn = 0; fn < 4; ++fn) {
+    v[4 * fn + 0] = acc[fn][fm].x + bias_v[4 * fn + 0];
+    v[4 * fn + 1] = acc[fn][fm].y + bias_v[4 * fn + 1];
+    v[4 * fn + 2] = acc[fn][fm].z + bias_v[4 * fn + 2];
+    v[4 * fn + 3] = acc[fn][fm].w + bias_v[4 * fn + 3];
+  }
+}
+// Activations over those 16 values (x2: as packed pairs).
+__device__ __forceinline__ void silu16(float (&v)[16]) {
+#pragma unroll
+  for (int t = 0; t < 16; ++t) v[t] = v[t] / (1.0f + expf(-v[t]));
+}
+__device__ __forceinline__ void gelu_fast16x2(float (&v)[16]) {
+#pragma unroll
+  for (int t = 0; t < 16; t += 2) {
+    const f32x2_hw r = gelu_erf_fast2(f32x2_hw{v[t], v[t + 1]});
+    v[t] = r.x;
+    v[t + 1] = r.y;
+  }
+}
+// the ladder of the direct epilogues (the coalesced ones choose packed forms in place)
+template <typename T>
+__device__ __forceinline__ void activate16(int act, float (&v)[16]) {
+  if (act == AURORA_ACT_GELU) {
+#pragma unroll
+    for (int t = 0; t < 16; ++t) v[t] = gelu_for<T>(v[t]);
+  } else if (act == ACT_GELU_FAST) {
+#pragma unroll
+    for (int t = 0; t < 16; ++t) v[t] = gelu_erf_fast(v[t]);
+  } else if (act == AURORA_ACT_SILU) {
+    silu16(v);
+  }
+}
+
 // Epilogue of the 256 x 256 kernels: a lane owns a row x 16 consecutive features (same ownership as the
 // 128 x 128 kernel) -> bias, activation, fp32 residual, dual-dtype 16-byte stores.
 template <typename T>
@@ -169,23 +230,8 @@ __device__ __forceinline__ void epilogue_256(const LinearArgs& p, f32x4 (&acc)[4
     const int64_t m = m0 + wm * 128 + 16 * fm + i16;
     if (m >= p.M) continue;
     float v[16];
-#pragma unroll
-    for (int fn = 0; fn < 4; ++fn) {
-      v[4 * fn + 0] = acc[fn][fm].x + bias_v[4 * fn + 0];
-      v[4 * fn + 1] = acc[fn][fm].y + bias_v[4 * fn + 1];
-      v[4 * fn + 2] = acc[fn][fm].z + bias_v[4 * fn + 2];
-      v[4 * fn + 3] = acc[fn][fm].w + bias_v[4 * fn + 3];
-    }
-    if (p.act == AURORA_ACT_GELU) {
-#pragma unroll
-      for (int t = 0; t < 16; ++t) v[t] = gelu_for<T>(v[t]);
-    } else if (p.act == ACT_GELU_FAST) {
-#pragma unroll
-      for (int t = 0; t < 16; ++t) v[t] = gelu_erf_fast(v[t]);
-    } else if (p.act == AURORA_ACT_SILU) {
-#pragma unroll
-      for (int t = 0; t < 16; ++t) v[t] = v[t] / (1.0f + expf(-v[t]));
-    }
+    biased16(acc, fm, bias_v, v);
+    activate16<T>(p.act, v);
     if (p.res) {
       const float* rp = p.res + m * p.ldr + nbase;
       if (vec && n_left >= 16) {
@@ -234,13 +280,7 @@ __device__ __forceinline__ void epilogue_256_bf16_coalesced(const LinearArgs& p,
     for (int f = 0; f < 8 / PARTS; ++f) {
       const int fm = part * (8 / PARTS) + f;
       float v[16];
-#pragma unroll
-      for (int fn = 0; fn < 4; ++fn) {
-        v[4 * fn + 0] = acc[fn][fm].x + bias_v[4 * fn + 0];
-        v[4 * fn + 1] = acc[fn][fm].y + bias_v[4 * fn + 1];
-        v[4 * fn + 2] = acc[fn][fm].z + bias_v[4 * fn + 2];
-        v[4 * fn + 3] = acc[fn][fm].w + bias_v[4 * fn + 3];
-      }
+      biased16(acc, fm, bias_v, v);
       if (p.act == AURORA_ACT_GELU) {   // (packed form of gelu_for<bf16_t>: same operations, same bits)
 #pragma unroll
         for (int t = 0; t < 16; t += 2) {
@@ -287,13 +327,7 @@ __device__ __forceinline__ void epilogue_256_f32_coalesced(const LinearArgs& p, 
     for (int f = 0; f < 4; ++f) {
       const int fm = 4 * half + f;
       float v[16];
-#pragma unroll
-      for (int fn = 0; fn < 4; ++fn) {
-        v[4 * fn + 0] = acc[fn][fm].x + bias_v[4 * fn + 0];
-        v[4 * fn + 1] = acc[fn][fm].y + bias_v[4 * fn + 1];
-        v[4 * fn + 2] = acc[fn][fm].z + bias_v[4 * fn + 2];
-        v[4 * fn + 3] = acc[fn][fm].w + bias_v[4 * fn + 3];
-      }
+      biased16(acc, fm, bias_v, v);
       if (p.act == AURORA_ACT_GELU) {
 #pragma unroll
         for (int t = 0; t < 16; ++t) v[t] = gelu_for<float>(v[t]);
@@ -305,8 +339,7 @@ __device__ __forceinline__ void epilogue_256_f32_coalesced(const LinearArgs& p, 
           v[t + 1] = r.y;
         }
       } else if (p.act == AURORA_ACT_SILU) {
-#pragma unroll
-        for (int t = 0; t < 16; ++t) v[t] = v[t] / (1.0f + expf(-v[t]));
+        silu16(v);
       }
       if (p.res) {
         const int64_t m = m0 + wm * 128 + 16 * fm + i16;
@@ -332,6 +365,10 @@ __device__ __forceinline__ void epilogue_256_f32_coalesced(const LinearArgs& p, 
     }
   }
 }
+
+// A row of a dispatcher's kernel table (gemm.hip by plan id, gemm_f32.hip by F32Kernel): what a launch and the per-device
+// LDS attribute need.
+struct LinearKernel { void (*fn)(LinearArgs); unsigned threads; int lds_bytes; };
 
 // The fp32 kernels of gemm_f32.hip, as the dispatcher of gemm.hip names them to aurora_f32_launch.
 // F32_PP*: linear_kernel_f32pp with pre-split weights (W), pre-split activations and weights (AW), 256 x 128 tiles (TALL).

@@ -435,6 +435,24 @@ def test_linear_ws_split_k_equals_the_unsplit_product(M, N, K, split, epilogue):
     assert (d <= plain.float().abs() * 2.0 ** -7 + 1e-6).all()     # at most one bf16 ulp apart
 
 
+def test_linear_ws_with_k_too_short_to_split_is_the_plain_linear():
+    """A requested split that K cannot carry (K = 64 < 128: the plan's slice count comes out 0) launches the un-split kernel
+    over every tile: the same kernel as aurora_hip_linear takes for the shape, so the same bits, and the tickets stay zero."""
+    L = lib()
+    M, N, K = 1024, 256, 64
+    ad, wd = rnd(M, K, seed=1).bfloat16().to(DEV), rnd(N, K, seed=2, scale=K ** -0.5).bfloat16().to(DEV)
+    bd = rnd(N, seed=3).float().to(DEV)
+    ws = torch.empty(2 * 4 * 256 * 256 * 4, dtype=torch.uint8, device=DEV)
+    tickets = torch.zeros(64, dtype=torch.int32, device=DEV)
+    out = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=DEV)
+    plain = torch.full((M, N), float("nan"), dtype=torch.bfloat16, device=DEV)
+    L.linear_ws(ad, wd, bd, out, ws, tickets, split=2)
+    L.linear(ad, wd, bd, plain)
+    torch.cuda.synchronize()
+    assert int(tickets.abs().sum()) == 0
+    assert not out.float().isnan().any() and torch.equal(out, plain)
+
+
 def test_linear_broadcast_residual_row_and_strided_views():
     L = lib()
     M, N, K = 200, 96, 64
