@@ -3,7 +3,8 @@
 Public surface = the reference's (aurora/__init__.py:3-29).  The cyclone tracker (aurora/tracker.py) follows a roll-out
 without moving the predictions off the device: only its search windows travel (aurora_amd/tracker.py).  `scores` verifies a
 prediction against truth on the device (aurora_amd/scores.py) and `ensemble_scores` an ensemble of them (CRPS, spread, rank
-histogram: aurora_amd/ensemble.py), and `spectra` gives the zonal power spectra of a prediction, of the truth and of the error
+histogram: aurora_amd/ensemble.py) while `ensemble_quantiles` gives its per-point quantile maps -- median, 10 % / 90 %,
+interquartile range -- and the map of the truth's rank among the members (aurora_amd/quantiles.py), and `spectra` gives the zonal power spectra of a prediction, of the truth and of the error
 (aurora_amd/spectra.py), and `event_scores` the contingency tables and the fractions skill score of threshold exceedances
 (aurora_amd/events.py), and `probability_scores` the Brier score, reliability diagram and ROC of an ensemble's event
 probabilities (aurora_amd/probability.py), and `FieldStats` accumulates per-point statistics over the steps of a roll-out or
@@ -30,6 +31,7 @@ from aurora_amd.model.aurora import (
     AuroraWave,
 )
 from aurora_amd.probability import ProbabilityScores, probability_scores
+from aurora_amd.quantiles import EnsembleQuantiles, ensemble_quantiles
 from aurora_amd.rollout import rollout, write_rollout
 from aurora_amd.scores import Scores, scores
 from aurora_amd.spectra import Spectra, spectra
@@ -52,6 +54,8 @@ __all__ = [
     "Scores",
     "ensemble_scores",
     "EnsembleScores",
+    "ensemble_quantiles",
+    "EnsembleQuantiles",
     "spectra",
     "Spectra",
     "event_scores",

@@ -1,6 +1,7 @@
-"""What the verification front ends (`scores`, `ensemble_scores`, `event_scores`, `probability_scores`, `spectra`,
-`FieldStats`, `diagnostics`) share: coordinates and grid checks, the selection of the fields of a call, the decision where
-they are reduced, the layout accessor, threshold tables, the fixed summation trees and the cache of small device tables.
+"""What the verification front ends (`scores`, `ensemble_scores`, `ensemble_quantiles`, `event_scores`, `probability_scores`,
+`spectra`, `FieldStats`, `diagnostics`) share: coordinates and grid checks, the selection of the fields of a call, the
+decision where they are reduced, the layout accessor, threshold tables, the fixed summation trees and the cache of small
+device tables.
 
 Plain functions.  The name a message starts with (`fn`) and the words for the operands are arguments, so every module's
 messages are made here with its own wording; tests/test_verification_messages.py pins them."""
@@ -219,6 +220,63 @@ def select_members(fn: str, members, truth: Batch, only=None):
                              f"{MAX_MEMBERS}, got {sorted(sizes | {M})}")
         member_fields = [[f[m:m + 1] for f in member_fields[0]] for m in range(M)]
     return names, truth_fields, member_fields, layout_of(names, truth_fields)
+
+
+def select_samples(fn: str, members, truth: Optional[Batch] = None):
+    """M members as in `select_members`, with or WITHOUT a truth (`ensemble_quantiles`): without one the grid and the shapes
+    of members[0] are what the others must match, and with one `truth` is one more operand of the same shapes.  (names, truth's
+    fields or None, M lists of member fields, the layout)."""
+    if truth is not None and not isinstance(truth, Batch):
+        raise TypeError(f"{fn}: truth must be a Batch or None, got {type(truth).__name__}")
+    one_batch = isinstance(members, Batch)
+    batches = [members] if one_batch else list(members)
+    for m, b in enumerate(batches):
+        if not isinstance(b, Batch):
+            raise TypeError(f"{fn}: members[{m}] must be a Batch, got {type(b).__name__}")
+    who = ["members"] if one_batch else [f"members[{m}]" for m in range(len(batches))]
+    if not one_batch and not 2 <= len(batches) <= MAX_MEMBERS:
+        raise ValueError(f"{fn}: members must hold 2 to {MAX_MEMBERS} batches, got {len(batches)}")
+    operands = list(zip(who, batches)) + ([("truth", truth)] if truth is not None else [])
+    first_name, first = operands[0]
+    for w, b in operands:
+        check_vector_grid(fn, b, w, band="quantiles")
+    for w, b in operands[1:]:
+        check_same_coordinates(fn, b, first, w, first_name, w)
+    n_lat, n_lon = first.metadata.lat.shape[0], first.metadata.lon.shape[0]
+
+    names, fields = [], [[] for _ in operands]
+    for group in GROUPS:
+        for k in getattr(first, group):
+            if not all(k in getattr(b, group) for _, b in operands):
+                continue
+            if k in names:
+                raise ValueError(f"{fn}: {k!r} is both a surface and an atmospheric variable")
+            names.append(k)
+            for slot, (w, b) in enumerate(operands):
+                f = getattr(b, group)[k]
+                check_field(fn, f, w, group, k, n_lat, n_lon)
+                f = f[:, -1]
+                if w == "truth" and one_batch:
+                    if f.shape[0] != 1:
+                        raise ValueError(f"{fn}: members is ONE Batch (its batch elements are the members), so truth must "
+                                         f"have batch size 1, got {f.shape[0]} for {k!r}; pass a sequence of Batches for a "
+                                         "batch of ensembles")
+                    if f.shape[1:] != fields[0][-1].shape[1:]:
+                        raise ValueError(f"{fn}: members and truth differ in shape for {k!r}: {tuple(fields[0][-1].shape)} "
+                                         f"against {tuple(f.shape)}")
+                elif slot and f.shape != fields[0][-1].shape:
+                    raise _differ(fn, w, first_name, k, f.shape, fields[0][-1].shape)
+                fields[slot].append(f)
+    member_fields = fields[:len(batches)]
+    truth_fields = fields[-1] if truth is not None else None
+    if one_batch and names:                                # the batch elements of the one Batch are the members
+        sizes = {f.shape[0] for f in member_fields[0]}
+        M = sizes.pop()
+        if sizes or not 2 <= M <= MAX_MEMBERS:
+            raise ValueError(f"{fn}: members is ONE Batch, whose batch size is the number of members: it must be 2 to "
+                             f"{MAX_MEMBERS}, got {sorted(sizes | {M})}")
+        member_fields = [[f[m:m + 1] for f in member_fields[0]] for m in range(M)]
+    return names, truth_fields, member_fields, layout_of(names, member_fields[0])
 
 
 def by_variable(layout: Layout, t: torch.Tensor) -> dict[str, torch.Tensor]:

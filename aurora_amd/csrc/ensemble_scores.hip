@@ -11,7 +11,7 @@
 // `m < M` guard, so every register index is a compile-time constant (no scratch).  Per point:
 //   pass 1, member order   sd = sum d_m (e = sd / M), any x_m == y (a tie); the point is valid iff sd is finite
 //                          (a NaN or an infinity in any input makes some d_m, and with it sd, NaN or infinite);
-//   sort                   the fp32 values x_m by Batcher's odd-even merge network (fp32 min / max; x -> x - y is
+//   sort                   the fp32 values x_m by Batcher's odd-even merge network (sortnet.h; x -> x - y is
 //                          monotone, so the d_m are then ascending too);
 //   pass 2, sorted order   sum |d_(k)|, sum (2k - M - 1) d_(k)  (= M^2 g / 2), sum (d_(k) - e)^2, and for the
 //                          histogram one ballot per k: the number of valid points of the wave with x_(k) < y, added
@@ -23,9 +23,8 @@
 // the bucket; the integer counts ride along (they are wave sums from the start: popcounts of ballots).
 // ensemble_finish_kernel is the tree's second launch and also turns the cumulative counts #{points : x_(k) < y} into
 // the M + 1 bins.  No atomics of any kind.
-#include <utility>
-
 #include "planes.h"
+#include "sortnet.h"
 
 namespace aurora {
 namespace {
@@ -33,11 +32,6 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kSlots = kSumSlots;
-constexpr int kMaxMembers = 64;
-
-constexpr int bucket_of(int n_members) {
-  return n_members <= 4 ? 4 : n_members <= 8 ? 8 : n_members <= 16 ? 16 : n_members <= 32 ? 32 : 64;
-}
 // Target size of a row chunk (elements of one input): that of scores.hip where a point is cheap, smaller chunks (more
 // workgroups to balance) where a point costs hundreds of instructions.
 constexpr int chunk_elems(int bucket) { return bucket <= 8 ? 40960 : 16384; }
@@ -45,51 +39,6 @@ constexpr int chunk_elems(int bucket) { return bucket <= 8 ? 40960 : 16384; }
 // Bytes of one workgroup's partial: eight doubles, then bucket + 2 counts (valid points, #{x_(k) < y} for k < bucket,
 // ties) padded to whole doubles.
 __host__ __device__ constexpr int64_t partial_bytes(int bucket) { return kSlots * 8 + ((bucket + 2) * 4 + 7) / 8 * 8; }
-
-// ---- Batcher's odd-even merge sort for N = 2^k inputs as a table of compare-exchange pairs ----------------------------
-template <int N> struct SortNet {
-  int count = 0;
-  unsigned char lo[N * 11] = {}, hi[N * 11] = {};        // (N log N (log N + 1) / 4 pairs at most: 672 for N = 64)
-};
-template <int N> constexpr SortNet<N> make_sort_net() {
-  SortNet<N> s{};
-  for (int p = 1; p < N; p *= 2)
-    for (int k = p; k >= 1; k /= 2)
-      for (int j = k % p; j <= N - 1 - k; j += 2 * k)
-        for (int i = 0; i < k && i <= N - j - k - 1; ++i)
-          if ((i + j) / (2 * p) == (i + j + k) / (2 * p)) {
-            s.lo[s.count] = (unsigned char)(i + j);
-            s.hi[s.count] = (unsigned char)(i + j + k);
-            ++s.count;
-          }
-  return s;
-}
-template <int N> struct Net { static constexpr SortNet<N> v = make_sort_net<N>(); };
-
-// The network runs on integer keys: key(x) = bits ^ (0x7fffffff where the sign is set) orders as the floats do (-0 just
-// below +0, +inf above every finite value), is its own inverse, and integer min / max need no NaN handling (fp32 min /
-// max cost a canonicalising instruction per operand here, which doubled the network).
-__device__ __forceinline__ int sort_key(int bits) { return bits ^ ((bits >> 31) & 0x7fffffff); }
-
-template <int N, int I> __device__ __forceinline__ int compare_exchange(int (&v)[N]) {
-  constexpr int a = Net<N>::v.lo[I], b = Net<N>::v.hi[I];
-  const int lo = min(v[a], v[b]), hi = max(v[a], v[b]);
-  v[a] = lo;
-  v[b] = hi;
-  return 0;
-}
-template <int N, size_t... I> __device__ __forceinline__ void sort_keys(int (&v)[N], std::index_sequence<I...>) {
-  const int done[] = {compare_exchange<N, (int)I>(v)...};
-  (void)done;
-}
-template <int N> __device__ __forceinline__ void sort_ascending(float (&v)[N]) {
-  int key[N];
-#pragma unroll
-  for (int k = 0; k < N; ++k) key[k] = sort_key(__float_as_int(v[k]));
-  sort_keys<N>(key, std::make_index_sequence<Net<N>::v.count>{});
-#pragma unroll
-  for (int k = 0; k < N; ++k) v[k] = __int_as_float(sort_key(key[k]));
-}
 
 // ---- accumulators ---------------------------------------------------------------------------------------------------
 struct Acc {                                    // per lane

@@ -129,6 +129,8 @@ _SIGNATURES = {
     "aurora_hip_ensemble_scores_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int]),
     "aurora_hip_ensemble_scores": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                            c_void_p]),
+    "aurora_hip_ensemble_quantiles": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p,
+                                              c_void_p]),
     "aurora_hip_spectra_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "aurora_hip_spectra": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, ctypes.c_size_t, c_void_p]),
@@ -849,6 +851,50 @@ def ensemble_scores_sums(members: list[list[torch.Tensor]], truth: list[torch.Te
             _check(load().aurora_hip_ensemble_scores(base, base + 8 * M * n, M, n, n_lat, n_lon, _ptr(row_w), _ptr(sums),
                                                      _ptr(hist), _ptr(workspace), _stream()))
     return sums, hist
+
+
+# ---- quantile maps of an ensemble (aurora_hip_ensemble_quantiles) --------------------------------------------------------
+QUANTILES_MAX = 8
+
+
+def ensemble_quantiles(members: list[list[torch.Tensor]], truth: Optional[list[torch.Tensor]], q,
+                       out: Optional[torch.Tensor] = None,
+                       rank_out: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, Optional[torch.Tensor]]:
+    """The quantile maps of include/aurora_hip.h for every plane of M members, and with `truth` the map of its rank among them,
+    in ONE aurora_hip_ensemble_quantiles call (one launch): an (n_planes, Q, n_lat, n_lon) fp32 tensor and an (n_planes, n_lat,
+    n_lon) int8 tensor (None without a truth) on the device.
+
+    members: M lists (2 <= M <= 64), each like `truth`: fp32 (..., n_lat, n_lon) tensors on one device with row-major
+    contiguous planes (any leading strides, any 4-byte plane alignment) and the same leading shapes; truth: one such list or
+    None; q: 1 to 8 finite values in [0, 1] on the HOST (the library forms the indices and passes them by value); out / rank_out:
+    contiguous tensors of the result's shape and dtype on that device to write into (any 4-byte / 1-byte alignment), or None
+    to allocate them.  The plane-pointer table is cached by address as in `scores_sums`.  Nothing but the outputs is allocated
+    and the host does not wait for the device."""
+    M = len(members)
+    assert 2 <= M <= ENSEMBLE_MAX_MEMBERS, f"ensemble_quantiles: members must hold 2..{ENSEMBLE_MAX_MEMBERS} lists, got {M}"
+    assert members[0], "ensemble_quantiles: no fields"
+    qs = np.ascontiguousarray(q, dtype=np.float64).reshape(-1)
+    Q = qs.shape[0]
+    assert 1 <= Q <= QUANTILES_MAX, f"ensemble_quantiles: 1..{QUANTILES_MAX} values of q, got {Q}"
+    assert rank_out is None or truth is not None, "ensemble_quantiles: rank_out without a truth"
+    dev, (n_lat, n_lon) = members[0][0].device, members[0][0].shape[-2:]
+    lists = [(f"member {m}", fs) for m, fs in enumerate(members)] + ([("truth", truth)] if truth is not None else [])
+    n, addresses = _plane_lists("ensemble_quantiles", lists, dev, "the first member", n_lat, n_lon)
+    for what, t, shape, dt in (("out", out, (n, Q, n_lat, n_lon), torch.float32), ("rank_out", rank_out, (n, n_lat, n_lon), torch.int8)):
+        assert t is None or (t.device == dev and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()), \
+            f"ensemble_quantiles: {what} must be a contiguous {dt} tensor of {shape} on the device of the members"
+    if out is None:
+        out = torch.empty(n, Q, n_lat, n_lon, dtype=torch.float32, device=dev)
+    if truth is not None and rank_out is None:
+        rank_out = torch.empty(n, n_lat, n_lon, dtype=torch.int8, device=dev)
+    with torch.cuda.device(dev):
+        table = _plane_table("ensemble_quantiles", tuple(addresses), dev)
+        base = table.data_ptr()
+        moved = float(n * n_lat * n_lon * (4 * M + 4 * Q + (5 if truth is not None else 0)))
+        with _Timed("ensemble_quantiles", moved):
+            _check(load().aurora_hip_ensemble_quantiles(base, base + 8 * M * n if truth is not None else None, M, n, n_lat, n_lon,
+                                                        qs.ctypes.data, Q, _ptr(out), _ptr(rank_out), _stream()))
+    return out, rank_out
 
 
 # ---- zonal power spectra (aurora_hip_spectra) -------------------------------------------------------------------------

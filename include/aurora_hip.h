@@ -721,6 +721,31 @@ int aurora_hip_ensemble_scores(const float* const* member_planes, const float* c
                                int n_lat, int n_lon, const double* row_w, double* sums, int64_t* hist, void* workspace,
                                void* stream);
 
+/* ---- quantile maps of an ENSEMBLE and the truth's rank map on the device (aurora_amd.ensemble_quantiles: the median, the
+ * 10 % and 90 % maps, where the truth fell outside the ensemble; not in the reference) --------------------------------------
+ * Planes and plane-pointer arrays as for aurora_hip_ensemble_scores; M = n_members, 2 <= M <= 64.  Per point of plane k:
+ *   validity  the point is VALID where all M members are finite; at an invalid point every quantile is NaN.
+ *   order     the M fp32 values are put in ascending order x_(0) <= ... <= x_(M-1) of the integer key
+ *             bits ^ ((bits >> 31) & 0x7fffffff): the order of the floats, with -0 below +0.
+ *   index     for each q[i], 1 <= n_q <= 8 finite values in [0, 1], any order, repeats allowed: h = (M - 1) q[i] in fp64,
+ *             j = min(floor(h), M - 1), g = h - j, hi = min(j + 1, M - 1).  The LIBRARY forms (j, g) from the HOST array q
+ *             and passes them to the kernel by value; nothing is uploaded.
+ *   value     quantiles[((k n_q + i) n_lat + row) n_lon + col] = (float)(a + g (b - a)), a = (double)x_(j), b = (double)x_(hi):
+ *             the subtraction, the product and the sum are each rounded to fp64 on their own (no fused multiply-add), and
+ *             the result is rounded to fp32 once.  With g = 0 that is x_(j): q = 0 gives the minimum, q = 1 the maximum.
+ *   rank      with truth_planes: rank[(k n_lat + row) n_lon + col] = #{m : x_m < y}, the values compared as they are stored
+ *             (the rule of the rank histogram of aurora_hip_ensemble_scores); -1 where y or any member is not finite.  The
+ *             quantiles do not depend on the truth.
+ * truth_planes and rank are both given or both NULL.  quantiles: n_planes x n_q x n_lat x n_lon device floats, 4-byte
+ * aligned; rank: n_planes x n_lat x n_lon device int8.  16-byte loads and stores are used for M <= 16 where every member
+ * pointer, the truth pointer, the plane's output pointers and n_lon allow; the same bits are written either way.  The outputs
+ * must not overlap the inputs, which are not modified.  n_planes = 0 is a no-op.  ONE launch: no workspace, no atomics, no
+ * reduction across threads, no host synchronisation, no allocation: capturable in a hipGraph.  A plane's maps depend on its
+ * own values, M and q alone, not on the order of the members and not on the other planes of the call. */
+int aurora_hip_ensemble_quantiles(const float* const* member_planes, const float* const* truth_planes, int n_members,
+                                  int n_planes, int n_lat, int n_lon, const double* q, int n_q, float* quantiles, int8_t* rank,
+                                  void* stream);
+
 /* ---- zonal power spectra of a forecast on the device (aurora_amd.spectra; not in the reference) ---------------------------
  * Planes as above, N = n_lon, K = N / 2 + 1 wavenumbers.  For row i of a plane
  *   X_i[k] = sum_n x_i[n] exp(-2 pi i k n / N),  k = 0 .. K-1,        P_i[k] = c_k |X_i[k]|^2 / N^2,
