@@ -758,9 +758,19 @@ constexpr LinearKernel KERNELS[K_A4 - K_TILE_128][2] = {
     /* K_PP_SPLITK */ {{linear_kernel_256pp<true>, THREADS2, PP_LDS}, {}},
 };
 
+// LinearArgs::vec_store of a checked call: 1 iff every row piece of C, C2 and the residual is 16-byte aligned.
+int vec_store_of(const LinearCall& c) {
+  const int es = c.es(), es2 = es == 4 ? 2 : 4;
+  if (c.plane_stride) return ((uintptr_t)c.C % 16) == 0 ? 1 : 0;   // (rows of a plane are 128 bytes: ldc plays no part)
+  bool vec = ((uintptr_t)c.C % 16) == 0 && (c.ldc * es) % 16 == 0;
+  if (c.C2) vec = vec && ((uintptr_t)c.C2 % 16) == 0 && (c.ldc2 * es2) % 16 == 0;
+  if (c.residual) vec = vec && ((uintptr_t)c.residual % 16) == 0 && (c.ldr * 4) % 16 == 0;
+  return vec ? 1 : 0;
+}
+
 int launch_linear(const LinearCall& c, const LinearPlan& plan) {
   const int64_t M = c.M;
-  const int N = c.N, K = c.K, es = c.es(), es2 = es == 4 ? 2 : 4;
+  const int N = c.N, K = c.K, es = c.es();
   const bool split = c.dtype == AURORA_F32 && c.mode >= 1, big = plan.bm == BM2;
   LinearArgs p;
   p.A = (const char*)c.A; p.lda_b = c.lda * es;
@@ -771,10 +781,7 @@ int launch_linear(const LinearCall& c, const LinearPlan& plan) {
   p.M = M; p.N = N; p.k_tiles = (int)(((int64_t)K * es) / plan.rowb); p.act = c.act;
   p.tiles_n = (N + plan.bn - 1) / plan.bn;
   p.n_blocks = ((M + plan.bm - 1) / plan.bm) * p.tiles_n;
-  bool vec = ((uintptr_t)c.C % 16) == 0 && (c.ldc * es) % 16 == 0;
-  if (c.C2) vec = vec && ((uintptr_t)c.C2 % 16) == 0 && (c.ldc2 * es2) % 16 == 0;
-  if (c.residual) vec = vec && ((uintptr_t)c.residual % 16) == 0 && (c.ldr * 4) % 16 == 0;
-  p.vec_store = vec ? 1 : 0;
+  p.vec_store = vec_store_of(c);
   if (split && big && c.act == AURORA_ACT_GELU) p.act = ACT_GELU_FAST;
   p.guard = split ? c.guard : nullptr;
   p.guard_limit = c.guard_limit;
@@ -784,7 +791,6 @@ int launch_linear(const LinearCall& c, const LinearPlan& plan) {
   p.bs_a = c.stride_a * es; p.bs_w = c.stride_w * es; p.bs_c = c.stride_c * es; p.bs_bias = c.stride_bias;
   p.split = plan.ksplit; p.slabs = plan.ksplit > 1 ? c.ws->slabs : nullptr; p.tickets = plan.ksplit > 1 ? c.ws->tickets : nullptr;
   p.plane_stride = c.plane_stride; p.plane_heads = c.plane_heads;
-  if (c.plane_stride) p.vec_store = ((uintptr_t)c.C % 16) == 0 ? 1 : 0;   // (rows of a plane are 128 bytes: ldc plays no part)
   once_per_device([] {
     for (const auto& row : KERNELS)
       for (const LinearKernel& k : row)
@@ -819,6 +825,14 @@ int linear_impl(LinearCall c) {
   if (const int err = check_call(c)) return err;
   return launch_linear(c, plan_linear(c, device_cus()));
 }
+
+// The ids aurora_hip_linear_plan reports are this dispatcher's own.
+static_assert(F32_THREE == AURORA_PLAN_F32_THREE && F32_TWO == AURORA_PLAN_F32_TWO && F32_PP == AURORA_PLAN_F32_PP &&
+              F32_PP_W == AURORA_PLAN_F32_PP_W && F32_PP_AW == AURORA_PLAN_F32_PP_AW &&
+              F32_PP_W_TALL == AURORA_PLAN_F32_PP_W_TALL && F32_PP_AW_TALL == AURORA_PLAN_F32_PP_AW_TALL &&
+              K_TILE_128 == AURORA_PLAN_TILE128 && K_RING == AURORA_PLAN_RING && K_RING_MID == AURORA_PLAN_RING_MID &&
+              K_PP == AURORA_PLAN_PP && K_PP_SPLITK == AURORA_PLAN_PP_SPLITK && K_A4 == AURORA_PLAN_A4,
+              "include/aurora_hip.h: AURORA_PLAN_* out of step with the dispatcher's kernel ids");
 
 // The call aurora_hip_linear's arguments describe; the other entry points add what is their own to it.
 LinearCall plain_call(const void* A, int64_t lda, const void* W, int64_t ldw, const float* bias, void* C, int64_t ldc, void* C2,
@@ -887,4 +901,33 @@ extern "C" int aurora_hip_linear_batched(const void* A, int64_t lda, const void*
   c.f32_gemm = f32_gemm; c.guard = guard; c.guard_limit = guard_limit;
   c.batch = batch; c.stride_a = stride_a; c.stride_w = stride_w; c.stride_bias = stride_bias; c.stride_c = stride_c;
   return linear_impl(c);
+}
+
+// What linear_impl would launch for a call, without launching: check_call and plan_linear as the launch path runs them.
+extern "C" int aurora_hip_linear_plan(int64_t M, int N, int K, int dtype, int f32_gemm, int has_guard, int batch, int64_t ldc,
+                                      int64_t c_addr, int64_t ldc2, int64_t c2_addr, int64_t ldr, int64_t residual_addr,
+                                      int64_t workspace_bytes, int n_tickets, int split, int64_t plane_stride, int plane_heads,
+                                      int cus, int32_t* plan_out) {
+  AURORA_CHECK_ARG(plan_out != nullptr && c_addr != 0 && cus >= 0 && batch >= 1, "linear_plan: bad query");
+  // Operands as the tightest legal call has them (16-byte aligned, rows of K elements); of the output addresses only the
+  // alignment is read.  The guard is never dereferenced here.
+  static const float guard_word = 0.f;
+  LinearCall c = plain_call((const void*)16, K, (const void*)16, K, nullptr, (void*)(uintptr_t)c_addr, ldc,
+                            (void*)(uintptr_t)c2_addr, ldc2, (const float*)(uintptr_t)residual_addr, ldr, M, N, K, dtype,
+                            AURORA_ACT_NONE, nullptr);
+  c.f32_gemm = f32_gemm; c.guard = has_guard ? &guard_word : nullptr;
+  c.batch = batch;
+  const SplitWs ws{nullptr, workspace_bytes, nullptr, n_tickets, split};
+  if (workspace_bytes >= 0) c.ws = &ws;
+  c.plane_stride = plane_stride; c.plane_heads = plane_heads;
+  if (const int err = check_call(c)) return err;
+  const LinearPlan plan = plan_linear(c, cus > 0 ? cus : device_cus());
+  const bool pp = plan.kernel >= F32_PP && plan.kernel < F32_KERNELS, tall = pp && plan.kernel >= F32_PP_W_TALL;
+  plan_out[0] = plan.kernel;
+  plan_out[1] = plan.twin ? 1 : 0;
+  plan_out[2] = pp ? (tall ? 256 : VM) : plan.bm;    // (linear_kernel_f32pp counts its own tiles: launch_linear)
+  plan_out[3] = pp ? (tall ? 128 : VN) : plan.bn;
+  plan_out[4] = plan.ksplit;
+  plan_out[5] = vec_store_of(c);
+  return AURORA_OK;
 }

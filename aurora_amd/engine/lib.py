@@ -11,7 +11,7 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
-from collections import OrderedDict
+from collections import OrderedDict, namedtuple
 from ctypes import c_float, c_int, c_int32, c_int64, c_void_p
 from pathlib import Path
 from typing import Optional
@@ -63,6 +63,9 @@ _SIGNATURES = {
     "aurora_hip_linear_batched": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int64, c_int,
                                           c_int, c_int, c_int, c_int, c_void_p, c_float, c_int, c_int64, c_int64, c_int64,
                                           c_int64, c_void_p]),
+    "aurora_hip_linear_plan": (c_int, [c_int64, c_int, c_int, c_int, c_int, c_int, c_int, c_int64, c_int64, c_int64, c_int64,
+                                       c_int64, c_int64, c_int64, c_int, c_int, c_int64, c_int, c_int,
+                                       ctypes.POINTER(c_int32)]),
     "aurora_hip_absmax": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "aurora_hip_absmax_fold": (c_int, [c_void_p, c_int64, c_void_p, c_void_p]),
     "aurora_hip_zero_words": (c_int, [c_void_p, c_int, c_void_p]),
@@ -407,6 +410,59 @@ def linear_ws(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], ou
                                            workspace.numel() * workspace.element_size(), _ptr(tickets), tickets.numel(), split,
                                            _stream()))
     return out
+
+
+def linear_batched(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], out: torch.Tensor, *,
+                   act: int = ACT_NONE) -> torch.Tensor:
+    """out[g] = act(a[g] @ w[g].T + bias[g]) for every problem g of a strided batch, in one launch (aurora_hip_linear_batched).
+    a (G, M, K), w (G, N, K), out (G, M, N): 3-D views with unit inner stride, any row and batch strides the C entry takes;
+    a batch of one (or an `expand`ed operand: batch stride 0) shares that operand.  bias (G, >= N) fp32 or None.  The fp32
+    mode and guard are this thread's (`f32_gemm`), as for `linear`."""
+    assert a.dim() == w.dim() == out.dim() == 3 and a.dtype == w.dtype == out.dtype, (a.dtype, w.dtype, out.dtype)
+    G, M, N, K = out.shape[0], a.shape[1], w.shape[1], a.shape[2]
+    assert w.shape[2] == K and out.shape[1] == M and out.shape[2] == N
+    for t in (a, w):
+        assert t.shape[0] in (1, G) and t.stride(2) == 1, (t.shape, t.stride())
+    assert out.stride(2) == 1
+    bstride = lambda t: 0 if t.shape[0] == 1 else t.stride(0)  # noqa: E731
+    lda, _ = _rows(a[0])
+    ldw, _ = _rows(w[0])
+    ldc, _ = _rows(out[0])
+    sb = 0
+    if bias is not None:
+        assert bias.dtype == torch.float32 and bias.dim() == 2 and bias.shape[0] in (1, G) and bias.shape[1] >= N
+        assert bias.stride(1) == 1
+        sb = bstride(bias)
+    name = "linear_bf16" if a.dtype == torch.bfloat16 else "linear_f32"
+    with _Timed(name, 2.0 * G * M * N * K):
+        mode, guard, limit = _f32_state()
+        _check(load().aurora_hip_linear_batched(_ptr(a), lda, _ptr(w), ldw, _ptr(bias), _ptr(out), ldc, M, N, K,
+                                                dtype_code(a.dtype), act, mode, _ptr(guard), limit, G, bstride(a),
+                                                bstride(w), sb, bstride(out), _stream()))
+    return out
+
+
+PLAN_KERNELS = ("f32_three", "f32_two", "f32_pp", "f32_pp_w", "f32_pp_aw", "f32_pp_w_tall", "f32_pp_aw_tall", "tile128",
+                "ring", "ring_mid", "pp", "pp_splitk", "a4")   # include/aurora_hip.h: AURORA_PLAN_*, in order
+LinearPlan = namedtuple("LinearPlan", "kernel twin bm bn ksplit vec_store")
+
+
+def linear_plan(M: int, N: int, K: int, dtype: torch.dtype, *, f32_gemm: int = -1, guard: bool = False, batch: int = 1,
+                ldc: Optional[int] = None, c_offset: int = 0, ldc2: Optional[int] = None, c2_offset: int = 0,
+                ldr: Optional[int] = None, residual_offset: int = 0, workspace_bytes: int = -1, n_tickets: int = 0,
+                split: int = 0, plane_stride: int = 0, plane_heads: int = 0, cus: int = 0) -> LinearPlan:
+    """What `linear` and its siblings would launch for such a call, without launching (aurora_hip_linear_plan): the kernel by
+    name (PLAN_KERNELS), whether a guarded two-term launch brings its three-term twin, the tile, the K split and whether
+    the 16-byte store paths are taken.  f32_gemm as aurora_hip_linear_ex (-1: the process default; F32_* flags OR-ed in);
+    ldc2 / ldr None = no second output / no residual (ldr = 0: a broadcast row); the *_offset are the bytes by which a base
+    address misses 16-byte alignment; workspace_bytes >= 0 describes a `linear_ws` call.  cus = 0 plans for the current
+    device and needs one; any other count is host arithmetic only."""
+    out = (c_int32 * 6)()
+    _check(load().aurora_hip_linear_plan(M, N, K, dtype_code(dtype), f32_gemm, int(guard), batch, N if ldc is None else ldc,
+                                         16 + c_offset, ldc2 or 0, 0 if ldc2 is None else 16 + c2_offset, ldr or 0,
+                                         0 if ldr is None else 16 + residual_offset, workspace_bytes, n_tickets, split,
+                                         plane_stride, plane_heads, cus, out))
+    return LinearPlan(PLAN_KERNELS[out[0]], bool(out[1]), out[2], out[3], out[4], bool(out[5]))
 
 
 def linear_layernorm(a: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], gain: Optional[torch.Tensor],

@@ -89,6 +89,36 @@ int aurora_hip_linear_batched(const void* A, int64_t lda, const void* W, int64_t
                               float guard_limit, int batch, int64_t stride_a, int64_t stride_w, int64_t stride_bias,
                               int64_t stride_c, void* stream);
 
+/* Which kernel the calls above would launch, without launching anything: the argument checks and the dispatch decision of
+ * the launch path itself, run on a description of the call.  Host arithmetic only; with cus > 0 no device is needed.
+ *   f32_gemm                  : as aurora_hip_linear_ex, AURORA_F32_*_SPLIT bits included; has_guard: a guard word is given.
+ *   ldc / c_addr              : leading dimension and address of C -- of the address only its value modulo 16 is read (a
+ *                               real address, or 16 + a byte offset); likewise ldc2 / c2_addr and ldr / residual_addr,
+ *                               address 0 = no second output / no residual.
+ *   workspace_bytes, n_tickets, split : the scratch of aurora_hip_linear_ws; workspace_bytes < 0 = a call without scratch.
+ *   plane_stride, plane_heads : aurora_hip_linear_planes (0, 0 otherwise).
+ *   cus                       : compute units of the device to plan for; 0 = the current device's.
+ * plan_out[0..5]: kernel (AURORA_PLAN_*), 1 if a guarded two-term launch is followed by its three-term twin, tile rows,
+ * tile columns, K slices (0 or 1: none), and whether the kernels would use their 16-byte stores (all of C, C2 and the
+ * residual 16-byte aligned row by row).  Returns what the call itself would return for bad arguments. */
+#define AURORA_PLAN_F32_THREE 0
+#define AURORA_PLAN_F32_TWO 1
+#define AURORA_PLAN_F32_PP 2
+#define AURORA_PLAN_F32_PP_W 3
+#define AURORA_PLAN_F32_PP_AW 4
+#define AURORA_PLAN_F32_PP_W_TALL 5
+#define AURORA_PLAN_F32_PP_AW_TALL 6
+#define AURORA_PLAN_TILE128 7
+#define AURORA_PLAN_RING 8
+#define AURORA_PLAN_RING_MID 9
+#define AURORA_PLAN_PP 10
+#define AURORA_PLAN_PP_SPLITK 11
+#define AURORA_PLAN_A4 12
+int aurora_hip_linear_plan(int64_t M, int N, int K, int dtype, int f32_gemm, int has_guard, int batch, int64_t ldc,
+                           int64_t c_addr, int64_t ldc2, int64_t c2_addr, int64_t ldr, int64_t residual_addr,
+                           int64_t workspace_bytes, int n_tickets, int split, int64_t plane_stride, int plane_heads,
+                           int cus, int32_t* plan_out);
+
 /* aurora_hip_linear for callers that can lend scratch memory: a bf16 linear with few 256 x 256 tiles and a long K (the
  * per-rank shapes of a latitude band at the coarse backbone stages, swin3d.py:59-66,153,169 at M = 2,160: 72 tiles on
  * 256 CUs, K = 8192) is then split along K inside ONE launch -- every tile's K range is cut into `split` slices, one

@@ -99,3 +99,30 @@ def test_constants_and_new_argument_contracts_match_the_header(built):
     assert L.aurora_hip_linear_ws(16, 8192, 16, 8192, None, 16, 2048, None, 0, None, 0, 2160, 2048, 8192, shim.BF16, 0,
                                   8, 1 << 26, 16, 4096, 0, None) == -1 and b"workspace" in err()
     assert L.aurora_hip_zero_words(None, 4, None) == -1 and L.aurora_hip_zero_words(16, 65, None) == -1
+    # the dispatch query: kernel ids as the header numbers them; with an explicit CU count it is host arithmetic, runs the
+    # launch path's own argument check (the same refusals) and tells the store path from the alignment it is given
+    import torch
+
+    plan_ids = {k.lower(): int(v) for k, v in re.findall(r"#define AURORA_PLAN_(\w+) (\d+)", header)}
+    assert plan_ids == {name: i for i, name in enumerate(shim.PLAN_KERNELS)} and len(plan_ids) == 13
+    bf, f32 = torch.bfloat16, torch.float32
+    assert shim.linear_plan(300, 200, 128, bf, cus=256) == ("tile128", False, 128, 128, 1, True)
+    assert shim.linear_plan(8193, 1024, 512, bf, cus=256)[:4] == ("pp", False, 256, 256)
+    assert shim.linear_plan(8193, 512, 128, bf, cus=256)[:4] == ("ring_mid", False, 256, 128)
+    assert shim.linear_plan(8193, 1024, 32, f32, f32_gemm=0, cus=256).kernel == "ring"
+    assert shim.linear_plan(2160, 2048, 8192, bf, workspace_bytes=72 * 3 * 256 * 256 * 4, n_tickets=72, cus=256)[::4] == ("pp_splitk", 3)
+    assert shim.linear_plan(2160, 2048, 8192, bf, workspace_bytes=72 * 3 * 256 * 256 * 4, n_tickets=71, cus=256).ksplit == 1
+    assert shim.linear_plan(300, 256, 96, f32, f32_gemm=2, guard=True, cus=256)[:4] == ("f32_pp", True, 128, 256)
+    assert shim.linear_plan(300, 384, 96, f32, f32_gemm=2 | shim.F32_W_SPLIT, cus=256)[:4] == ("f32_pp_w_tall", False, 256, 128)
+    assert shim.linear_plan(300, 256, 64, f32, f32_gemm=1, cus=256).kernel == "f32_three"
+    for kw in (dict(ldc=259), dict(c_offset=4), dict(ldc2=257), dict(ldr=258), dict(ldr=256, residual_offset=8)):
+        assert not shim.linear_plan(300, 256, 64, f32, f32_gemm=1, cus=256, **kw).vec_store, kw
+    assert shim.linear_plan(300, 256, 64, f32, f32_gemm=1, ldc=260, ldc2=264, ldr=0, cus=256).vec_store
+    with pytest.raises(ValueError, match="multiple"):
+        shim.linear_plan(4, 8, 40, f32, cus=256)
+    with pytest.raises(ValueError, match="pre-split weights"):
+        shim.linear_plan(512, 512, 128, f32, f32_gemm=2 | shim.F32_A_SPLIT, cus=256)
+    with pytest.raises(ValueError, match="fp16-pair output"):
+        shim.linear_plan(512, 512, 128, f32, f32_gemm=2 | shim.F32_W_SPLIT | shim.F32_C_SPLIT, ldc=520, cus=256)
+    with pytest.raises(ValueError, match="bad query"):
+        shim.linear_plan(512, 512, 128, f32, cus=-1)

@@ -45,7 +45,9 @@ def relerr(a, b):
 # ------------------------------------------------------------------------------------------
 @pytest.mark.parametrize("M,N,K", [(300, 80, 160), (128, 128, 32), (1, 512, 64), (1000, 100, 96),
                                    (257, 1536, 512), (64, 27, 1408),
-                                   # >= 1024 rows and N % 256 == 0: the 256 x 256 ring kernel
+                                   # >= 1024 rows and N % 256 == 0: in the default mode the three-term kernel (f32_three); in
+                                   # native mode these would take 128 x 128 tiles (linear_plan; the fp32 ring kernel needs
+                                   # more tiles: tests/test_gpu_linear.py, ring-f32-*)
                                    (1030, 256, 32), (2050, 512, 160), (1279, 768, 64)])
 @pytest.mark.parametrize("act", [0, 1, 2])
 def test_linear_fp32(M, N, K, act):
@@ -323,13 +325,14 @@ def test_linear_fp32_range_guard_picks_the_split_on_the_device(amax):
 
 
 @pytest.mark.parametrize("M,N,K", [(300, 192, 128), (130, 64, 64), (1000, 1536, 512), (129, 80, 2048),
-                                   # the 256 x 256 ring kernel: 2, 4, 6 and 32 stages, ragged M
+                                   # 2, 4, 6 and 32 stages of 32, ragged M: on 256 CUs the cost model gives all four 128 x 128
+                                   # tiles (linear_plan), not the 256 x 256 ring kernel
                                    (1030, 256, 64), (1500, 512, 128), (1100, 768, 192), (4099, 1536, 1024),
-                                   # more tiles than CUs, ragged last m-tile: the persistent ring kernel (N >= 1024) and the
-                                   # plain one (N = 512)
+                                   # more tiles than CUs, ragged last m-tile: both take 256 x 128 tiles (ring_mid)
                                    (66001, 512, 256), (33000, 1024, 512),
                                    # per-rank shapes of an 8-way latitude-band split: the cost model picks 256 x 128 tiles
                                    # (two workgroups per CU) for the first two, 128 x 128 tiles for the third
+                                   # (the 256 x 256 kernels, kernel by kernel: tests/test_gpu_linear.py)
                                    (34560, 512, 512), (8100, 3072, 1024), (2160, 2048, 2048)])
 @pytest.mark.parametrize("act", [0, 1])
 def test_linear_bf16(M, N, K, act):
