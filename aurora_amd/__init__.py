@@ -11,7 +11,8 @@ probabilities (aurora_amd/probability.py), and `FieldStats` accumulates per-poin
 the members of an ensemble as maps (aurora_amd/fieldstats.py), and `diagnostics` forms the derived fields all of them can
 then take -- vorticity, divergence, wind speed, integrated vapour transport -- as a `Batch` (aurora_amd/diagnostics.py), and
 `conditional_scores` gives the error by bin of the truth and over its tails, against climatology maps such as those of
-`FieldStats` (aurora_amd/conditional.py); the reference has no counterpart.
+`FieldStats` (aurora_amd/conditional.py), and `region_scores` gives the scores of `scores` by region -- latitude bands,
+longitude boxes and masks, as scorecards report them (aurora_amd/regions.py); the reference has no counterpart.
 """
 
 from aurora_amd.batch import Batch, Metadata
@@ -32,6 +33,7 @@ from aurora_amd.model.aurora import (
 )
 from aurora_amd.probability import ProbabilityScores, probability_scores
 from aurora_amd.quantiles import EnsembleQuantiles, ensemble_quantiles
+from aurora_amd.regions import Region, Regions, RegionScores, region_scores
 from aurora_amd.rollout import rollout, write_rollout
 from aurora_amd.scores import Scores, scores
 from aurora_amd.spectra import Spectra, spectra
@@ -66,5 +68,9 @@ __all__ = [
     "diagnostics",
     "conditional_scores",
     "ConditionalScores",
+    "region_scores",
+    "Region",
+    "Regions",
+    "RegionScores",
     "Tracker",
 ]

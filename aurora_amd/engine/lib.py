@@ -151,6 +151,9 @@ _SIGNATURES = {
     "aurora_hip_conditional_scores_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int]),
     "aurora_hip_conditional_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int,
                                               c_void_p, c_void_p, c_void_p, c_void_p]),
+    "aurora_hip_region_scores_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int]),
+    "aurora_hip_region_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                         c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1096,6 +1099,52 @@ def conditional_sums(pred: list[torch.Tensor], truth: list[torch.Tensor], centre
             _check(load().aurora_hip_conditional_scores(base, base + 8 * n, centre_at, scale_at, n, n_lat, n_lon, _ptr(edges), E,
                                                         1 if by_pred else 0, _ptr(row_w), _ptr(sums), _ptr(workspace),
                                                         _stream()))
+    return sums
+
+
+# ---- region sums: the verification sums per region (aurora_hip_region_scores) --------------------------------------------
+REGION_MAX_PER_CALL = 8
+
+
+def region_scores_workspace_bytes(n_planes: int, n_lat: int, n_lon: int, n_regions: int) -> int:
+    return int(load().aurora_hip_region_scores_workspace_bytes(n_planes, n_lat, n_lon, n_regions))
+
+
+def region_sums(pred: list[torch.Tensor], truth: list[torch.Tensor], clim: Optional[list[torch.Tensor]], row_bits: torch.Tensor,
+                col_bits: torch.Tensor, mask_bits: Optional[torch.Tensor], n_regions: int, row_w: torch.Tensor) -> torch.Tensor:
+    """The eight sums of `scores_sums` per region of every plane of `pred` against the same plane of `truth` (and of `clim`, or
+    None), as an (n_planes, n_regions, 8) fp64 tensor on the device, in ONE aurora_hip_region_scores call.  A point belongs to
+    region r where bit r of row_bits[row] & col_bits[col] & mask_bits[row, col] is set (mask_bits None: every bit set).
+
+    pred / truth / clim: as in `scores_sums`; row_bits: (n_lat,) uint8, col_bits: (n_lon,) uint8, mask_bits: None or
+    (n_lat, n_lon) uint8, contiguous, on that device, any alignment; 1 <= n_regions <= 8; row_w: (n_lat,) fp64 on that device.
+    The plane-pointer table is cached by address as in `scores_sums`.  Nothing of plane size is allocated and the host does
+    not wait for the device."""
+    assert row_w.is_cuda and row_w.dtype == torch.float64 and row_w.dim() == 1 and row_w.is_contiguous(), \
+        "region_sums: row_w must be a contiguous fp64 vector on the device"
+    dev, n_lat = row_w.device, row_w.shape[0]
+    assert 1 <= n_regions <= REGION_MAX_PER_CALL, f"region_sums: 1..{REGION_MAX_PER_CALL} regions per call, got {n_regions}"
+    lists = [("prediction", pred), ("truth", truth)] + ([("climatology", clim)] if clim is not None else [])
+    n_lon = pred[0].shape[-1] if pred else col_bits.shape[0]
+    for what, t, shape in (("row_bits", row_bits, (n_lat,)), ("col_bits", col_bits, (n_lon,)), ("mask_bits", mask_bits, (n_lat, n_lon))):
+        if t is not None:
+            assert t.dtype == torch.uint8 and tuple(t.shape) == shape and t.is_contiguous(), \
+                f"region_sums: {what} must be a contiguous uint8 tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}"
+            assert t.device == dev, "region_sums: every tensor must be on the device of row_w"
+    n, addresses = _plane_lists("region_sums", lists, dev, "row_w", n_lat, n_lon)
+    sums = torch.empty(n, n_regions, 8, dtype=torch.float64, device=dev)
+    if n == 0:
+        return sums
+    with torch.cuda.device(dev):
+        table = _plane_table("region_sums", tuple(addresses), dev)
+        workspace = torch.empty(region_scores_workspace_bytes(n, n_lat, n_lon, n_regions), dtype=torch.uint8, device=dev)
+        base = table.data_ptr()
+        read = n * n_lat * n_lon * (4 * len(lists) + (1 if mask_bits is not None else 0))
+        with _Timed("region_scores", float(read)):   # bytes read, were every row in some region
+            _check(load().aurora_hip_region_scores(base, base + 8 * n, base + 16 * n if clim is not None else None, n, n_lat,
+                                                   n_lon, _ptr(row_bits), _ptr(col_bits),
+                                                   None if mask_bits is None else _ptr(mask_bits), n_regions, _ptr(row_w),
+                                                   _ptr(sums), _ptr(workspace), _stream()))
     return sums
 
 

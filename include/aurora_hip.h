@@ -980,6 +980,38 @@ int aurora_hip_diagnostics(const float* const* wind_u, const float* const* wind_
                            float* const* ivt_planes, int n_cols, int n_levels, const double* level_w, int n_lat, int n_lon,
                            void* stream);
 
+/* ---- verification sums by region on the device (aurora_amd.region_scores: the scores of aurora_amd.scores over latitude
+ * bands, longitude boxes and masks; not in the reference) ----------------------------------------------------------------------
+ * Planes as above.  For every plane k < n_planes the prediction p, the truth t and, unless clim_planes is NULL, the
+ * climatology c are read once.  The point (i, j) BELONGS to region r < n_regions where bit r of
+ *   row_bits[i] & col_bits[j] & mask_bits[i n_lon + j]                      (mask_bits = NULL: every bit set)
+ * is set; regions may overlap.  A point is VALID as in aurora_hip_scores: p, t and (if given) c finite.  Over the valid points
+ * of region r, with w = row_w[i]:
+ *   sums[(k n_regions + r) 8 + slot]: the eight slots of aurora_hip_scores (count, w, w d, w d^2, w |d|, w p' t', w p'^2,
+ *   w t'^2; slots 5..7 are 0 without clim_planes)
+ * -- aurora_hip_scores' sums restricted to the region.  A region without a valid point gives zeros.  Differences and products
+ * are formed in fp64 from the fp32 inputs and accumulated in fp64.  A row i whose byte has none of the bits 0 .. n_regions - 1
+ * set is not read at all.
+ * Determinism: the reduction tree of aurora_hip_scores (lane -> wavefront -> workgroup -> one partial per plane, row chunk and
+ * region in `workspace` -> partials added in chunk order by a second launch; no atomics).  A point enters every region it does
+ * not belong to as exactly +0, so the eight sums of a region are repeatable bit for bit and depend on the points of THAT
+ * region, row_w, n_lat and n_lon alone: not on n_planes, on the other planes, on the alignment of any pointer, on which other
+ * regions share the call or how many, or (slots 0..4, where c is finite wherever p and t are) on whether a climatology is given.
+ * The three plane arrays are DEVICE arrays of n_planes plane pointers (4-byte aligned).  row_bits: n_lat device bytes;
+ * col_bits: n_lon device bytes; mask_bits: NULL or n_lat x n_lon device bytes, row-major; any alignment.  16-byte loads of the
+ * planes and 4-byte loads of col_bits and mask_bits are used where n_lon % 4 == 0, all of a plane's pointers are 16-byte
+ * aligned and col_bits and mask_bits are 4-byte aligned: the same elements either way.  1 <= n_regions <= 8; bits n_regions
+ * .. 7 of the tables are ignored.  row_w: n_lat device doubles; sums: n_planes x n_regions x 8 device doubles; workspace:
+ * aurora_hip_region_scores_workspace_bytes(n_planes, n_lat, n_lon, n_regions) device bytes, 8-byte aligned, no
+ * initialisation needed (0 bytes for an argument out of range).  Arguments are checked before anything is enqueued
+ * (AURORA_E_ARG and aurora_hip_last_error()).  n_planes = 0 is a no-op.  The inputs are not modified.  Two launches, no
+ * plane-sized temporary, no host synchronisation, no allocation, no environment variable: capturable in a hipGraph. */
+size_t aurora_hip_region_scores_workspace_bytes(int n_planes, int n_lat, int n_lon, int n_regions);
+int aurora_hip_region_scores(const float* const* pred_planes, const float* const* truth_planes,
+                             const float* const* clim_planes, int n_planes, int n_lat, int n_lon, const uint8_t* row_bits,
+                             const uint8_t* col_bits, const uint8_t* mask_bits, int n_regions, const double* row_w,
+                             double* sums, void* workspace, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
