@@ -12,11 +12,14 @@ the members of an ensemble as maps (aurora_amd/fieldstats.py), and `diagnostics`
 then take -- vorticity, divergence, wind speed, integrated vapour transport -- as a `Batch` (aurora_amd/diagnostics.py), and
 `conditional_scores` gives the error by bin of the truth and over its tails, against climatology maps such as those of
 `FieldStats` (aurora_amd/conditional.py), and `region_scores` gives the scores of `scores` by region -- latitude bands,
-longitude boxes and masks, as scorecards report them (aurora_amd/regions.py); the reference has no counterpart.
+longitude boxes and masks, as scorecards report them (aurora_amd/regions.py), and `conservative_regrid` brings a batch to the
+grid of its truth by area-weighted remapping, which `Batch.regrid`'s bilinear sampling is not made for
+(aurora_amd/conservative.py); the reference has no counterpart.
 """
 
 from aurora_amd.batch import Batch, Metadata
 from aurora_amd.conditional import ConditionalScores, conditional_scores
+from aurora_amd.conservative import conservative_regrid
 from aurora_amd.diagnostics import diagnostics
 from aurora_amd.ensemble import EnsembleScores, ensemble_scores
 from aurora_amd.events import EventScores, event_scores
@@ -72,5 +75,6 @@ __all__ = [
     "Region",
     "Regions",
     "RegionScores",
+    "conservative_regrid",
     "Tracker",
 ]

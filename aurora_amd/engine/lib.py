@@ -127,6 +127,9 @@ _SIGNATURES = {
                                        c_void_p, c_void_p, c_void_p]),
     "aurora_hip_regrid": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p,
                                   c_void_p, c_int, c_void_p]),
+    "aurora_hip_conservative_regrid": (c_int, [c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, ctypes.c_double,
+                                               c_void_p]),
     "aurora_hip_scores_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int]),
     "aurora_hip_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "aurora_hip_ensemble_scores_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int]),
@@ -774,6 +777,46 @@ def regrid(src: list[torch.Tensor], dst: list[torch.Tensor], rows: torch.Tensor,
         _check(load().aurora_hip_regrid(_ptr(planes[0]), F64 if dt == torch.float64 else F32, _ptr(planes[1]), len(sp),
                                         n_lat, n_lon, _ptr(rows), _ptr(row_w), n_rows, _ptr(cols), _ptr(col_w), n_cols,
                                         _stream()))
+
+
+def conservative_regrid(src: list[torch.Tensor], out: torch.Tensor, tables, min_valid: float) -> None:
+    """out[p] = the conservative regrid (aurora_amd/conservative.py has the rule) of plane p of `src`, the planes of its
+    tensors counted one tensor after the other, in ONE aurora_hip_conservative_regrid launch.
+
+    src: contiguous (..., n_lat, n_lon) tensors, all fp32 or all fp64; out: ONE contiguous fp32 (n_planes, n_rows, n_cols)
+    tensor on their device; tables: the eight device tables of include/aurora_hip.h (row first / count / weights / measures,
+    then the same of the columns).  The source plane-pointer table is cached by address as in `scores_sums`; the
+    destination's is formed on the device from the address of `out`, which may therefore be a new tensor in every call,
+    also during stream capture.  No workspace, and the host does not wait for the device."""
+    row_first, row_count, row_w, row_m, col_first, col_count, col_w, col_m = tables
+    assert src and out.dim() == 3 and out.dtype == torch.float32 and out.is_contiguous(), "conservative_regrid: bad output"
+    dev, dt = out.device, src[0].dtype
+    n_lat, n_lon = src[0].shape[-2:]
+    n, n_rows, n_cols = out.shape
+    assert dt in (torch.float32, torch.float64), f"conservative_regrid: sources must be fp32 or fp64, got {dt}"
+    for t, d_, shape in ((row_first, torch.int32, (n_rows, 2)), (row_count, torch.int32, (n_rows,)), (row_w, torch.float64, None),
+                         (row_m, torch.float64, (n_rows,)), (col_first, torch.int32, (n_cols, 2)),
+                         (col_count, torch.int32, (n_cols,)), (col_w, torch.float64, None), (col_m, torch.float64, (n_cols,))):
+        assert t.device == dev and t.dtype == d_ and t.is_contiguous() and (t.dim() == 1 if shape is None else tuple(t.shape) == shape), \
+            "conservative_regrid: a table has the wrong device, dtype or shape"
+    addresses = []
+    for s_ in src:
+        assert s_.device == dev and s_.dtype == dt and s_.is_contiguous() and tuple(s_.shape[-2:]) == (n_lat, n_lon), \
+            "conservative_regrid: bad source"
+        addresses += [s_.data_ptr() + i * n_lat * n_lon * s_.element_size() for i in range(s_.numel() // (n_lat * n_lon))]
+    assert len(addresses) == n, f"conservative_regrid: the sources hold {len(addresses)} planes, out {n}"
+    if n == 0:
+        return
+    with torch.cuda.device(dev):
+        planes = _plane_table("conservative_regrid", tuple(addresses), dev)
+        step = 4 * n_rows * n_cols
+        dst = torch.arange(out.data_ptr(), out.data_ptr() + n * step, step, dtype=torch.int64, device=dev)
+        moved = float(n) * (n_lat * n_lon * src[0].element_size() + step)
+        with _Timed("conservative_regrid", moved):
+            _check(load().aurora_hip_conservative_regrid(_ptr(planes), F64 if dt == torch.float64 else F32, _ptr(dst), n, n_lat,
+                                                         n_lon, n_rows, n_cols, _ptr(row_first), _ptr(row_count), _ptr(row_w),
+                                                         _ptr(row_m), _ptr(col_first), _ptr(col_count), _ptr(col_w), _ptr(col_m),
+                                                         float(min_valid), _stream()))
 
 
 # ---- verification sums (aurora_hip_scores) ----------------------------------------------------------------

@@ -685,6 +685,42 @@ int aurora_hip_regrid(const void* const* src_planes, int src_dtype, float* const
                       int n_lon, const int32_t* rows, const double* row_w, int n_rows_out, const int32_t* cols,
                       const double* col_w, int n_cols_out, void* stream);
 
+/* ---- conservative (area-weighted) regridding of a batch on the device (aurora_amd.conservative_regrid; not in the
+ * reference) ----------------------------------------------------------------------------------------------------------------
+ * First-order conservative remapping from a (lat, lon) grid to another: a target cell takes the mean of the source cells
+ * it overlaps, weighted by the overlap (sin(lat) x degrees of longitude), over the source values that are finite.
+ * aurora_amd/conservative.py states the cell model and builds the tables; a C host fills them itself as follows.
+ *
+ * Tables, all in DEVICE memory.  For the rows (i < n_rows_out) and, alike, for the columns (j < n_cols_out):
+ *   first    int32 [n][2]  first[i][0]: source index of the first tap of target cell i; first[i][1]: index of its first
+ *                          weight in w (>= 0).  Tap t < count[i] reads source row first[i][0] + t (clamped into
+ *                          [0, n_lat - 1]) or source column (first[j][0] + t) mod n_lon (first[j][0] clamped into
+ *                          [0, 3 n_lon - 1]: a full-circle source stores n_lon + k for column k, so that a cell that
+ *                          straddles the seam starts at n_lon - 1 or below and runs eastward), with weight
+ *                          w[first[.][1] + t].  Along the columns neither first[j][0] nor first[j][0] + count[j] may
+ *                          decrease (a cell without taps takes the end of its western neighbours): the kernel takes the
+ *                          span of source columns of a tile of target columns from the tile's first and last cell.
+ *   count    int32 [n]     taps of the cell, 0 .. 64 (clamped); 0: the cell is NaN.
+ *   w        fp64 [...]    the overlaps, cell after cell, every one > 0; first[.][1] + count must stay inside it.
+ *   measure  fp64 [n]      A_i / B_j: the full measure of the target cell (sin(lat) difference / degrees).
+ * Arithmetic: fp64, each operation rounded on its own (no fused multiply-add).  For target row i and every source
+ * column c, over the row taps (a, r) in order from cn = cd = 0: where x[r][c] is finite, cn += a * x[r][c] and cd += a.
+ * For target column j, over the column taps (b, c) in order from n = d = 0: n += b * cn[c], d += b * cd[c].
+ * dst[p][i][j] = (float)(n / d) where d > 0 and d >= min_valid * (A_i * B_j), and NaN otherwise.
+ *
+ * src_planes / dst_planes: DEVICE arrays of n_planes plane pointers: sources n_lat x n_lon row-major, AURORA_F32 or
+ * AURORA_F64, element-aligned (16-byte aligned planes with n_lon % 4 == 0 are read 16 bytes at a time; the result is the
+ * same bits either way); destinations fp32 n_rows_out x n_cols_out, 4-byte aligned, not overlapping any source.  ONE
+ * launch over every plane; a plane's result does not depend on the other planes.  min_valid in (0, 1].  Null pointers,
+ * sizes < 1, another dtype and a min_valid outside (0, 1] are AURORA_E_ARG before anything is launched.  Every source
+ * index is clamped or wrapped into the plane whatever the tables hold.  No workspace, no atomics, nothing read back, no
+ * host synchronisation: capturable in a hipGraph. */
+int aurora_hip_conservative_regrid(const void* const* src_planes, int src_dtype, float* const* dst_planes, int n_planes,
+                                   int n_lat, int n_lon, int n_rows_out, int n_cols_out, const int32_t* row_first,
+                                   const int32_t* row_count, const double* row_w, const double* row_measure,
+                                   const int32_t* col_first, const int32_t* col_count, const double* col_w,
+                                   const double* col_measure, double min_valid, void* stream);
+
 /* ---- scoring a forecast against truth on the device (aurora_amd.scores: latitude-weighted RMSE / bias / MAE and the
  * anomaly correlation; not in the reference) -------------------------------------------------------------------------------
  * A plane is one variable, level and batch element: n_lat x n_lon fp32, row-major.  For every plane k < n_planes the
