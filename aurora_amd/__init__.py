@@ -14,7 +14,8 @@ then take -- vorticity, divergence, wind speed, integrated vapour transport -- a
 `FieldStats` (aurora_amd/conditional.py), and `region_scores` gives the scores of `scores` by region -- latitude bands,
 longitude boxes and masks, as scorecards report them (aurora_amd/regions.py), and `conservative_regrid` brings a batch to the
 grid of its truth by area-weighted remapping, which `Batch.regrid`'s bilinear sampling is not made for
-(aurora_amd/conservative.py); the reference has no counterpart.
+(aurora_amd/conservative.py), and `objects` labels the connected regions of threshold exceedances -- storms, atmospheric rivers,
+heat domes -- with their sizes, centres and peaks (aurora_amd/objects.py); the reference has no counterpart.
 """
 
 from aurora_amd.batch import Batch, Metadata
@@ -34,6 +35,7 @@ from aurora_amd.model.aurora import (
     AuroraSmallPretrained,
     AuroraWave,
 )
+from aurora_amd.objects import Objects, objects
 from aurora_amd.probability import ProbabilityScores, probability_scores
 from aurora_amd.quantiles import EnsembleQuantiles, ensemble_quantiles
 from aurora_amd.regions import Region, Regions, RegionScores, region_scores
@@ -76,5 +78,7 @@ __all__ = [
     "Regions",
     "RegionScores",
     "conservative_regrid",
+    "objects",
+    "Objects",
     "Tracker",
 ]

@@ -157,6 +157,9 @@ _SIGNATURES = {
     "aurora_hip_region_scores_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int]),
     "aurora_hip_region_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int,
                                          c_void_p, c_void_p, c_void_p, c_void_p]),
+    "aurora_hip_objects_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int]),
+    "aurora_hip_objects": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
+                                   c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1192,6 +1195,61 @@ def region_sums(pred: list[torch.Tensor], truth: list[torch.Tensor], clim: Optio
 
 
 # ---- event probabilities of an ensemble (aurora_hip_probability_scores) -----------------------------------------------
+# ---- threshold objects: connected components and their table (aurora_hip_objects) ------------------------------------------
+OBJECT_MAX_THRESHOLDS, OBJECT_MAX_LON, OBJECT_COLUMNS, OBJECT_MAX_POINTS = 8, 4096, 10, 2 ** 31 - 2
+
+
+def objects_workspace_bytes(n_planes: int, n_lat: int, n_lon: int, n_thresholds: int) -> int:
+    return int(load().aurora_hip_objects_workspace_bytes(n_planes, n_lat, n_lon, n_thresholds))
+
+
+def object_labels(fields: list[torch.Tensor], thresholds: torch.Tensor, unit: torch.Tensor, below: bool = False,
+                  connectivity: int = 8, wrap: bool = False, max_objects: int = 4096, *, out=None,
+                  workspace: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The objects (include/aurora_hip.h) of every plane of `fields` for every threshold, in ONE aurora_hip_objects call:
+    labels (n_planes, T, n_lat, n_lon) int32, count (n_planes, T) int32 and table (n_planes, T, max_objects, 10) int64, on the
+    device.
+
+    fields: a list of fp32 (..., n_lat, n_lon) tensors on one device with row-major contiguous planes (any leading strides,
+    any 4-byte plane alignment); thresholds: contiguous (n_planes, T) fp32 on that device (NaN: no event); unit: contiguous
+    (n_lat,) int64 on that device, the area units of the rows.  out: (labels, count, table) to write into, contiguous and of
+    those shapes; workspace: a uint8 tensor of at least `objects_workspace_bytes` bytes -- both are allocated when not given
+    (the workspace is plane-sized: 4 bytes per point and threshold).  The plane-pointer table is cached by address as in
+    `scores_sums`.  The host does not wait for the device."""
+    assert thresholds.is_cuda and thresholds.dtype == torch.float32 and thresholds.dim() == 2 and thresholds.is_contiguous(), \
+        "object_labels: thresholds must be a contiguous (n_planes, T) fp32 matrix on the device"
+    dev, (n_thr_planes, T) = thresholds.device, thresholds.shape
+    assert 1 <= T <= OBJECT_MAX_THRESHOLDS, f"object_labels: 1..{OBJECT_MAX_THRESHOLDS} thresholds, got {T}"
+    assert fields, "object_labels: the list of fields is empty"
+    n_lat, n_lon = fields[0].shape[-2:]
+    assert unit.device == dev and unit.dtype == torch.int64 and tuple(unit.shape) == (n_lat,) and unit.is_contiguous(), \
+        "object_labels: unit must be a contiguous (n_lat,) int64 vector on the device of thresholds"
+    max_objects = int(max_objects)
+    n, addresses = _plane_lists("object_labels", [("field", fields)], dev, "thresholds", n_lat, n_lon)
+    assert n == n_thr_planes, f"object_labels: {n} planes but thresholds for {n_thr_planes}"
+    shapes = ((n, T, n_lat, n_lon), (n, T), (n, T, max(max_objects, 0), OBJECT_COLUMNS))
+    dtypes = (torch.int32, torch.int32, torch.int64)
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=dev) for s, d in zip(shapes, dtypes))
+    for t, s, d, what in zip(out, shapes, dtypes, ("labels", "count", "table")):
+        assert t.device == dev and t.dtype == d and tuple(t.shape) == s and t.is_contiguous(), \
+            f"object_labels: {what} must be a contiguous {d} tensor of shape {s} on the device of thresholds"
+    labels, count, table = out
+    if n == 0:
+        return labels, count, table
+    with torch.cuda.device(dev):
+        planes = _plane_table("object_labels", tuple(addresses), dev)
+        if workspace is None:
+            workspace = torch.empty(objects_workspace_bytes(n, n_lat, n_lon, T), dtype=torch.uint8, device=dev)
+        assert workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous(), \
+            "object_labels: the workspace must be a contiguous uint8 tensor on the device of thresholds"
+        with _Timed("objects", 0.0):
+            _check(load().aurora_hip_objects(planes.data_ptr(), n, n_lat, n_lon, _ptr(thresholds), T, _ptr(unit),
+                                             1 if below else 0, int(connectivity), 1 if wrap else 0, max_objects, _ptr(labels),
+                                             _ptr(count), _ptr(table), _ptr(workspace), workspace.numel(), _stream()))
+    return labels, count, table
+
+
 def probability_rows(members: list[list[torch.Tensor]], truth: list[torch.Tensor], thresholds: torch.Tensor,
                      below: bool = False) -> torch.Tensor:
     """The integer table of include/aurora_hip.h -- per row of every plane, threshold and (event observed o, k of M members

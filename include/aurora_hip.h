@@ -1048,6 +1048,37 @@ int aurora_hip_region_scores(const float* const* pred_planes, const float* const
                              const uint8_t* col_bits, const uint8_t* mask_bits, int n_regions, const double* row_w,
                              double* sums, void* workspace, void* stream);
 
+/* ---- threshold objects on the device (aurora_amd.objects: connected components of events with their sizes, positions and
+ * peaks; not in the reference) ----------------------------------------------------------------------------------------------
+ * Planes as above.  For every plane k < n_planes and threshold t < n_thresholds (thresholds[k n_thresholds + t], device fp32;
+ * NaN: no event) a point is an EVENT where its value v is finite and v >= threshold (below = 1: v <= threshold).  An OBJECT is
+ * a maximal connected set of events: `connectivity` 4 or 8 among grid neighbours, none beyond row 0 or row n_lat - 1; with
+ * wrap = 1 column n_lon - 1 and column 0 are neighbours (diagonally too with 8).  Its FIRST POINT is its smallest flat index
+ * i n_lon + j, and objects are numbered 1, 2, ... in ascending order of their first points.
+ *   labels[(k n_thresholds + t) n_lat n_lon + i n_lon + j]   int32: the number of the point's object, 0 for background
+ *   count[k n_thresholds + t]                                int32: the number of objects (also beyond max_objects)
+ *   table[((k n_thresholds + t) max_objects + (o - 1)) 10 + c]   int64, for the objects o <= max_objects; other rows are 0:
+ *     0 points   1 area_units = sum of unit[i] (device int64 per row)   2 first   3 row_min   4 row_max   5 row_sum = sum of i
+ *     6 col_off_min  7 col_off_max  8 col_off_sum of d = j - j_first, with wrap reduced into [-(n_lon / 2), n_lon - n_lon / 2)
+ *     9 peak_key = (K(v) << 32) | (0xffffffff - flat index), the unsigned 64-bit MAXIMUM over the points, where for the bits
+ *       u of v: K = ~u if u has the sign bit, else u | 0x80000000 (ascending with v, -0 below +0), and ~K is taken with
+ *       below = 1: the largest (below: smallest) value, and among equal values the smallest flat index.
+ * Union-find in `workspace`, aurora_hip_objects_workspace_bytes(n_planes, n_lat, n_lon, n_thresholds) device bytes (one int32
+ * per point and threshold plus one per row and threshold; 8-byte aligned; no initialisation needed; 0 for an argument out of
+ * range): seven launches on `stream` (zero, rows, unite, flatten, scan, number, tabulate).  parent[x] <= x holds throughout,
+ * every loop moves to a strictly smaller index or is bounded by n_lat or n_lon, and no launch waits on a value written within
+ * it.  The table is filled by 64-bit integer atomics only.  labels, count and table are repeatable bit for bit and depend on
+ * the plane's own values and thresholds alone: not on the other planes, not on the alignment of a plane pointer (planes are
+ * read 4 bytes at a time), not on the order in which workgroups run.
+ * 1 <= n_lon <= 4096, n_lat n_lon <= 2^31 - 2, 1 <= n_thresholds <= 8, max_objects >= 1; workspace_size: the bytes at
+ * `workspace`, refused if too few.  Arguments are checked before anything is enqueued (AURORA_E_ARG and
+ * aurora_hip_last_error()).  n_planes = 0 is a no-op.  The inputs are not modified.  No host synchronisation, no allocation,
+ * no environment variable: capturable in a hipGraph. */
+size_t aurora_hip_objects_workspace_bytes(int n_planes, int n_lat, int n_lon, int n_thresholds);
+int aurora_hip_objects(const float* const* planes, int n_planes, int n_lat, int n_lon, const float* thresholds,
+                       int n_thresholds, const int64_t* unit, int below, int connectivity, int wrap, int max_objects,
+                       int32_t* labels, int32_t* count, int64_t* table, void* workspace, size_t workspace_size, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
