@@ -11,7 +11,10 @@
 // enters the others.  x + (+0) = x, so a bin's sums are the sums over the points of that bin alone, in the order of the
 // reduction tree of planes.h: they do not depend on how many other edges the call has or on which instantiation ran.
 // That only holds while every instantiation rounds alike, so contraction is off in this file's arithmetic and the one
-// fused multiply-add that is wanted is written out.  conditional_finish_kernel is the second launch of the tree.
+// fused multiply-add that is wanted is written out.  finish_partials ((n_edges + 1) x 5 sums to a chunk) is the second launch
+// of the tree.
+#include <type_traits>
+
 #include "planes.h"
 
 namespace aurora {
@@ -150,21 +153,6 @@ __global__ __launch_bounds__(kThreads) void conditional_kernel(const float* cons
     partial[(int64_t)blockIdx.x * n_out + threadIdx.x] = sum_waves(s_wave, (int)threadIdx.x);
 }
 
-// sums[plane][bin][slot] = partial[plane][0][bin][slot] + partial[plane][1][bin][slot] + ... in chunk order; one lane per
-// (plane, bin, slot).
-__global__ __launch_bounds__(kThreads) void conditional_finish_kernel(const double* __restrict__ partial, int n_planes,
-                                                                      int n_chunks, int n_out, double* __restrict__ sums) {
-#pragma clang fp contract(off)
-  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (i >= (int64_t)n_planes * n_out) return;
-  const int64_t plane = i / n_out;
-  const int s = (int)(i % n_out);
-  const double* p = partial + plane * n_chunks * n_out + s;
-  double v = p[0];
-  for (int k = 1; k < n_chunks; ++k) v += p[(int64_t)k * n_out];
-  sums[i] = v;
-}
-
 template <int kE, bool kCentre, bool kScale>
 void launch(unsigned groups, hipStream_t stream, const float* const* pred_planes, const float* const* truth_planes,
             const float* const* centre_planes, const float* const* scale_planes, int n_lat, int n_lon, int n_chunks,
@@ -186,17 +174,16 @@ template <int kE, typename... A> void launch_maps(bool centre, bool scale, A... 
 using namespace aurora;
 
 extern "C" size_t aurora_hip_conditional_scores_workspace_bytes(int n_planes, int n_lat, int n_lon, int n_edges) {
-  if (n_planes < 1 || n_lat < 1 || n_lon < 1 || n_edges < 1 || n_edges > kMaxEdges) return 0;
-  return (size_t)n_planes * (size_t)chunks_per_plane(n_lat, n_lon, kChunkElems, kWaves) * (size_t)(n_edges + 1) * kSlots *
-         sizeof(double);
+  if (n_edges < 1 || n_edges > kMaxEdges) return 0;
+  return (size_t)chunk_plan(n_planes, n_lat, n_lon, kChunkElems, kWaves).groups * (size_t)(n_edges + 1) * kSlots * sizeof(double);
 }
 
 extern "C" int aurora_hip_conditional_scores(const float* const* pred_planes, const float* const* truth_planes,
                                              const float* const* centre_planes, const float* const* scale_planes,
                                              int n_planes, int n_lat, int n_lon, const float* edges, int n_edges, int by_pred,
                                              const double* row_w, double* sums, void* workspace, void* stream) {
-  AURORA_CHECK_ARG(n_planes >= 0 && n_lat >= 1 && n_lon >= 1, "conditional_scores: bad sizes (planes %d, grid %d x %d)",
-                   n_planes, n_lat, n_lon);
+  ChunkPlan plan;
+  if (const int code = plan_chunks("conditional_scores", n_planes, n_lat, n_lon, kChunkElems, kWaves, &plan)) return code;
   AURORA_CHECK_ARG(n_edges >= 1 && n_edges <= kMaxEdges, "conditional_scores: 1 to %d edges, got %d", kMaxEdges, n_edges);
   if (n_planes == 0) return AURORA_OK;
   AURORA_CHECK_ARG(pred_planes && truth_planes && edges && row_w && sums && workspace,
@@ -204,26 +191,17 @@ extern "C" int aurora_hip_conditional_scores(const float* const* pred_planes, co
   AURORA_CHECK_ARG(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)sums & 7) == 0 && ((uintptr_t)row_w & 7) == 0 &&
                        ((uintptr_t)edges & 3) == 0,
                    "conditional_scores: weights, output and workspace must be 8-byte aligned, the edge table 4-byte aligned");
-  const int64_t n_chunks = chunks_per_plane(n_lat, n_lon, kChunkElems, kWaves);
-  const int64_t groups = n_chunks * n_planes;
-  AURORA_CHECK_ARG(groups <= 0x7fffffff, "conditional_scores: too many planes for one launch (%d planes x %lld row chunks)",
-                   n_planes, (long long)n_chunks);
   double* const partial = (double*)workspace;
-  const bool centre = centre_planes != nullptr, scale = scale_planes != nullptr;
   const hipStream_t s = as_stream(stream);
-  if (n_edges <= 2)
-    launch_maps<2>(centre, scale, (unsigned)groups, s, pred_planes, truth_planes, centre_planes, scale_planes, n_lat, n_lon,
-                   (int)n_chunks, edges, n_edges, by_pred, row_w, partial);
-  else if (n_edges <= 4)
-    launch_maps<4>(centre, scale, (unsigned)groups, s, pred_planes, truth_planes, centre_planes, scale_planes, n_lat, n_lon,
-                   (int)n_chunks, edges, n_edges, by_pred, row_w, partial);
-  else
-    launch_maps<8>(centre, scale, (unsigned)groups, s, pred_planes, truth_planes, centre_planes, scale_planes, n_lat, n_lon,
-                   (int)n_chunks, edges, n_edges, by_pred, row_w, partial);
+  const auto run = [&](auto max_edges) {        // max_edges: the instantiation, an integral_constant
+    launch_maps<decltype(max_edges)::value>(centre_planes != nullptr, scale_planes != nullptr, (unsigned)plan.groups, s,
+                                            pred_planes, truth_planes, centre_planes, scale_planes, n_lat, n_lon,
+                                            (int)plan.n_chunks, edges, n_edges, by_pred, row_w, partial);
+  };
+  if (n_edges <= 2) run(std::integral_constant<int, 2>{});
+  else if (n_edges <= 4) run(std::integral_constant<int, 4>{});
+  else run(std::integral_constant<int, 8>{});
   const int code = check_launch("conditional_scores");
   if (code != AURORA_OK) return code;
-  const int n_out = (n_edges + 1) * kSlots;
-  const unsigned fin = (unsigned)(((int64_t)n_planes * n_out + kThreads - 1) / kThreads);
-  hipLaunchKernelGGL(conditional_finish_kernel, dim3(fin), dim3(kThreads), 0, s, partial, n_planes, (int)n_chunks, n_out, sums);
-  return check_launch("conditional_scores (finish)");
+  return finish_partials("conditional_scores", partial, n_planes, (int)plan.n_chunks, (n_edges + 1) * kSlots, sums, s);
 }

@@ -21,8 +21,9 @@
 //
 // The fp64 sums go through the reduction tree of planes.h, four waves to a workgroup, with a chunk size that depends on
 // the bucket; the integer counts ride along (they are wave sums from the start: popcounts of ballots).
-// ensemble_finish_kernel is the tree's second launch and also turns the cumulative counts #{points : x_(k) < y} into
-// the M + 1 bins.  No atomics of any kind.
+// ensemble_finish_kernel is the tree's second launch in place of finish_partials: it adds the sums by the plane rule of
+// planes.h, over partials that are partial_bytes apart, and also turns the cumulative counts #{points : x_(k) < y} into the
+// M + 1 bins.  No atomics of any kind.
 #include "planes.h"
 #include "sortnet.h"
 
@@ -228,7 +229,7 @@ __global__ __launch_bounds__(kThreads) void ensemble_finish_kernel(const char* _
   const int64_t stride = partial_bytes(bucket);
   const char* p = partial + plane * n_chunks * stride;
   if (j < kSlots) {
-    double v = ((const double*)p)[j];
+    double v = ((const double*)p)[j];           // the plane stage of planes.h: partial 0, then += partial 1, 2, ...
     for (int k = 1; k < n_chunks; ++k) v += ((const double*)(p + k * stride))[j];
     sums[plane * kSlots + j] = v;
     return;
@@ -259,9 +260,9 @@ void launch(unsigned groups, void* stream, const float* const* member_planes, co
 using namespace aurora;
 
 extern "C" size_t aurora_hip_ensemble_scores_workspace_bytes(int n_members, int n_planes, int n_lat, int n_lon) {
-  if (n_members < 2 || n_members > kMaxMembers || n_planes < 1 || n_lat < 1 || n_lon < 1) return 0;
+  if (n_members < 2 || n_members > kMaxMembers) return 0;
   const int bucket = bucket_of(n_members);
-  return (size_t)n_planes * (size_t)chunks_per_plane(n_lat, n_lon, chunk_elems(bucket), kWaves) * (size_t)partial_bytes(bucket);
+  return (size_t)chunk_plan(n_planes, n_lat, n_lon, chunk_elems(bucket), kWaves).groups * (size_t)partial_bytes(bucket);
 }
 
 extern "C" int aurora_hip_ensemble_scores(const float* const* member_planes, const float* const* truth_planes, int n_members,
@@ -269,25 +270,21 @@ extern "C" int aurora_hip_ensemble_scores(const float* const* member_planes, con
                                           int64_t* hist, void* workspace, void* stream) {
   AURORA_CHECK_ARG(n_members >= 2 && n_members <= kMaxMembers, "ensemble_scores: n_members must be in 2..%d, got %d",
                    kMaxMembers, n_members);
-  AURORA_CHECK_ARG(n_planes >= 0 && n_lat >= 1 && n_lon >= 1, "ensemble_scores: bad sizes (planes %d, grid %d x %d)", n_planes,
-                   n_lat, n_lon);
+  const int bucket = bucket_of(n_members);
+  ChunkPlan plan;
+  if (const int code = plan_chunks("ensemble_scores", n_planes, n_lat, n_lon, chunk_elems(bucket), kWaves, &plan)) return code;
   if (n_planes == 0) return AURORA_OK;
   AURORA_CHECK_ARG(member_planes && truth_planes && row_w && sums && hist && workspace,
                    "ensemble_scores: null plane array, weight, output or workspace pointer");
   AURORA_CHECK_ARG((((uintptr_t)workspace | (uintptr_t)sums | (uintptr_t)hist | (uintptr_t)row_w) & 7) == 0,
                    "ensemble_scores: weights, outputs and workspace must be 8-byte aligned");
-  const int bucket = bucket_of(n_members);
   // (a wave's counts are 32-bit: at most chunk_rows x n_lon points of a workgroup)
   AURORA_CHECK_ARG((int64_t)chunk_rows(n_lon, chunk_elems(bucket), kWaves) * n_lon <= 0x7fffffff, "ensemble_scores: n_lon %d is too long a row",
                    n_lon);
-  const int64_t n_chunks = chunks_per_plane(n_lat, n_lon, chunk_elems(bucket), kWaves);
-  const int64_t groups = n_chunks * n_planes;
-  AURORA_CHECK_ARG(groups <= 0x7fffffff, "ensemble_scores: too many planes for one launch (%d planes x %lld row chunks)",
-                   n_planes, (long long)n_chunks);
   char* const partial = (char*)workspace;
-#define AURORA_ENSEMBLE_LAUNCH(MB, PPL)                                                                                  \
-  launch<MB, PPL>((unsigned)groups, stream, member_planes, truth_planes, n_members, n_planes, n_lat, n_lon, (int)n_chunks, \
-                  row_w, partial)
+#define AURORA_ENSEMBLE_LAUNCH(MB, PPL)                                                                          \
+  launch<MB, PPL>((unsigned)plan.groups, stream, member_planes, truth_planes, n_members, n_planes, n_lat, n_lon, \
+                  (int)plan.n_chunks, row_w, partial)
   switch (bucket) {
     case 4: AURORA_ENSEMBLE_LAUNCH(4, 4); break;
     case 8: AURORA_ENSEMBLE_LAUNCH(8, 4); break;
@@ -300,6 +297,6 @@ extern "C" int aurora_hip_ensemble_scores(const float* const* member_planes, con
   if (code != AURORA_OK) return code;
   const int64_t outputs = (int64_t)n_planes * (kSlots + n_members + 2);
   hipLaunchKernelGGL(ensemble_finish_kernel, dim3((unsigned)((outputs + kThreads - 1) / kThreads)), dim3(kThreads), 0,
-                     as_stream(stream), partial, n_members, bucket, n_planes, (int)n_chunks, sums, hist);
+                     as_stream(stream), partial, n_members, bucket, n_planes, (int)plan.n_chunks, sums, hist);
   return check_launch("ensemble_scores (finish)");
 }

@@ -1,7 +1,7 @@
-// Plane access and fixed-order reduction shared by the verification kernels (scores, ensemble_scores, probability_scores,
-// event_scores, conditional_scores, field_stats, spectra, diagnostics) and regrid.  Three contracts live here and nowhere
-// else: the quad rule, the reduction tree and the wind-speed expression.  A plane is n_lat x n_lon fp32, row-major, in global
-// memory.
+// Plane access and fixed-order reduction shared by the verification kernels (scores, region_scores, conditional_scores,
+// ensemble_scores, ensemble_quantiles, probability_scores, event_scores, field_stats, spectra, diagnostics, objects) and the
+// two regrids.  Three contracts live here and nowhere else: the quad rule, the reduction tree (its one kernel and its launch
+// are in planes.hip) and the wind-speed expression.  A plane is n_lat x n_lon fp32, row-major, in global memory.
 #pragma once
 
 #include "common.h"
@@ -83,10 +83,16 @@ __device__ __forceinline__ void store4(V* base, int64_t i0, int cnt, bool vec, c
 //             row chunk (W waves; a chunk is chunk_rows consecutive rows);
 //   wave      xor butterfly over the 64 lanes (wave_sum_f64);
 //   workgroup the W waves' sums through LDS, added in wave order (sum_waves): one partial per (plane, row chunk);
-//   plane     a second launch (the file's finish kernel) adds the partials of a plane in chunk order: v = partial 0, then
-//             v += partial 1, 2, ...
+//   plane     a second launch (finish_partials below; ensemble_scores.hip folds its histogram in a finish kernel of its own,
+//             by the same rule) adds the partials of a plane in chunk order: v = partial 0, then v += partial 1, 2, ...
 // No floating-point atomics, no tickets: the second launch is the hand-off.
 constexpr int kSumSlots = 8;                    // fp64 sums per plane, per partial and per wave
+// Target size of a row chunk (elements of one input) of scores and region_scores, whose sums must agree; conditional_scores
+// and ensemble_scores have their own.
+#ifndef AURORA_SCORES_CHUNK_ELEMS               // (a probe build may set it: AURORA_BUILD_FLAGS=-DAURORA_SCORES_CHUNK_ELEMS=...)
+#define AURORA_SCORES_CHUNK_ELEMS 40960
+#endif
+constexpr int kScoresChunkElems = AURORA_SCORES_CHUNK_ELEMS;
 
 // Rows per chunk: a function of n_lon and the target chunk size (elements of one input) alone, never of n_planes; at least
 // a row per wave.  Chunks per plane: of n_lat besides.
@@ -98,6 +104,19 @@ inline int64_t chunks_per_plane(int n_lat, int n_lon, int chunk_elems, int waves
   const int r = chunk_rows(n_lon, chunk_elems, waves);
   return ((int64_t)n_lat + r - 1) / r;
 }
+
+// The launch of a kernel that reduces by row chunks: one workgroup per (plane, row chunk), `groups` of them, and as many
+// partials in the workspace.  Nothing to do (groups 0) where a size is below 1.
+struct ChunkPlan {
+  int64_t n_chunks, groups;                     // chunks per plane; n_planes x n_chunks
+};
+inline ChunkPlan chunk_plan(int n_planes, int n_lat, int n_lon, int chunk_elems, int waves) {
+  if (n_planes < 1 || n_lat < 1 || n_lon < 1) return {0, 0};
+  const int64_t n_chunks = chunks_per_plane(n_lat, n_lon, chunk_elems, waves);
+  return {n_chunks, n_chunks * n_planes};
+}
+// The plan of the entry `name`, or AURORA_E_ARG and its message: sizes that are no grid, more workgroups than one launch takes.
+int plan_chunks(const char* name, int n_planes, int n_lat, int n_lon, int chunk_elems, int waves, ChunkPlan* plan);
 
 __device__ __forceinline__ double wave_sum_f64(double v) {
 #pragma unroll
@@ -113,6 +132,11 @@ __device__ __forceinline__ double sum_waves(const double (&s_wave)[W][S], int s)
   for (int k = 1; k < W; ++k) v += s_wave[k][s];
   return v;
 }
+
+// The plane stage: sums[plane][j] = partial[plane][0][j] + partial[plane][1][j] + ... for the n_out sums j of every plane, as
+// the second launch of the entry `name` on `stream`: the launch's code, with "<name> (finish)" in the message of a failure.
+int finish_partials(const char* name, const double* partial, int n_planes, int n_chunks, int n_out, double* sums,
+                    hipStream_t stream);
 
 // ---- the wind-speed expression --------------------------------------------------------------------------------------------
 // |(u, v)| in fp64 from fp32 components: both squares are exact, so the sum rounds once and the root once.  FieldStats over

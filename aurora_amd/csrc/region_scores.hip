@@ -12,7 +12,10 @@
 // enters the others.  x + (+0) = x, so a region's sums are the sums over its own points alone, in the order of the reduction
 // tree of planes.h: they do not depend on which other regions share the launch or on which instantiation ran.  That only
 // holds while every instantiation rounds alike, so contraction is off in this file's arithmetic and the fused multiply-adds
-// that are wanted are written out.  region_finish_kernel is the second launch of the tree.
+// that are wanted are written out.  finish_partials (n_regions x 8 sums to a chunk) is the second launch of the tree, as it
+// is for scores.hip: a region's sums are the sums of aurora_hip_scores restricted to its points.
+#include <type_traits>
+
 #include "planes.h"
 
 namespace aurora {
@@ -22,10 +25,7 @@ constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kSlots = kSumSlots;
 constexpr int kMaxRegions = 8;
-#ifndef AURORA_SCORES_CHUNK_ELEMS               // the chunk size of scores.hip (a probe build may set it there and here)
-#define AURORA_SCORES_CHUNK_ELEMS 40960
-#endif
-constexpr int kChunkElems = AURORA_SCORES_CHUNK_ELEMS;   // target size of a row chunk (elements of one input)
+constexpr int kChunkElems = kScoresChunkElems;  // target size of a row chunk (elements of one input): that of scores.hip
 
 template <int kR, bool kClim> struct Acc {
   double s2[kR], s3[kR], s4[kR];
@@ -159,21 +159,6 @@ __global__ __launch_bounds__(kThreads) void region_kernel(const float* const* __
         kClim || ((int)threadIdx.x % kSlots) < 5 ? sum_waves(s_wave, (int)threadIdx.x) : 0.0;
 }
 
-// sums[plane][region][slot] = partial[plane][0][region][slot] + partial[plane][1][region][slot] + ... in chunk order; one
-// lane per (plane, region, slot).
-__global__ __launch_bounds__(kThreads) void region_finish_kernel(const double* __restrict__ partial, int n_planes,
-                                                                 int n_chunks, int n_out, double* __restrict__ sums) {
-#pragma clang fp contract(off)
-  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (i >= (int64_t)n_planes * n_out) return;
-  const int64_t plane = i / n_out;
-  const int s = (int)(i % n_out);
-  const double* p = partial + plane * n_chunks * n_out + s;
-  double v = p[0];
-  for (int k = 1; k < n_chunks; ++k) v += p[(int64_t)k * n_out];
-  sums[i] = v;
-}
-
 template <int kR, typename... A> void launch(bool clim, unsigned groups, hipStream_t stream, A... args) {
   if (clim) hipLaunchKernelGGL((region_kernel<kR, true>), dim3(groups), dim3(kThreads), 0, stream, args...);
   else hipLaunchKernelGGL((region_kernel<kR, false>), dim3(groups), dim3(kThreads), 0, stream, args...);
@@ -185,17 +170,16 @@ template <int kR, typename... A> void launch(bool clim, unsigned groups, hipStre
 using namespace aurora;
 
 extern "C" size_t aurora_hip_region_scores_workspace_bytes(int n_planes, int n_lat, int n_lon, int n_regions) {
-  if (n_planes < 1 || n_lat < 1 || n_lon < 1 || n_regions < 1 || n_regions > kMaxRegions) return 0;
-  return (size_t)n_planes * (size_t)chunks_per_plane(n_lat, n_lon, kChunkElems, kWaves) * (size_t)n_regions * kSlots *
-         sizeof(double);
+  if (n_regions < 1 || n_regions > kMaxRegions) return 0;
+  return (size_t)chunk_plan(n_planes, n_lat, n_lon, kChunkElems, kWaves).groups * (size_t)n_regions * kSlots * sizeof(double);
 }
 
 extern "C" int aurora_hip_region_scores(const float* const* pred_planes, const float* const* truth_planes,
                                         const float* const* clim_planes, int n_planes, int n_lat, int n_lon,
                                         const uint8_t* row_bits, const uint8_t* col_bits, const uint8_t* mask_bits,
                                         int n_regions, const double* row_w, double* sums, void* workspace, void* stream) {
-  AURORA_CHECK_ARG(n_planes >= 0 && n_lat >= 1 && n_lon >= 1, "region_scores: bad sizes (planes %d, grid %d x %d)", n_planes,
-                   n_lat, n_lon);
+  ChunkPlan plan;
+  if (const int code = plan_chunks("region_scores", n_planes, n_lat, n_lon, kChunkElems, kWaves, &plan)) return code;
   AURORA_CHECK_ARG(n_regions >= 1 && n_regions <= kMaxRegions, "region_scores: 1 to %d regions per call, got %d", kMaxRegions,
                    n_regions);
   if (n_planes == 0) return AURORA_OK;
@@ -203,29 +187,17 @@ extern "C" int aurora_hip_region_scores(const float* const* pred_planes, const f
                    "region_scores: null plane array, row or column table, weight, output or workspace pointer");
   AURORA_CHECK_ARG(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)sums & 7) == 0 && ((uintptr_t)row_w & 7) == 0,
                    "region_scores: weights, output and workspace must be 8-byte aligned");
-  const int64_t n_chunks = chunks_per_plane(n_lat, n_lon, kChunkElems, kWaves);
-  const int64_t groups = n_chunks * n_planes;
-  AURORA_CHECK_ARG(groups <= 0x7fffffff, "region_scores: too many planes for one launch (%d planes x %lld row chunks)", n_planes,
-                   (long long)n_chunks);
   double* const partial = (double*)workspace;
-  const bool clim = clim_planes != nullptr;
   const hipStream_t s = as_stream(stream);
-  if (n_regions <= 1)
-    launch<1>(clim, (unsigned)groups, s, pred_planes, truth_planes, clim_planes, n_lat, n_lon, (int)n_chunks, row_bits, col_bits,
-              mask_bits, n_regions, row_w, partial);
-  else if (n_regions <= 2)
-    launch<2>(clim, (unsigned)groups, s, pred_planes, truth_planes, clim_planes, n_lat, n_lon, (int)n_chunks, row_bits, col_bits,
-              mask_bits, n_regions, row_w, partial);
-  else if (n_regions <= 4)
-    launch<4>(clim, (unsigned)groups, s, pred_planes, truth_planes, clim_planes, n_lat, n_lon, (int)n_chunks, row_bits, col_bits,
-              mask_bits, n_regions, row_w, partial);
-  else
-    launch<8>(clim, (unsigned)groups, s, pred_planes, truth_planes, clim_planes, n_lat, n_lon, (int)n_chunks, row_bits, col_bits,
-              mask_bits, n_regions, row_w, partial);
+  const auto run = [&](auto regions) {          // regions: the instantiation, an integral_constant
+    launch<decltype(regions)::value>(clim_planes != nullptr, (unsigned)plan.groups, s, pred_planes, truth_planes, clim_planes,
+                                     n_lat, n_lon, (int)plan.n_chunks, row_bits, col_bits, mask_bits, n_regions, row_w, partial);
+  };
+  if (n_regions <= 1) run(std::integral_constant<int, 1>{});
+  else if (n_regions <= 2) run(std::integral_constant<int, 2>{});
+  else if (n_regions <= 4) run(std::integral_constant<int, 4>{});
+  else run(std::integral_constant<int, 8>{});
   const int code = check_launch("region_scores");
   if (code != AURORA_OK) return code;
-  const int n_out = n_regions * kSlots;
-  const unsigned fin = (unsigned)(((int64_t)n_planes * n_out + kThreads - 1) / kThreads);
-  hipLaunchKernelGGL(region_finish_kernel, dim3(fin), dim3(kThreads), 0, s, partial, n_planes, (int)n_chunks, n_out, sums);
-  return check_launch("region_scores (finish)");
+  return finish_partials("region_scores", partial, n_planes, (int)plan.n_chunks, n_regions * kSlots, sums, s);
 }

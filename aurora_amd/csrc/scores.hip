@@ -6,7 +6,7 @@
 // products are formed in fp64 from the fp32 inputs; nothing is accumulated in fp32.
 //
 // A lane takes quads of columns (the quad rule of planes.h) and the sums go through the reduction tree of planes.h, four
-// waves to a workgroup; scores_finish_kernel is its second launch.
+// waves to a workgroup; finish_partials (eight sums to a chunk) is its second launch.
 #include "planes.h"
 
 namespace aurora {
@@ -15,10 +15,7 @@ namespace {
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / 64;
 constexpr int kSlots = kSumSlots;
-#ifndef AURORA_SCORES_CHUNK_ELEMS               // (a probe build may set it: AURORA_BUILD_FLAGS=-DAURORA_SCORES_CHUNK_ELEMS=...)
-#define AURORA_SCORES_CHUNK_ELEMS 40960
-#endif
-constexpr int kChunkElems = AURORA_SCORES_CHUNK_ELEMS;   // target size of a row chunk (elements of one input)
+constexpr int kChunkElems = kScoresChunkElems;  // target size of a row chunk (elements of one input)
 
 struct Acc {
   double s2 = 0.0, s3 = 0.0, s4 = 0.0, s5 = 0.0, s6 = 0.0, s7 = 0.0;
@@ -117,54 +114,33 @@ __global__ __launch_bounds__(kThreads) void scores_kernel(const float* const* __
   }
 }
 
-// sums[plane][slot] = partial[plane][0][slot] + partial[plane][1][slot] + ... in chunk order; one lane per (plane, slot).
-__global__ __launch_bounds__(kThreads) void scores_finish_kernel(const double* __restrict__ partial, int n_planes,
-                                                                 int n_chunks, double* __restrict__ sums) {
-  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
-  if (i >= (int64_t)n_planes * kSlots) return;
-  const int64_t plane = i / kSlots;
-  const int s = (int)(i % kSlots);
-  const double* p = partial + plane * n_chunks * kSlots + s;
-  double v = p[0];
-  for (int k = 1; k < n_chunks; ++k) v += p[(int64_t)k * kSlots];
-  sums[i] = v;
-}
-
 }  // namespace
 }  // namespace aurora
 
 using namespace aurora;
 
 extern "C" size_t aurora_hip_scores_workspace_bytes(int n_planes, int n_lat, int n_lon) {
-  if (n_planes < 1 || n_lat < 1 || n_lon < 1) return 0;
-  return (size_t)n_planes * (size_t)chunks_per_plane(n_lat, n_lon, kChunkElems, kWaves) * kSlots * sizeof(double);
+  return (size_t)chunk_plan(n_planes, n_lat, n_lon, kChunkElems, kWaves).groups * kSlots * sizeof(double);
 }
 
 extern "C" int aurora_hip_scores(const float* const* pred_planes, const float* const* truth_planes,
                                  const float* const* clim_planes, int n_planes, int n_lat, int n_lon, const double* row_w,
                                  double* sums, void* workspace, void* stream) {
-  AURORA_CHECK_ARG(n_planes >= 0 && n_lat >= 1 && n_lon >= 1, "scores: bad sizes (planes %d, grid %d x %d)", n_planes, n_lat,
-                   n_lon);
+  ChunkPlan plan;
+  if (const int code = plan_chunks("scores", n_planes, n_lat, n_lon, kChunkElems, kWaves, &plan)) return code;
   if (n_planes == 0) return AURORA_OK;
   AURORA_CHECK_ARG(pred_planes && truth_planes && row_w && sums && workspace,
                    "scores: null plane array, weight, output or workspace pointer");
   AURORA_CHECK_ARG(((uintptr_t)workspace & 7) == 0 && ((uintptr_t)sums & 7) == 0 && ((uintptr_t)row_w & 7) == 0,
                    "scores: weights, output and workspace must be 8-byte aligned");
-  const int64_t n_chunks = chunks_per_plane(n_lat, n_lon, kChunkElems, kWaves);
-  const int64_t groups = n_chunks * n_planes;
-  AURORA_CHECK_ARG(groups <= 0x7fffffff, "scores: too many planes for one launch (%d planes x %lld row chunks)", n_planes,
-                   (long long)n_chunks);
   double* const partial = (double*)workspace;
   if (clim_planes)
-    hipLaunchKernelGGL(scores_kernel<true>, dim3((unsigned)groups), dim3(kThreads), 0, as_stream(stream), pred_planes,
-                       truth_planes, clim_planes, n_lat, n_lon, (int)n_chunks, row_w, partial);
+    hipLaunchKernelGGL(scores_kernel<true>, dim3((unsigned)plan.groups), dim3(kThreads), 0, as_stream(stream), pred_planes,
+                       truth_planes, clim_planes, n_lat, n_lon, (int)plan.n_chunks, row_w, partial);
   else
-    hipLaunchKernelGGL(scores_kernel<false>, dim3((unsigned)groups), dim3(kThreads), 0, as_stream(stream), pred_planes,
-                       truth_planes, clim_planes, n_lat, n_lon, (int)n_chunks, row_w, partial);
+    hipLaunchKernelGGL(scores_kernel<false>, dim3((unsigned)plan.groups), dim3(kThreads), 0, as_stream(stream), pred_planes,
+                       truth_planes, clim_planes, n_lat, n_lon, (int)plan.n_chunks, row_w, partial);
   const int code = check_launch("scores");
   if (code != AURORA_OK) return code;
-  const unsigned fin = (unsigned)(((int64_t)n_planes * kSlots + kThreads - 1) / kThreads);
-  hipLaunchKernelGGL(scores_finish_kernel, dim3(fin), dim3(kThreads), 0, as_stream(stream), partial, n_planes, (int)n_chunks,
-                     sums);
-  return check_launch("scores (finish)");
+  return finish_partials("scores", partial, n_planes, (int)plan.n_chunks, kSlots, sums, as_stream(stream));
 }
