@@ -15,7 +15,9 @@ then take -- vorticity, divergence, wind speed, integrated vapour transport -- a
 longitude boxes and masks, as scorecards report them (aurora_amd/regions.py), and `conservative_regrid` brings a batch to the
 grid of its truth by area-weighted remapping, which `Batch.regrid`'s bilinear sampling is not made for
 (aurora_amd/conservative.py), and `objects` labels the connected regions of threshold exceedances -- storms, atmospheric rivers,
-heat domes -- with their sizes, centres and peaks (aurora_amd/objects.py); the reference has no counterpart.
+heat domes -- with their sizes, centres and peaks (aurora_amd/objects.py), and `field_quantiles` gives the spatial quantiles of
+every plane by area or by count, the percentile thresholds those event modules are fed (aurora_amd/field_quantiles.py); the
+reference has no counterpart.
 """
 
 from aurora_amd.batch import Batch, Metadata
@@ -24,6 +26,7 @@ from aurora_amd.conservative import conservative_regrid
 from aurora_amd.diagnostics import diagnostics
 from aurora_amd.ensemble import EnsembleScores, ensemble_scores
 from aurora_amd.events import EventScores, event_scores
+from aurora_amd.field_quantiles import FieldQuantiles, field_quantiles
 from aurora_amd.fieldstats import FieldStats
 from aurora_amd.model.aurora import (
     Aurora,
@@ -80,5 +83,7 @@ __all__ = [
     "conservative_regrid",
     "objects",
     "Objects",
+    "field_quantiles",
+    "FieldQuantiles",
     "Tracker",
 ]

@@ -1,5 +1,5 @@
 """What the verification front ends (`scores`, `ensemble_scores`, `ensemble_quantiles`, `event_scores`, `probability_scores`,
-`spectra`, `FieldStats`, `diagnostics`) share: coordinates and grid checks, the selection of the fields of a call, the
+`spectra`, `FieldStats`, `diagnostics`, `field_quantiles`) share: coordinates and grid checks, the selection of the fields of a call, the
 decision where they are reduced, the layout accessor, threshold tables, the fixed summation trees and the cache of small
 device tables.
 
@@ -160,6 +160,27 @@ def select_pair(fn: str, pred: Batch, others: Sequence[tuple[str, Batch]], only=
                     raise _differ(fn, "pred", what, k, fields[0][-1].shape, f.shape)
                 fields[slot].append(f)
     return names, fields, layout_of(names, fields[0])
+
+
+def select_one(fn: str, b: Batch, what: str = "batch", only=None):
+    """The last history entry of every variable (of `only`, if given, all of which `b` must hold) of ONE batch on a checked
+    grid, for the front ends that look at a field on its own: (names, fields, the layout)."""
+    n_lat, n_lon = b.metadata.lat.shape[0], b.metadata.lon.shape[0]
+    names, fields = [], []
+    for group in GROUPS:
+        for k, f in getattr(b, group).items():
+            if only is not None and k not in only:
+                continue
+            if k in names:
+                raise ValueError(f"{fn}: {k!r} is both a surface and an atmospheric variable")
+            check_field(fn, f, what, group, k, n_lat, n_lon)
+            names.append(k)
+            fields.append(f[:, -1])
+    for k in (only if only is not None else ()):
+        if k not in names:
+            raise ValueError(f"{fn}: only names the variable {k!r}, which {what} does not hold as a surface or atmospheric "
+                             "variable")
+    return names, fields, layout_of(names, fields)
 
 
 def select_members(fn: str, members, truth: Batch, only=None):

@@ -1,5 +1,6 @@
 // Plane access and fixed-order reduction shared by the verification kernels (scores, region_scores, conditional_scores,
-// ensemble_scores, ensemble_quantiles, probability_scores, event_scores, field_stats, spectra, diagnostics, objects) and the
+// ensemble_scores, ensemble_quantiles, probability_scores, event_scores, field_stats, spectra, diagnostics, objects,
+// field_quantiles) and the
 // two regrids.  Three contracts live here and nowhere else: the quad rule, the reduction tree (its one kernel and its launch
 // are in planes.hip) and the wind-speed expression.  A plane is n_lat x n_lon fp32, row-major, in global memory.
 #pragma once

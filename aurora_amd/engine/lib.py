@@ -160,6 +160,9 @@ _SIGNATURES = {
     "aurora_hip_objects_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int]),
     "aurora_hip_objects": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_void_p,
                                    c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
+    "aurora_hip_field_quantiles_workspace_bytes": (ctypes.c_size_t, [c_int, c_int]),
+    "aurora_hip_field_quantiles": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, ctypes.c_size_t, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1248,6 +1251,52 @@ def object_labels(fields: list[torch.Tensor], thresholds: torch.Tensor, unit: to
                                              1 if below else 0, int(connectivity), 1 if wrap else 0, max_objects, _ptr(labels),
                                              _ptr(count), _ptr(table), _ptr(workspace), workspace.numel(), _stream()))
     return labels, count, table
+
+
+# ---- spatial quantiles of planes (aurora_hip_field_quantiles) ------------------------------------------------------------------
+def field_quantiles_workspace_bytes(n_planes: int, n_q: int) -> int:
+    return int(load().aurora_hip_field_quantiles_workspace_bytes(n_planes, n_q))
+
+
+def field_quantile_values(fields: list[torch.Tensor], q, unit: Optional[torch.Tensor] = None, *, out=None,
+                          workspace: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The spatial quantiles (include/aurora_hip.h) of every plane of `fields`, in ONE aurora_hip_field_quantiles call: values
+    (n_planes, Q) fp32, valid (n_planes,) int64 and total (n_planes,) int64, on the device.
+
+    fields: a list of fp32 (..., n_lat, n_lon) tensors on one device with row-major contiguous planes (any leading strides,
+    any 4-byte plane alignment); q: 1 to 8 finite values in [0, 1] on the HOST (passed to the kernels by value); unit: contiguous
+    (n_lat,) int64 on that device, the area units of the rows (kind = area), or None (kind = count).  out: (values, valid,
+    total) to write into, contiguous and of those shapes; workspace: a uint8 tensor of at least
+    `field_quantiles_workspace_bytes` bytes -- both are allocated when not given (the workspace holds histograms only).  The
+    plane-pointer table is cached by address as in `scores_sums`.  The host does not wait for the device."""
+    assert fields, "field_quantile_values: the list of fields is empty"
+    qs = np.ascontiguousarray(q, dtype=np.float64).reshape(-1)
+    Q = qs.shape[0]
+    assert 1 <= Q <= QUANTILES_MAX, f"field_quantile_values: 1..{QUANTILES_MAX} values of q, got {Q}"
+    dev, (n_lat, n_lon) = fields[0].device, fields[0].shape[-2:]
+    assert unit is None or (unit.device == dev and unit.dtype == torch.int64 and tuple(unit.shape) == (n_lat,) and unit.is_contiguous()), \
+        "field_quantile_values: unit must be a contiguous (n_lat,) int64 vector on the device of the fields"
+    n, addresses = _plane_lists("field_quantile_values", [("field", fields)], dev, "the first field", n_lat, n_lon)
+    shapes, dtypes = ((n, Q), (n,), (n,)), (torch.float32, torch.int64, torch.int64)
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=dev) for s, d in zip(shapes, dtypes))
+    for t, s, d, what in zip(out, shapes, dtypes, ("values", "valid", "total")):
+        assert t.device == dev and t.dtype == d and tuple(t.shape) == s and t.is_contiguous(), \
+            f"field_quantile_values: {what} must be a contiguous {d} tensor of shape {s} on the device of the fields"
+    values, valid, total = out
+    if n == 0:
+        return values, valid, total
+    with torch.cuda.device(dev):
+        planes = _plane_table("field_quantile_values", tuple(addresses), dev)
+        if workspace is None:
+            workspace = torch.empty(field_quantiles_workspace_bytes(n, Q), dtype=torch.uint8, device=dev)
+        assert workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous(), \
+            "field_quantile_values: the workspace must be a contiguous uint8 tensor on the device of the fields"
+        with _Timed("field_quantiles", float(4 * n * n_lat * n_lon * 4)):
+            _check(load().aurora_hip_field_quantiles(planes.data_ptr(), n, n_lat, n_lon, _ptr(unit), qs.ctypes.data, Q,
+                                                     _ptr(values), _ptr(valid), _ptr(total), _ptr(workspace),
+                                                     workspace.numel(), _stream()))
+    return values, valid, total
 
 
 def probability_rows(members: list[list[torch.Tensor]], truth: list[torch.Tensor], thresholds: torch.Tensor,

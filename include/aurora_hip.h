@@ -1079,6 +1079,43 @@ int aurora_hip_objects(const float* const* planes, int n_planes, int n_lat, int 
                        int n_thresholds, const int64_t* unit, int below, int connectivity, int wrap, int max_objects,
                        int32_t* labels, int32_t* count, int64_t* table, void* workspace, size_t workspace_size, void* stream);
 
+/* ---- spatial quantiles of planes on the device (aurora_amd.field_quantiles: a plane's 0.9 / 0.99 quantile by area or by
+ * count, the percentile thresholds of the event modules; not in the reference) ------------------------------------------------
+ * Planes as above.  For every plane k < n_planes on its own:
+ *   VALIDITY  a point is valid where its value is finite: NaN and +-Inf drop out.  valid[k] = n is their number.
+ *   ORDER     by the 32-bit key K(v) of aurora_hip_objects: for the bits u of v, K = ~u if u has the sign bit, else
+ *             u | 0x80000000: ascending with the value, -0 below +0.
+ *   unit = NULL (kind = count): numpy's method = "linear" over the valid points, the expression of
+ *             aurora_hip_ensemble_quantiles with n in place of M.  For q_i: h = (double)(n - 1) q_i, j = min(floor(h), n - 1),
+ *             g = h - j, hi = min(j + 1, n - 1), and with a = (double)x_(j), b = (double)x_(hi)
+ *               values[k n_q + i] = (float)(a + g (b - a)),
+ *             the three fp64 operations rounded one by one (never an fma).  (j, g) are formed on the device, where n is known,
+ *             by these very operations.  n = 0 gives NaN.  total[k] = n.
+ *   unit != NULL (kind = area): unit[i] is the integer weight of row i (n_lat device int64, >= 0; aurora_amd.objects.area_units:
+ *             llrint(w_i 2^32)).  W = sum of unit over the valid points = total[k];
+ *               target = min(max((int64)ceil(q_i (double)W), 1), W),
+ *               values[k n_q + i] = the smallest valid x with U(x) = sum{unit : K <= K(x)} >= target
+ *             -- the inverted CDF, no interpolation.  W = 0 (no valid point, or all of them on rows of unit 0) gives NaN.
+ * q: n_q HOST doubles, 1 <= n_q <= 8, finite and in [0, 1], in any order, repeats allowed; they are passed to the kernels by
+ * value, so nothing is uploaded.  An exact radix select over K, most significant byte first, 8 bits per pass: a zeroing
+ * launch, then four passes that each read the planes once (16-byte loads where n_lon % 4 == 0 and the plane pointer is
+ * 16-byte aligned, 4-byte loads otherwise: the same elements either way) and fill 256-bin histograms of 64-bit integers in
+ * `workspace`, each followed by a small launch that picks every target's bin; nine launches on `stream`.  Everything that is
+ * accumulated is an integer, so values, valid and total are repeatable bit for bit, equal the rule above exactly, and depend
+ * on the plane's own values, unit and q alone: not on the other planes, the alignment of a plane pointer or the order of the
+ * atomics.  No launch waits on a value written within it; every loop is bounded by n_lat, n_lon, 256 or the number of targets.
+ * workspace: aurora_hip_field_quantiles_workspace_bytes(n_planes, n_q) device bytes (histograms only: (2 + 6 n_q) x 256 x 8
+ * bytes and a few hundred more per plane, never plane-sized; 8-byte aligned; cleared by the call's own first launch; 0 for
+ * an argument out of range); workspace_bytes: the bytes at `workspace`, refused if too few.  n_lat n_lon <= 2^31 - 2, and
+ * <= 2^30 with unit (the unit sum stays within int64).  values: n_planes x n_q device floats; valid, total: n_planes device
+ * int64.  Arguments are checked before anything is enqueued (AURORA_E_ARG and aurora_hip_last_error()).  n_planes = 0 is a
+ * no-op.  The inputs are not modified.  No plane-sized temporary, no host synchronisation, no allocation, no environment
+ * variable: capturable in a hipGraph. */
+size_t aurora_hip_field_quantiles_workspace_bytes(int n_planes, int n_q);
+int aurora_hip_field_quantiles(const float* const* planes, int n_planes, int n_lat, int n_lon, const int64_t* unit,
+                               const double* q, int n_q, float* values, int64_t* valid, int64_t* total, void* workspace,
+                               size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

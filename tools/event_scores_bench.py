@@ -19,7 +19,7 @@ import torch
 import torch.nn.functional as F
 from verification_bench import N_LAT, N_LON, N_PLANES, alternate, captured, med_min_max, planes, state, window_ms
 
-from aurora_amd import Batch, event_scores  # (verification_bench has put the repository on sys.path)
+from aurora_amd import Batch, event_scores, field_quantiles  # (verification_bench has put the repository on sys.path)
 from aurora_amd._fields import device_weights
 from aurora_amd.engine import lib
 
@@ -69,11 +69,9 @@ def main() -> None:
     truth = batch(0)
     pred = batch(1, truth, spread=0.5)
     P, T = planes(pred), planes(truth)
-    q = torch.tensor(QUANTILES, device="cuda")
-    thr_of = lambda v: torch.quantile(v[:, -1].reshape(-1, N_LAT * N_LON)[:, ::7], q, dim=1).T  # noqa: E731  (planes, T)
-    thresholds = {k: thr_of(v)[0].tolist() for k, v in truth.surf_vars.items()}
-    thresholds.update({k: thr_of(v).cpu().numpy() for k, v in truth.atmos_vars.items()})
-    thr = torch.cat([thr_of(v) for v in (*truth.surf_vars.values(), *truth.atmos_vars.values())]).float().contiguous()
+    fq = field_quantiles(truth, QUANTILES, kind="count")       # every plane's quantiles by count, where the plane lives
+    thresholds = fq.thresholds()
+    thr = fq.value_table                                       # (planes, T)
     row_w = device_weights("event_scores_bench", truth.metadata.lat.numpy(), torch.device("cuda", torch.cuda.current_device()))
 
     kernel = lambda: lib.event_rowsums(P, T, thr, SCALES)  # noqa: E731

@@ -5,7 +5,7 @@ levels of one atmospheric variable), at T = 1 and T = 3 thresholds, connectivity
 
 State and timing: tools/verification_bench.py.  The fields are smooth (a k^-2.5 amplitude spectrum in both directions), so that
 the objects are few and large as those of a weather field; thresholds are each plane's 0.9 (T = 1) or 0.5 / 0.9 / 0.99 (T = 3)
-quantiles.  Kernel arm: the ONE aurora_hip_objects call over all planes and thresholds with outputs and workspace allocated
+quantiles by count, from `field_quantiles` on the device.  Kernel arm: the ONE aurora_hip_objects call over all planes and thresholds with outputs and workspace allocated
 beforehand, captured in a hipGraph.  Measured against, in the same session: (a) the time one read of the inputs plus one write
 of the labels would take at the rate aurora_hip_scores reaches on the same planes (a streaming floor: the call also writes and
 re-reads its 4-byte-per-point workspace several times); (b) scipy.ndimage.label on the host, the transfer of the plane counted,
@@ -20,7 +20,7 @@ import numpy as np
 import torch
 from verification_bench import LEVELS, N_LAT, N_LON, SURF, alternate, captured, med_min_max, metadata, window_ms
 
-from aurora_amd import Batch, objects  # (verification_bench has put the repository on sys.path)
+from aurora_amd import Batch, field_quantiles, objects  # (verification_bench has put the repository on sys.path)
 from aurora_amd.engine import lib
 
 mod = importlib.import_module("aurora_amd.objects")       # (the package's attribute of this name is the function)
@@ -39,9 +39,8 @@ def smooth(g: torch.Generator, *lead) -> torch.Tensor:
 def case(T: int, batch: Batch, calls: int, repeats: int) -> dict:
     fields = [v[:, -1] for v in (*batch.surf_vars.values(), *batch.atmos_vars.values())]
     flat = torch.cat([f.reshape(-1, N_LAT * N_LON) for f in fields])
-    qs = torch.tensor([0.9] if T == 1 else [0.5, 0.9, 0.99], device="cuda")
-    thr_host = np.stack([np.quantile(p, qs.cpu().numpy()) for p in flat.cpu().numpy()]).astype(np.float32)
-    thr = torch.from_numpy(thr_host).cuda()
+    thr = field_quantiles(batch, (0.9,) if T == 1 else (0.5, 0.9, 0.99), kind="count").value_table   # (planes, T), on the device
+    thr_host = thr.cpu().numpy()
     lat = batch.metadata.lat.numpy()
     unit = torch.from_numpy(mod.area_units(lat)).cuda()
     M = 4096
