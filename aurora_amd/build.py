@@ -16,7 +16,7 @@ from pathlib import Path
 PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "_lib" / "libaurora_hip.so"
-SOURCES = ("runtime.hip", "gemm.hip", "gemm_f32.hip", "gemm_ln512.hip", "gemm_a4.hip", "attention.hip", "norm.hip", "embed.hip", "perceiver_out.hip", "band.hip",
+SOURCES = ("runtime.hip", "gemm.hip", "gemm_f32.hip", "gemm_ln512.hip", "gemm_a4.hip", "attention.hip", "norm.hip", "embed.hip", "perceiver_attention.hip", "perceiver_out.hip", "band.hip",
            "model.hip", "model_weights.hip", "model_grid.hip", "step.hip", "regrid.hip", "conservative_regrid.hip", "planes.hip", "scores.hip", "ensemble_scores.hip", "ensemble_quantiles.hip", "spectra.hip", "event_scores.hip",
            "field_stats.hip", "probability_scores.hip", "diagnostics.hip", "conditional_scores.hip", "region_scores.hip", "objects.hip", "field_quantiles.hip")
 ARCH = "gfx950"
@@ -49,7 +49,7 @@ def build_library(force: bool = False, verbose: bool = True) -> Path:
     procs = []
     for src in SOURCES:
         obj = LIB.parent / (src.replace(".hip", ".o"))
-        # (AURORA_BUILD_FLAGS: extra compiler flags of a probe build, e.g. -DPO_STAMPS for tools/probes/po_stamps.py)
+        # (AURORA_BUILD_FLAGS: extra compiler flags of a probe build, e.g. -DAURORA_SCORES_CHUNK_ELEMS=... of planes.h)
         cmd = [_hipcc(), *COMPILE_FLAGS, *os.environ.get("AURORA_BUILD_FLAGS", "").split(), "-c", str(CSRC / src), "-o", str(obj)]
         if verbose:
             print(" ".join(cmd), flush=True)

@@ -148,7 +148,7 @@ void build_heads(Model& m, HeadGroup& hg, const char* kind, const std::vector<st
 //   [ W_v  |  one row W_k,h^T q_l,h / sqrt(head_dim) per (query l, head h)  |  zero rows up to a multiple of 256 ]
 // -- Lq * heads rows instead of heads * head_dim: 48 instead of 512 in the encoder's level aggregation, 208 instead of 1,024 in
 // the decoder's de-aggregation -- and a context row leaves that linear with its values and its SCALED SCORES against every
-// query (embed.hip: perceiver_attention_scores_kernel; perceiver_out.hip: perceiver_probs_kernel<.., true>).  The rows are
+// query (perceiver_attention.hip: perceiver_attention_scores_kernel; perceiver_out.hip: perceiver_probs_kernel<.., true>).  The rows are
 // summed in double on the host (64 terms each) and rounded once.  Not with a LayerNorm on the keys (`ln_k_q`), and only where
 // the pre-split form exists iff to_kv's does (a context in the fp16-pair layout needs pre-split weights, step.hip).
 void score_weights(Model& m, Resampler& r, const float* q0, int Lq, int heads) {

@@ -35,7 +35,7 @@
 #include <type_traits>
 #include <utility>
 
-#include "common.h"
+#include "perceiver.h"
 
 namespace aurora {
 
@@ -51,10 +51,6 @@ constexpr int PO_NST = 4;                   // two heads
 constexpr int PO_PS = 64;                   // floats of P per (column, head): [l][4], padded (Lq <= 16)
 constexpr int PO_PTILE = PO_COLS * PO_PS * 4;   // 8 KiB: the 32 columns' weights of one head
 constexpr int PO_LDS = PO_NST * PO_STAGE + 2 * PO_PTILE;   // 144 KiB
-
-#ifdef PO_STAMPS   // probe build (AURORA_BUILD_FLAGS=-DPO_STAMPS): tools/probes/po_stamps.py
-__device__ uint32_t po_stamps[8 * 256];
-#endif
 
 struct PercOutArgs {
   const char* V; int64_t ldv_b;     // value rows in the fp16-pair layout: row col * 3 + j
@@ -255,27 +251,15 @@ __global__ __launch_bounds__(PO_THREADS, 2) void perceiver_out_kernel(const Perc
   // stage st, into the ring slot of stage st - 1 (last read a barrier before), and ends that R waiting until only the pieces
   // of stages st + 2 and st + 3 are in flight: stage st + 1 is complete, for every wave, a barrier before its first reader.
   // P of head h travels with stage 2 h.
-  // Measured (s_memtime stamps, 0.25 degree shape, tools/probes/po_stamps.py on a -DPO_STAMPS build of round 6): R ~450-550
-  // cycles, C ~800-900 (24 MFMAs alone: ~400; the 70 VALU instructions alone: ~410 -- they add up, see the file header),
+  // Measured (s_memtime stamps at the slot boundaries, 0.25 degree shape: tools/probes/po_stamps.py on a -DPO_STAMPS build; those
+  // probe blocks left this kernel with the commit of profiles/perceiver_units_same_code.log, commit 9ac2471 before it still
+  // builds them): R ~450-550 cycles, C ~800-900 (24 MFMAs alone: ~400; the 70 VALU instructions alone: ~410 -- they add up, see the file header),
   // ~100 per barrier.  Also measured and not kept: the combine in R instead of C (M = MFMAs only: +7 %), the combine's
   // instructions dealt out singly between the MFMAs (+13 %), one slot per stage (+10 %).
   constexpr int NF = 2 * NLP;   // (key, level pair) steps per row fragment
   const int n_st = 2 * heads;
-#ifdef PO_STAMPS
-  int sidx = 0;
-  auto stamp = [&]() {   // slot boundaries of workgroup 4000, per wave, through spare LDS
-    if (blockIdx.x == 4000) {
-      const uint64_t t = __builtin_amdgcn_s_memtime();
-      if (lane == 0) reinterpret_cast<uint32_t*>(smem + PO_LDS)[wave * 256 + sidx] = (uint32_t)t;
-    }
-    ++sidx;
-  };
-#else
-  auto stamp = [&]() {};
-#endif
   auto phase = [&](int st, auto KS, f32x4 (&U)[2][4], f32x2 (&pr)[2], f32x4 (&Un)[2][4], f32x2 (&prn)[2]) {
     constexpr int ks = decltype(KS)::value;
-    stamp();
     // ---- R: this stage's fragments (+ the head's weights), the LDS-DMA of stage st + 3; the SIMD partner computes meanwhile ----
     const char* buf = smem + (st & (PO_NST - 1)) * PO_STAGE;
     u32x4 vh[2], vl[2], wh[4], wl[4];
@@ -302,11 +286,9 @@ __global__ __launch_bounds__(PO_THREADS, 2) void perceiver_out_kernel(const Perc
     else if (nx == n_st) asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
     else asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_sched_barrier(0);
-    stamp();
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("" ::: "memory");
-    stamp();
     // ---- C: 24 MFMAs into Un, the steps of the previous head's combine between them; the partner reads ----
     // (the asm FMAs are invisible to hipcc's hazard recogniser -- a matrix result may be read 11 states after its MFMA issued --:
     //  the products they read were finished at least a stage and two barriers ago)
@@ -324,7 +306,6 @@ __global__ __launch_bounds__(PO_THREADS, 2) void perceiver_out_kernel(const Perc
       if constexpr (i == 23) base_add(U, std::integral_constant<int, ks>{});
       __builtin_amdgcn_sched_barrier(0);
     });
-    stamp();
     __builtin_amdgcn_s_barrier();
     __builtin_amdgcn_sched_barrier(0);
     asm volatile("" ::: "memory");
@@ -361,12 +342,6 @@ __global__ __launch_bounds__(PO_THREADS, 2) void perceiver_out_kernel(const Perc
   auto level = [&](int mt, int nt, int l) -> float { return l < 2 * NFULL ? out2[mt][nt][l >> 1][l & 1] : outl[mt][nt]; };
   if (late == 0) __builtin_amdgcn_s_barrier();   // (every wave passes the same number of barriers)
 
-#ifdef PO_STAMPS
-  if (blockIdx.x == 4000) {
-    __syncthreads();
-    for (int i = tid; i < 8 * 256; i += PO_THREADS) po_stamps[i] = reinterpret_cast<uint32_t*>(smem + PO_LDS)[i];
-  }
-#endif
   // ---- result: undo the 2^6 weight scale (exact), bias; 16 bytes per (column, level): features n .. n + 3 ----
   const int n = n0 + wn * 64 + 4 * i16;
   f32x4 b4 = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -390,7 +365,7 @@ __global__ __launch_bounds__(PO_THREADS, 2) void perceiver_out_kernel(const Perc
 // ------------------------------------------------------------------------------------------------------------------
 // Softmax weights of the level queries over a column's (three) keys, and the column's values as fp16 pairs.
 // A group of 16 adjacent lanes owns one (column, head): a lane holds 4 of the head's 64 features (the layout of
-// perceiver_attention_kernel, embed.hip: a group reads a key / value row as one contiguous 256-byte run).
+// perceiver.h: a group reads a key / value row as one contiguous 256-byte run).
 // ------------------------------------------------------------------------------------------------------------------
 struct PercProbArgs {
   const float* q; const float* kv; float* P; char* Vp;
@@ -399,18 +374,7 @@ struct PercProbArgs {
   int64_t ld; int s_off;   // SCORES: a context row is [v (inner) | ... | scores at s_off], ld floats apart (else k | v, 2 inner)
 };
 
-__device__ __forceinline__ float group16_sum(float v) {
-  auto dpp = [](float x, auto ctrl) {
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), decltype(ctrl)::value, 0xf, 0xf, true));
-  };
-  v += dpp(v, std::integral_constant<int, 0x140>{});   // row_mirror: i <-> 15 - i
-  v += dpp(v, std::integral_constant<int, 0x141>{});   // row_half_mirror: i <-> 7 - i
-  v += dpp(v, std::integral_constant<int, 0x1B>{});    // quad_perm [3,2,1,0]
-  v += dpp(v, std::integral_constant<int, 0xB1>{});    // quad_perm [1,0,3,2]
-  return v;
-}
-
-// SCORES: the scaled scores q_l . k_j arrive pre-multiplied in the context rows (embed.hip, perceiver_attention_scores_kernel:
+// SCORES: the scaled scores q_l . k_j arrive pre-multiplied in the context rows (perceiver_attention.hip, perceiver_attention_scores_kernel:
 // the queries of a first layer are model constants); lane i of a group then owns level i -- its three scores are three
 // loads, its softmax needs no other lane.
 template <int LQ, bool SCORES>
@@ -451,19 +415,16 @@ __global__ __launch_bounds__(256) void perceiver_probs_kernel(const PercProbArgs
     w1 = e[1] * inv;
   };
   if constexpr (SCORES) {
-    auto dpp = [](float x, auto ctrl) {
-      return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), decltype(ctrl)::value, 0xf, 0xf, true));
-    };
     const int lq = i16 < LQ ? i16 : LQ - 1;   // (lanes past the last level repeat it; their weights are zeroed below)
     float sc[LK];
 #pragma unroll
     for (int j = 0; j < LK; ++j) sc[j] = row0[j * kv_step + p.s_off + lq * p.heads + h];
     float w0, w1;
     weights(sc, w0, w1);
-    const float p00 = dpp(w0, std::integral_constant<int, 0x150>{}), p10 = dpp(w1, std::integral_constant<int, 0x150>{});   // row_newbcast:0
+    const float p00 = dpp_move<DPP_ROW_BCAST0>(w0), p10 = dpp_move<DPP_ROW_BCAST0>(w1);
     if (i16 > 0) { w0 -= p00; w1 -= p10; }
     if (i16 >= LQ) w0 = w1 = 0.f;
-    const float n0 = dpp(w0, std::integral_constant<int, 0xB1>{}), n1 = dpp(w1, std::integral_constant<int, 0xB1>{});   // lane i ^ 1
+    const float n0 = dpp_move<DPP_PAIR_SWAP>(w0), n1 = dpp_move<DPP_PAIR_SWAP>(w1);   // lane i ^ 1
     // lane 2 lp writes pairs lp and NLP + lp; the lanes from 2 NLP on zero the pairs of their own number (all 16 pairs that
     // perceiver_out_kernel's lanes read are defined)
     if (i16 >= 2 * NLP) *reinterpret_cast<float2*>(prow + i16 * 2) = make_float2(0.f, 0.f);
@@ -484,7 +445,7 @@ __global__ __launch_bounds__(256) void perceiver_probs_kernel(const PercProbArgs
       float sc[LK];
 #pragma unroll
       for (int j = 0; j < LK; ++j)
-        sc[j] = group16_sum(fmaf(qv[0], kk[j][0], fmaf(qv[1], kk[j][1], fmaf(qv[2], kk[j][2], qv[3] * kk[j][3])))) * scale;
+        sc[j] = group_sum<HDIM / 4>(fmaf(qv[0], kk[j][0], fmaf(qv[1], kk[j][1], fmaf(qv[2], kk[j][2], qv[3] * kk[j][3])))) * scale;
       float w0, w1;
       weights(sc, w0, w1);
       if (c == 0) { p00 = w0; p10 = w1; }
@@ -519,13 +480,6 @@ __global__ __launch_bounds__(256) void perceiver_probs_kernel(const PercProbArgs
 }  // namespace aurora
 
 using namespace aurora;
-
-#ifdef PO_STAMPS
-extern "C" void aurora_hip_debug_po_stamps(void* dst) { (void)hipMemcpyFromSymbol(dst, HIP_SYMBOL(po_stamps), sizeof(po_stamps)); }
-constexpr int PO_LDS_LAUNCH = PO_LDS + 8192;
-#else
-constexpr int PO_LDS_LAUNCH = PO_LDS;
-#endif
 
 extern "C" int aurora_hip_perceiver_out_supported(int Lq, int Lk, int heads, int head_dim, int N) {
   return (Lq == 3 || Lq == 4 || Lq == 13) && Lk == 3 && head_dim == 64 && heads >= 2 && heads % 2 == 0 && N > 0 && N % PO_N == 0;
@@ -568,10 +522,8 @@ extern "C" int aurora_hip_perceiver_probs_scores(const float* vs, int64_t ld_vs,
   AURORA_CHECK_ARG(aurora_hip_perceiver_out_supported(Lq, Lk, heads, head_dim, PO_N),
                    "perceiver_probs_scores: Lq=%d Lk=%d head_dim=%d (built for Lq in {3, 4, 13}, Lk = 3, head_dim 64)", Lq, Lk,
                    head_dim);
-  AURORA_CHECK_ARG(vs && P && Vp && B > 0 && cols_per_b > 0 && ((uintptr_t)vs % 16) == 0 && ((uintptr_t)P % 16) == 0 &&
-                       ((uintptr_t)Vp % 16) == 0 && ld_vs % 4 == 0 && s_off >= heads * head_dim &&
-                       ld_vs >= (int64_t)s_off + (int64_t)Lq * heads,
-                   "perceiver_probs_scores: a row is [v (heads * head_dim) | ... | scores (Lq * heads) at s_off], ld %% 4 == 0");
+  const bool given = vs && P && Vp && B > 0 && cols_per_b > 0 && ((uintptr_t)P % 16) == 0 && ((uintptr_t)Vp % 16) == 0;
+  if (const int rc = check_scores_row("perceiver_probs_scores", vs, ld_vs, s_off, Lq, heads, head_dim, given)) return rc;
   PercProbArgs p{nullptr, vs, P, (char*)Vp, B, cols_per_b, kv_bstride, kv_lstride, heads, guard, guard_limit, ld_vs, s_off};
   return launch_probs(p, Lq, true, stream);
 }
@@ -592,15 +544,15 @@ extern "C" int aurora_hip_perceiver_out(const void* Vp, const void* W_pairs, int
   p.n_blocks = ((n_cols + PO_COLS - 1) / PO_COLS) * p.tiles_n;
   AURORA_CHECK_ARG(p.n_blocks < (int64_t)1 << 31, "perceiver_out: too many tiles");
   once_per_device([] {
-    (void)hipFuncSetAttribute((const void*)perceiver_out_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, PO_LDS_LAUNCH);
-    (void)hipFuncSetAttribute((const void*)perceiver_out_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, PO_LDS_LAUNCH);
-    (void)hipFuncSetAttribute((const void*)perceiver_out_kernel<13>, hipFuncAttributeMaxDynamicSharedMemorySize, PO_LDS_LAUNCH);
+    (void)hipFuncSetAttribute((const void*)perceiver_out_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, PO_LDS);
+    (void)hipFuncSetAttribute((const void*)perceiver_out_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, PO_LDS);
+    (void)hipFuncSetAttribute((const void*)perceiver_out_kernel<13>, hipFuncAttributeMaxDynamicSharedMemorySize, PO_LDS);
   });
   const dim3 grid((unsigned)p.n_blocks), block(PO_THREADS);
   switch (Lq) {
-    case 3: hipLaunchKernelGGL(perceiver_out_kernel<3>, grid, block, PO_LDS_LAUNCH, as_stream(stream), p); break;
-    case 4: hipLaunchKernelGGL(perceiver_out_kernel<4>, grid, block, PO_LDS_LAUNCH, as_stream(stream), p); break;
-    default: hipLaunchKernelGGL(perceiver_out_kernel<13>, grid, block, PO_LDS_LAUNCH, as_stream(stream), p); break;
+    case 3: hipLaunchKernelGGL(perceiver_out_kernel<3>, grid, block, PO_LDS, as_stream(stream), p); break;
+    case 4: hipLaunchKernelGGL(perceiver_out_kernel<4>, grid, block, PO_LDS, as_stream(stream), p); break;
+    default: hipLaunchKernelGGL(perceiver_out_kernel<13>, grid, block, PO_LDS, as_stream(stream), p); break;
   }
   return check_launch("perceiver_out");
 }

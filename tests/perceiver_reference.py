@@ -1,4 +1,4 @@
-"""fp64 definition of the Perceiver kernels of csrc/embed.hip and csrc/perceiver_out.hip, the cases and inputs their GPU tests
+"""fp64 definition of the Perceiver kernels of csrc/perceiver_attention.hip and csrc/perceiver_out.hip, the cases and inputs their GPU tests
 use, CPU models of their rounding points, and wrong variants.
 
 Plain torch on the CPU, NOT through F.scaled_dot_product_attention.  Per (b, column, head):

@@ -1,4 +1,4 @@
-"""The Perceiver kernels of csrc/embed.hip and csrc/perceiver_out.hip against the fp64 reference of tests/perceiver_reference.py.
+"""The Perceiver kernels of csrc/perceiver_attention.hip and csrc/perceiver_out.hip against the fp64 reference of tests/perceiver_reference.py.
 
   perceiver_attention_kernel<T, HDIM, QC, FEWK>     test_attention (the covering list of R.attention_cases: every Lq, Lk and head
                                                     count meets every instantiation it can reach, fp32 and bf16), test_strides

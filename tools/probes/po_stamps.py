@@ -1,4 +1,6 @@
-"""Slot stamps of perceiver_out_kernel (a probe build: AURORA_BUILD_FLAGS=-DPO_STAMPS python -m aurora_amd.build --force): per wave, per K-stage: start of R, end of R, start of C, end of C."""
+"""Slot stamps of perceiver_out_kernel (a probe build: AURORA_BUILD_FLAGS=-DPO_STAMPS python -m aurora_amd.build --force): per wave, per K-stage: start of R, end of R, start of C, end of C.
+
+The -DPO_STAMPS blocks and aurora_hip_debug_po_stamps left perceiver_out.hip with the commit of profiles/perceiver_units_same_code.log; run this against a library built from commit 9ac2471 before it."""
 import ctypes
 import sys
 from pathlib import Path
