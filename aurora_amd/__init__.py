@@ -16,8 +16,10 @@ longitude boxes and masks, as scorecards report them (aurora_amd/regions.py), an
 grid of its truth by area-weighted remapping, which `Batch.regrid`'s bilinear sampling is not made for
 (aurora_amd/conservative.py), and `objects` labels the connected regions of threshold exceedances -- storms, atmospheric rivers,
 heat domes -- with their sizes, centres and peaks (aurora_amd/objects.py), and `field_quantiles` gives the spatial quantiles of
-every plane by area or by count, the percentile thresholds those event modules are fed (aurora_amd/field_quantiles.py); the
-reference has no counterpart.
+every plane by area or by count, the percentile thresholds those event modules are fed (aurora_amd/field_quantiles.py), and
+`object_matches` pairs the objects of two fields -- forecast and truth, or step t and step t + 1 -- by their overlap: intersection
+over union, best partner, object POD / FAR / CSI, centroid displacement (aurora_amd/object_matches.py); the reference has no
+counterpart.
 """
 
 from aurora_amd.batch import Batch, Metadata
@@ -38,6 +40,7 @@ from aurora_amd.model.aurora import (
     AuroraSmallPretrained,
     AuroraWave,
 )
+from aurora_amd.object_matches import ObjectMatches, object_matches
 from aurora_amd.objects import Objects, objects
 from aurora_amd.probability import ProbabilityScores, probability_scores
 from aurora_amd.quantiles import EnsembleQuantiles, ensemble_quantiles
@@ -83,6 +86,8 @@ __all__ = [
     "conservative_regrid",
     "objects",
     "Objects",
+    "object_matches",
+    "ObjectMatches",
     "field_quantiles",
     "FieldQuantiles",
     "Tracker",

@@ -163,6 +163,9 @@ _SIGNATURES = {
     "aurora_hip_field_quantiles_workspace_bytes": (ctypes.c_size_t, [c_int, c_int]),
     "aurora_hip_field_quantiles": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p,
                                            c_void_p, ctypes.c_size_t, c_void_p]),
+    "aurora_hip_object_matches_workspace_bytes": (ctypes.c_size_t, [c_int64, c_int]),
+    "aurora_hip_object_matches": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
+                                          c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1251,6 +1254,55 @@ def object_labels(fields: list[torch.Tensor], thresholds: torch.Tensor, unit: to
                                              1 if below else 0, int(connectivity), 1 if wrap else 0, max_objects, _ptr(labels),
                                              _ptr(count), _ptr(table), _ptr(workspace), workspace.numel(), _stream()))
     return labels, count, table
+
+
+# ---- overlap pairs of two label maps (aurora_hip_object_matches) -----------------------------------------------------------------
+OBJECT_MAX_PAIRS, OBJECT_PAIR_COLUMNS = 8192, 4
+
+
+def object_matches_workspace_bytes(n_items: int, max_pairs: int) -> int:
+    return int(load().aurora_hip_object_matches_workspace_bytes(n_items, max_pairs))
+
+
+def object_pairs(labels_a: torch.Tensor, labels_b: torch.Tensor, unit: torch.Tensor, max_objects_a: int, max_objects_b: int,
+                 max_pairs: int, *, out=None, workspace: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """The overlap pairs (include/aurora_hip.h) of every item of two stacks of label maps, in ONE aurora_hip_object_matches call:
+    pairs (*lead, max_pairs, 4) int64 -- ka, kb, points, area units, ascending, zero past count -- and count (*lead) int32, -1
+    where an item has more than max_pairs, on the device.
+
+    labels_a, labels_b: contiguous int32 (*lead, n_lat, n_lon) tensors of one shape on one device (any 4-byte alignment), e.g.
+    the labels of `object_labels`; they need not be connected; unit: contiguous (n_lat,) int64 on that device, the area units of
+    the rows.  out: (pairs, count) to write into, contiguous and of those shapes; workspace: a uint8 tensor of at least
+    `object_matches_workspace_bytes` bytes -- both are allocated when not given (the workspace holds hash tables only: 48 to 96
+    bytes per pair of max_pairs and item).  The host does not wait for the device."""
+    assert labels_a.is_cuda and labels_a.dtype == torch.int32 and labels_a.dim() >= 2 and labels_a.is_contiguous(), \
+        "object_pairs: labels_a must be a contiguous (..., n_lat, n_lon) int32 tensor on the device"
+    dev, (n_lat, n_lon), lead = labels_a.device, labels_a.shape[-2:], tuple(labels_a.shape[:-2])
+    assert labels_b.device == dev and labels_b.dtype == torch.int32 and labels_b.shape == labels_a.shape and labels_b.is_contiguous(), \
+        f"object_pairs: labels_b must be a contiguous int32 tensor of shape {tuple(labels_a.shape)} on the device of labels_a"
+    assert unit.device == dev and unit.dtype == torch.int64 and tuple(unit.shape) == (n_lat,) and unit.is_contiguous(), \
+        "object_pairs: unit must be a contiguous (n_lat,) int64 vector on the device of labels_a"
+    max_objects_a, max_objects_b, max_pairs = int(max_objects_a), int(max_objects_b), int(max_pairs)
+    n = int(np.prod(lead, dtype=np.int64))
+    shapes, dtypes = ((*lead, max(max_pairs, 0), OBJECT_PAIR_COLUMNS), lead), (torch.int64, torch.int32)
+    if out is None:
+        out = tuple(torch.empty(s, dtype=d, device=dev) for s, d in zip(shapes, dtypes))
+    for t, s, d, what in zip(out, shapes, dtypes, ("pairs", "count")):
+        assert t.device == dev and t.dtype == d and tuple(t.shape) == s and t.is_contiguous(), \
+            f"object_pairs: {what} must be a contiguous {d} tensor of shape {s} on the device of labels_a"
+    pairs, count = out
+    if n == 0:
+        return pairs, count
+    with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = torch.empty(object_matches_workspace_bytes(n, max_pairs), dtype=torch.uint8, device=dev)
+        assert workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous(), \
+            "object_pairs: the workspace must be a contiguous uint8 tensor on the device of labels_a"
+        with _Timed("object_matches", float(8 * n * n_lat * n_lon)):   # bytes read: both maps once
+            _check(load().aurora_hip_object_matches(_ptr(labels_a), _ptr(labels_b), n, n_lat, n_lon, _ptr(unit), max_objects_a,
+                                                    max_objects_b, max_pairs, _ptr(count), _ptr(pairs), _ptr(workspace),
+                                                    workspace.numel(), _stream()))
+    return pairs, count
 
 
 # ---- spatial quantiles of planes (aurora_hip_field_quantiles) ------------------------------------------------------------------

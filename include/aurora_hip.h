@@ -1116,6 +1116,40 @@ int aurora_hip_field_quantiles(const float* const* planes, int n_planes, int n_l
                                const double* q, int n_q, float* values, int64_t* valid, int64_t* total, void* workspace,
                                size_t workspace_bytes, void* stream);
 
+/* ---- overlap pairs of two label maps on the device (aurora_amd.object_matches: which object of one field is which object of
+ * another, and how much they share; not in the reference) ----------------------------------------------------------------------
+ * labels_a, labels_b: n_items label maps each (an item is a plane and a threshold), n_lat x n_lon device int32, row-major, one
+ * after the other, as aurora_hip_objects writes them; the maps need not be connected.  For every item on its own a point of row
+ * i CONTRIBUTES where 1 <= la <= max_objects_a and 1 <= lb <= max_objects_b (any other value, negative ones and labels past
+ * the tables included, is ignored), to the pair (la, lb): one point and unit[i] area units (n_lat device int64, the units of
+ * aurora_hip_objects).
+ *   pairs[(item max_pairs + r) 4 + c]   int64: row r = [ka, kb, points, area_units] of the r-th pair in ascending (ka, kb)
+ *                                       order; rows past count are 0
+ *   count[item]                         int32: the number of pairs; -1 where there are more than max_pairs: the item OVERFLOWS
+ *                                       and all its rows are 0 (never a partial table, whose contents would depend on the
+ *                                       order of insertion)
+ * Hash aggregation in `workspace`, aurora_hip_object_matches_workspace_bytes(n_items, max_pairs) device bytes (8-byte aligned;
+ * cleared by the call's own first launch; 0 for an argument out of range): per item an open-addressed table of
+ * C = max(64, pow2ceil(2 max_pairs)) slots as 3 C + 1 words of 64 bits -- C key words (0 = empty, else (ka << 32) | kb), C points
+ * words, C units words and one overflow word.  THE HOME SLOT of a key is
+ *   home = (((uint64_t)ka << 32 | kb) * 0x9E3779B97F4A7C15) >> (64 - log2 C),
+ * the product taken modulo 2^64, with linear probing upwards that wraps from slot C - 1 to slot 0 (aurora_amd/csrc/pairs_hash.h).
+ * A key is claimed by one 64-bit compare-and-swap; the walk ends after C slots at the latest, then the overflow word is set and
+ * the contribution dropped.  Three launches on `stream` (zero, accumulate, finish): accumulate reads both maps once, four bytes
+ * at a time, a wavefront per row, the lanes that share a key combined first and a run carried across the row; finish gathers
+ * the keys of an item, sorts them in LDS (8 x max(2, pow2ceil(max_pairs)) bytes) and writes the rows.  Only 64-bit integers are
+ * accumulated, so pairs and count are repeatable bit for bit and depend on the item's own two maps and unit alone: not on the
+ * other items, not on the alignment of a map, not on the order in which workgroups run.  No launch waits on a value written
+ * within it; every loop is bounded by C, n_lon or 64.
+ * n_lat n_lon <= 2^31 - 2, max_objects_a, max_objects_b >= 1, 1 <= max_pairs <= 8192; workspace_size: the bytes at `workspace`,
+ * refused if too few.  Arguments are checked before anything is enqueued (AURORA_E_ARG and aurora_hip_last_error()), and then
+ * nothing is written.  n_items = 0 is a no-op.  The inputs are not modified.  No host synchronisation, no allocation, no
+ * environment variable: capturable in a hipGraph. */
+size_t aurora_hip_object_matches_workspace_bytes(int64_t n_items, int max_pairs);
+int aurora_hip_object_matches(const int32_t* labels_a, const int32_t* labels_b, int64_t n_items, int n_lat, int n_lon,
+                              const int64_t* unit, int max_objects_a, int max_objects_b, int max_pairs, int32_t* count,
+                              int64_t* pairs, void* workspace, size_t workspace_size, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
