@@ -18,14 +18,17 @@ grid of its truth by area-weighted remapping, which `Batch.regrid`'s bilinear sa
 heat domes -- with their sizes, centres and peaks (aurora_amd/objects.py), and `field_quantiles` gives the spatial quantiles of
 every plane by area or by count, the percentile thresholds those event modules are fed (aurora_amd/field_quantiles.py), and
 `object_matches` pairs the objects of two fields -- forecast and truth, or step t and step t + 1 -- by their overlap: intersection
-over union, best partner, object POD / FAR / CSI, centroid displacement (aurora_amd/object_matches.py); the reference has no
-counterpart.
+over union, best partner, object POD / FAR / CSI, centroid displacement (aurora_amd/object_matches.py), and `nearest_event` gives
+for every grid point the great-circle distance to the nearest event and which point that is, from which `object_separations`
+takes what objects that do not touch need: minimum boundary separation, Hausdorff distance, "nearest observed object within
+300 km" (aurora_amd/distances.py); the reference has no counterpart.
 """
 
 from aurora_amd.batch import Batch, Metadata
 from aurora_amd.conditional import ConditionalScores, conditional_scores
 from aurora_amd.conservative import conservative_regrid
 from aurora_amd.diagnostics import diagnostics
+from aurora_amd.distances import NearestEvent, ObjectSeparations, nearest_event, object_separations
 from aurora_amd.ensemble import EnsembleScores, ensemble_scores
 from aurora_amd.events import EventScores, event_scores
 from aurora_amd.field_quantiles import FieldQuantiles, field_quantiles
@@ -88,6 +91,10 @@ __all__ = [
     "Objects",
     "object_matches",
     "ObjectMatches",
+    "nearest_event",
+    "NearestEvent",
+    "object_separations",
+    "ObjectSeparations",
     "field_quantiles",
     "FieldQuantiles",
     "Tracker",

@@ -166,6 +166,11 @@ _SIGNATURES = {
     "aurora_hip_object_matches_workspace_bytes": (ctypes.c_size_t, [c_int64, c_int]),
     "aurora_hip_object_matches": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p,
                                           c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
+    "aurora_hip_nearest_event_workspace_bytes": (ctypes.c_size_t, [c_int64, c_int, c_int]),
+    "aurora_hip_nearest_event": (c_int, [c_void_p, c_int64, c_int, c_int, c_void_p, c_int, ctypes.c_double, c_void_p, c_void_p,
+                                         c_void_p, ctypes.c_size_t, c_void_p]),
+    "aurora_hip_object_separations": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p,
+                                              c_void_p, c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
@@ -1303,6 +1308,84 @@ def object_pairs(labels_a: torch.Tensor, labels_b: torch.Tensor, unit: torch.Ten
                                                     max_objects_b, max_pairs, _ptr(count), _ptr(pairs), _ptr(workspace),
                                                     workspace.numel(), _stream()))
     return pairs, count
+
+
+# ---- the nearest event of every point, the separations of objects (aurora_hip_nearest_event, aurora_hip_object_separations) ------
+NEAREST_MAX_LON, SEPARATION_COLUMNS = 4096, 3
+
+
+def nearest_event_workspace_bytes(n_items: int, n_lat: int, n_lon: int) -> int:
+    return int(load().aurora_hip_nearest_event_workspace_bytes(n_items, n_lat, n_lon))
+
+
+def nearest_event_maps(labels: torch.Tensor, tables: torch.Tensor, wrap: bool, key_max: float = float("inf"), *, out=None,
+                       workspace: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """The nearest event (include/aurora_hip.h) of every point of a stack of label maps, in ONE aurora_hip_nearest_event call:
+    index (*lead, n_lat, n_lon) int32 -- the flat index of the nearest point with label > 0, -1 for none -- and key, the same
+    shape in fp64 -- 1 - cos(angle), +inf for none -- on the device.
+
+    labels: a contiguous int32 (*lead, n_lat, n_lon) tensor on the device (any 4-byte alignment); tables: contiguous
+    (2 n_lat + n_lon,) fp64 on that device: sin(lat), max(cos(lat), 0), cos(d dlon); key_max: candidates beyond it are ignored
+    (a HOST number, passed by value).  out: (index, key) to write into, contiguous and of those shapes; workspace: a uint8 tensor
+    of at least `nearest_event_workspace_bytes` bytes -- both are allocated when not given (the workspace is plane-sized: 2 bytes
+    per point).  The host does not wait for the device."""
+    assert labels.is_cuda and labels.dtype == torch.int32 and labels.dim() >= 2 and labels.is_contiguous(), \
+        "nearest_event_maps: labels must be a contiguous (..., n_lat, n_lon) int32 tensor on the device"
+    dev, (n_lat, n_lon), lead = labels.device, labels.shape[-2:], tuple(labels.shape[:-2])
+    assert tables.device == dev and tables.dtype == torch.float64 and tuple(tables.shape) == (2 * n_lat + n_lon,) and tables.is_contiguous(), \
+        "nearest_event_maps: tables must be a contiguous (2 n_lat + n_lon,) fp64 vector on the device of labels"
+    n = int(np.prod(lead, dtype=np.int64))
+    dtypes = (torch.int32, torch.float64)
+    if out is None:
+        out = tuple(torch.empty(labels.shape, dtype=d, device=dev) for d in dtypes)
+    for t, d, what in zip(out, dtypes, ("index", "key")):
+        assert t.device == dev and t.dtype == d and t.shape == labels.shape and t.is_contiguous(), \
+            f"nearest_event_maps: {what} must be a contiguous {d} tensor of shape {tuple(labels.shape)} on the device of labels"
+    index, key = out
+    if n == 0:
+        return index, key
+    with torch.cuda.device(dev):
+        if workspace is None:
+            workspace = torch.empty(nearest_event_workspace_bytes(n, n_lat, n_lon), dtype=torch.uint8, device=dev)
+        assert workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous(), \
+            "nearest_event_maps: the workspace must be a contiguous uint8 tensor on the device of labels"
+        with _Timed("nearest_event", float(16 * n * n_lat * n_lon)):   # bytes: the map read once, the two maps written
+            _check(load().aurora_hip_nearest_event(_ptr(labels), n, n_lat, n_lon, _ptr(tables), 1 if wrap else 0, float(key_max),
+                                                   _ptr(index), _ptr(key), _ptr(workspace), workspace.numel(), _stream()))
+    return index, key
+
+
+def object_separation_table(labels_a: torch.Tensor, key: torch.Tensor, index: torch.Tensor, count_a: torch.Tensor,
+                            max_objects: int, *, out=None) -> tuple[torch.Tensor, torch.Tensor]:
+    """The separations (include/aurora_hip.h) of the objects of `labels_a` from the events whose nearest-event maps are `key` and
+    `index`, in ONE aurora_hip_object_separations call: table (*lead, max_objects, 3) int64 -- key bits, a_point, b_point -- and
+    hausdorff (*lead) int64, the greatest key of the item's events as bits, on the device.
+
+    labels_a, index: contiguous int32 (*lead, n_lat, n_lon) on one device; key: contiguous fp64 of that shape; count_a:
+    contiguous int32 (*lead).  out: (table, hausdorff) to write into.  The host does not wait for the device."""
+    assert labels_a.is_cuda and labels_a.dtype == torch.int32 and labels_a.dim() >= 2 and labels_a.is_contiguous(), \
+        "object_separation_table: labels_a must be a contiguous (..., n_lat, n_lon) int32 tensor on the device"
+    dev, (n_lat, n_lon), lead = labels_a.device, labels_a.shape[-2:], tuple(labels_a.shape[:-2])
+    for t, d, s, what in ((key, torch.float64, labels_a.shape, "key"), (index, torch.int32, labels_a.shape, "index"),
+                          (count_a, torch.int32, lead, "count_a")):
+        assert t.device == dev and t.dtype == d and tuple(t.shape) == tuple(s) and t.is_contiguous(), \
+            f"object_separation_table: {what} must be a contiguous {d} tensor of shape {tuple(s)} on the device of labels_a"
+    max_objects = int(max_objects)
+    n = int(np.prod(lead, dtype=np.int64))
+    shapes = ((*lead, max(max_objects, 0), SEPARATION_COLUMNS), lead)
+    if out is None:
+        out = tuple(torch.empty(s, dtype=torch.int64, device=dev) for s in shapes)
+    for t, s, what in zip(out, shapes, ("table", "hausdorff")):
+        assert t.device == dev and t.dtype == torch.int64 and tuple(t.shape) == s and t.is_contiguous(), \
+            f"object_separation_table: {what} must be a contiguous int64 tensor of shape {s} on the device of labels_a"
+    table, hausdorff = out
+    if n == 0:
+        return table, hausdorff
+    with torch.cuda.device(dev):
+        with _Timed("object_separations", float(32 * n * n_lat * n_lon)):   # bytes: label, key and index read twice
+            _check(load().aurora_hip_object_separations(_ptr(labels_a), _ptr(key), _ptr(index), _ptr(count_a), n, n_lat, n_lon,
+                                                        max_objects, _ptr(table), _ptr(hausdorff), _stream()))
+    return table, hausdorff
 
 
 # ---- spatial quantiles of planes (aurora_hip_field_quantiles) ------------------------------------------------------------------

@@ -1150,6 +1150,50 @@ int aurora_hip_object_matches(const int32_t* labels_a, const int32_t* labels_b, 
                               const int64_t* unit, int max_objects_a, int max_objects_b, int max_pairs, int32_t* count,
                               int64_t* pairs, void* workspace, size_t workspace_size, void* stream);
 
+/* ---- the nearest event of every grid point on the sphere, and the separations of objects (aurora_amd.nearest_event,
+ * aurora_amd.object_separations: minimum boundary separation, Hausdorff distance, "nearest observed object within 300 km"; not
+ * in the reference) ----------------------------------------------------------------------------------------------------------
+ * labels: n_items label maps as above; an EVENT is a point with label > 0.  tables: 2 n_lat + n_lon device doubles made on the
+ * host: s[i] = sin(lat_i), then c[i] = max(cos(lat_i), 0), then cd[d] = cos(d dlon) for d < n_lon with cd[0] = 1, for strictly
+ * monotone latitudes and equally spaced longitudes.  For every item on its own (THE RULE of aurora_amd/distances.py):
+ *   GAP        of columns j and j': d = |j - j'|, with wrap = 1 min(d, n_lon - d).
+ *   CANDIDATE  of target column j in source row k: the event of row k with the smallest gap, of two at the same gap the
+ *              smaller column; a row without events has none.
+ *   KEY        key(i, k, d) = 1 - (s_i s_k + (c_i c_k) cd[d]), every fp64 operation rounded on its own (never an fma),
+ *              negative results 0; a point that is itself an event is its own candidate with key exactly 0.
+ *   NEAREST    of (i, j): the row candidate with the smallest key, of equal keys the smallest flat index k n_lon + j';
+ *              candidates with key > key_max are ignored (key_max = +inf: no bound).
+ *   index[item n_lat n_lon + i n_lon + j]   int32: the flat index of the nearest event, -1 where there is none
+ *   key[...]                                fp64: its key, 1 - cos(angle); +inf where index is -1
+ * Three launches on `stream` (rows, extent, search): the candidates of every row as int16 in `workspace`,
+ * aurora_hip_nearest_event_workspace_bytes(n_items, n_lat, n_lon) device bytes (2 bytes per point, 4 per row, 8 per item;
+ * 8-byte aligned; no initialisation needed; 0 for an argument out of range); then every point walks the rows outward from its
+ * own and stops a direction at the first row whose zero-gap key exceeds min(best, key_max) by more than 2^-46, which proves
+ * that no farther row can win or tie (the derivation is in aurora_amd/csrc/nearest_event_search.h).  The walk is bounded by
+ * n_lat per direction, stays within the rows that have events, and waits for nobody; an item without events walks no row.
+ * index and key are repeatable bit for bit and depend on the item's own map and the tables alone.
+ *
+ * aurora_hip_object_separations: labels_a as above, key and index as written by aurora_hip_nearest_event for the OTHER map b,
+ * count_a[item] the number of objects of a (device int32).  For every object o <= max_objects of a, over its points:
+ *   table[(item max_objects + (o - 1)) 3 + c]   int64: 0 key_bits, the least key as the int64 of its fp64 bits (keys are not
+ *              negative, so they order like their bits); 1 a_point, the smallest flat index among the object's points that
+ *              attain it; 2 b_point = index[a_point].  Rows at or past count_a are 0; an object none of whose points has a
+ *              nearest event (or that has no point) is [bits of +inf, -1, -1].
+ *   hausdorff[item]                             int64: the greatest key over ALL events of a (labels past max_objects
+ *              included) as bits; 0 without events, the bits of +inf where an event has no nearest event.
+ * Four launches (init, least, point, finish); 64-bit integer minima and maxima by vector atomics only, the lanes of a wave
+ * that share a label combined first, so the result does not depend on the order of the atomics.  No workspace.
+ * 1 <= n_lon <= 4096 (nearest_event), n_lat n_lon <= 2^31 - 2, max_objects >= 1, key_max >= 0; workspace_size: the bytes at
+ * `workspace`, refused if too few.  Arguments are checked before anything is enqueued (AURORA_E_ARG and
+ * aurora_hip_last_error()), and then nothing is written.  n_items = 0 is a no-op.  The inputs are not modified.  No host
+ * synchronisation, no allocation, no environment variable: capturable in a hipGraph. */
+size_t aurora_hip_nearest_event_workspace_bytes(int64_t n_items, int n_lat, int n_lon);
+int aurora_hip_nearest_event(const int32_t* labels, int64_t n_items, int n_lat, int n_lon, const double* tables, int wrap,
+                             double key_max, int32_t* index, double* key, void* workspace, size_t workspace_size, void* stream);
+int aurora_hip_object_separations(const int32_t* labels_a, const double* key, const int32_t* index, const int32_t* count_a,
+                                  int64_t n_items, int n_lat, int n_lon, int max_objects, int64_t* table, int64_t* hausdorff,
+                                  void* stream);
+
 #ifdef __cplusplus
 }
 #endif
