@@ -133,12 +133,22 @@ struct Channel {
   int transform;           // aurora_hip_patchify transform code
   float tw0 = 0.f, tw1 = 0.f, tb = 0.f;
 };
+// The patch embedding folded into a linear that reads it (model_weights.hip:compose_front): W_c = W_ctx W_e per group and
+// the bias rows W_ctx (b_e + level_embed[c]) per level, summed in fp64 and rounded once.
+struct ComposedCtx {
+  DevBuf w, ws, bias;      // [groups][N][Kpad] fp32, its fp16-pair layout scaled by 2^6 (empty: not eligible), [levels][N]
+  int N = 0;
+  float v_l1 = 0.f, vb_max = 0.f;   // of the VALUE rows: largest L1 row norm, max |bias| -- |v| <= v_l1 max|input| + vb_max
+};
 // A LevelPatchEmbed weight as GEMM operand for one set of present channels and T history steps.
 struct EmbedPack {
   DevBuf w, ws;            // [groups][D][Kpad] fp32, and the same in the fp16-pair layout (scaled by 2^6) when eligible
   int K = 0, Kpad = 0, groups = 1;   // groups: 1, or one weight per pressure level (level-conditioned, levelcond.py)
   float l1 = 0.f;          // largest L1 row norm: |embedding| <= l1 * max|input| + |bias|
   std::vector<int> channels;   // indices into the channel list, in K order
+  // atmospheric pack, `compose_front` on and the rule of compose_front_rule met: one entry per layer of the level aggregation,
+  // which then reads the unfolded input itself -- the embedding is never launched (empty: today's two stages)
+  std::vector<ComposedCtx> composed;
 };
 // A surface / atmospheric output variable and the head columns it is decoded from (embed.hip unpatchify).
 struct HeadGroup {
@@ -233,6 +243,8 @@ struct aurora_hip_model {
   bool split_attention = false;
   bool qkv_planes = true;   // bf16 blocks: q | k | v leave the qkv linear one attention head per plane (aurora_hip_linear_planes)
   bool reassoc_out = true;  // decoder de-aggregation: to_out of the three value rows per column, combined in registers (perceiver_out.hip)
+  bool compose_front = true;   // encoder front: patch embedding folded into the level aggregation's context linears (model_weights.hip:compose_front)
+  bool front_composed = false; // what the last step did
   bool score_weights = true;   // first Perceiver layers: scores from W_k^T q rows instead of a key projection (model_weights.hip:score_weights)
 
   // per step
@@ -425,6 +437,18 @@ void score_weights(Model& m, Resampler& r, const float* q0, int Lq, int heads);
 void build_atmos_heads(Model& m, bool per_level);
 const AttnSet& attn_weights(Model& m, int key, void* stream);
 const EmbedPack& embed_pack(Model& m, int kind, int T, const std::vector<char>& present);
+// |v| <= a max|input| + c for the value rows a composed context linear writes: from the composed weight's own L1 row norms and
+// bias maxima, and never looser than what the two stages gave (a = v_l1 l1_e, c = v_l1 max|b|: the composed norms are below
+// these in exact arithmetic -- the induced norm is submultiplicative -- and `min` keeps it so in float).
+struct ValueBound {
+  float a, c;
+  float word_limit() const { return (F16_SAFE - c) / a; }   // a w + c < F16_SAFE  <=>  w < this
+};
+inline ValueBound composed_value_bound(float v_l1, float embed_l1, float embed_bias_max, float composed_v_l1, float composed_vb_max) {
+  return ValueBound{std::min(composed_v_l1, v_l1 * embed_l1), std::min(composed_vb_max, v_l1 * embed_bias_max)};
+}
+// Whether folding a (D, Kpad) embedding into the `n_layers` linears of N[i] rows that read it removes enough work.
+bool compose_front_rule(int Kpad, int D, const int* N, int n_layers);
 // model_grid.hip
 enum Expansion { POS, SCALE, LEAD_TIME, LEVELS, ABS_TIME };
 void fourier(Expansion kind, const double* x, int64_t n, int d, float* out);   // (n, d) Fourier features of `x`

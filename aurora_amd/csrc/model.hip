@@ -228,6 +228,7 @@ extern "C" int aurora_hip_create(const aurora_hip_config* c, aurora_hip_model** 
     m->split_k = sw(tu.split_k, true, "split_k");
     m->reassoc_out = sw(tu.perceiver_reassoc, true, "perceiver_reassoc");
     m->score_weights = sw(tu.score_weights, true, "score_weights");
+    m->compose_front = sw(tu.compose_front, true, "compose_front");
     m->tickets = DevBuf(SPLIT_TICKETS * sizeof(int32_t));
     hip_ok(hipMemset(m->tickets.p, 0, SPLIT_TICKETS * sizeof(int32_t)), "hipMemset");
     *out = m.release();

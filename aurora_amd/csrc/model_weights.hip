@@ -250,6 +250,76 @@ const AttnSet& attn_weights(Model& m, int key, void* stream) {
   return m.attn_sets.emplace(key, std::move(set)).first->second;
 }
 
+// ---- the encoder front composed: patch embedding folded into the level aggregation's context linears ----------------
+// Upstream the atmospheric embedding x = A W_e^T + b_e + level_embed[c] (encoder.py:305-326) is read by the level aggregation
+// alone (encoder.py:329), whose first operation on it is the bias-free `to_kv` (perceiver.py:117,142; `ln_k` comes behind the
+// projection).  Nothing nonlinear stands between the two, so for level c
+//   kv = A (W_ctx W_e[c])^T + W_ctx (b_e + level_embed[c])
+// with W_ctx what the layer multiplies its context by: [W_v | score rows] of score_weights, or to_kv.  One GEMM of K = Kpad
+// remains where a K = Kpad and a K = D one ran, and the embeddings (C B Lp rows of D) are neither written nor read.
+//
+// Worth it only where the composed linears do clearly less work than the two stages they replace: sum_i Kpad N_i against
+// Kpad D + sum_i D N_i multiply-adds per context row.  The margin is a factor of two: the composed launch splits its fp32
+// activation operand in the kernel (0.29 against 0.40 PFLOP/s for operands that arrive split), so at equal work
+// it would be the slower one, and it has to stay bound by its output store as the stages it replaces are.  Patch size 4
+// (Kpad 160, D 512, N 768) has 0.26 of the work and composes; patch size 10 (Kpad 1000) has 0.85 and keeps the two stages.
+bool compose_front_rule(int Kpad, int D, const int* N, int n_layers) {
+  if (Kpad <= 0 || D <= 0 || n_layers <= 0) return false;
+  double composed = 0.0, staged = (double)Kpad * D;
+  for (int i = 0; i < n_layers; ++i) {
+    if (N[i] <= 0) return false;
+    composed += (double)Kpad * N[i];
+    staged += (double)D * N[i];
+  }
+  return 2.0 * composed <= staged;
+}
+
+namespace {
+
+// Folds the embedding of `pk` into every layer of the encoder's level aggregation (all of them read the same context), or
+// into none: a layer that cannot be composed keeps today's path whole.
+void compose_front(Model& m, EmbedPack& pk) {
+  const Resampler& rs = m.enc_rs;
+  if (!m.compose_front || rs.layers.empty() || m.enc_bias.p == nullptr) return;
+  const int D = m.D, C = m.n_levels, Kpad = pk.Kpad;
+  std::vector<int> N;
+  for (size_t i = 0; i < rs.layers.size(); ++i) {
+    if (rs.layers[i].ctx_dim != D) return;
+    N.push_back(i == 0 && rs.n_vs > 0 ? rs.n_vs : 2 * rs.layers[i].inner);
+  }
+  if (!compose_front_rule(Kpad, D, N.data(), (int)N.size())) return;
+  const std::vector<float> we = to_host(pk.w.f(), (size_t)pk.groups * D * Kpad), eb = to_host(m.enc_bias.f(), (size_t)C * D);
+  std::vector<ComposedCtx> out;
+  for (size_t i = 0; i < rs.layers.size(); ++i) {
+    const auto& ly = rs.layers[i];
+    const bool scores = i == 0 && rs.n_vs > 0;
+    const int n = N[i], v0 = scores ? 0 : ly.inner;   // value rows: the first `inner` of [v | scores], the second half of k | v
+    const std::vector<float> wc = to_host(scores ? rs.vs_w.f() : ly.to_kv, (size_t)n * D);
+    std::vector<float> w((size_t)pk.groups * n * Kpad), b((size_t)C * n);
+    ok(aurora_hip_compose_weight(wc.data(), n, D, we.data(), Kpad, pk.groups, w.data()));
+    ok(aurora_hip_compose_bias(wc.data(), n, D, eb.data(), C, b.data()));
+    if (!(absmax(w) < PRESPLIT_W_MAX)) return;
+    ComposedCtx cc;
+    cc.N = n;
+    cc.v_l1 = 1e-6f;
+    for (int g = 0; g < pk.groups; ++g) {
+      const auto first = w.begin() + ((size_t)g * n + v0) * Kpad;
+      cc.v_l1 = max_row_l1(std::vector<float>(first, first + (size_t)ly.inner * Kpad), ly.inner, Kpad, cc.v_l1);
+    }
+    for (int c = 0; c < C; ++c)
+      for (int r = 0; r < ly.inner; ++r) cc.vb_max = std::max(cc.vb_max, fabsf(b[(size_t)c * n + v0 + r]));
+    cc.w = to_device(w);
+    cc.bias = to_device(b);
+    // in the fp16-pair form exactly where the stages it replaces are: the guarded chain is the same chain, one link shorter
+    if (ly.f16_mode == 2 && pk.ws.p != nullptr && (scores ? rs.vs_ws.p : ly.to_kv_s) != nullptr)
+      cc.ws = presplit(cc.w.f(), n, Kpad, Kpad, /*row_multiple=*/256, pk.groups);
+    out.push_back(std::move(cc));
+  }
+  pk.composed = std::move(out);
+}
+
+}  // namespace
+
 // (groups, D, Kpad) GEMM weight of a LevelPatchEmbed for the channels that are present and T history steps
 // (patchembed.py:100-115): per-variable (D, 1, Tmax, P, P) weights cut to T and laid out (v, t, i, j) along K, zero-padded
 // to a multiple of 32.  Level-conditioned models (levelcond.py:36-69) hold one such weight per pressure level.
@@ -292,6 +362,7 @@ const EmbedPack& embed_pack(Model& m, int kind, int T, const std::vector<char>& 
   // group is a GEMM of D rows, held to the 256 of the Perceiver weights: historical, kept
   if (bounded_mode() == 2 && absmax(host) < PRESPLIT_W_MAX)
     pk.ws = presplit(pk.w.f(), m.D, pk.Kpad, pk.Kpad, /*row_multiple=*/256, pk.groups);
+  if (kind == 1) compose_front(m, pk);
   return m.embed_packs.emplace(key, std::move(pk)).first->second;
 }
 
@@ -409,6 +480,56 @@ void feature_combiners(Model& m) {
 }  // namespace aurora
 
 using namespace aurora;
+
+// out[g][n][k] = sum_d w_ctx[n][d] w_e[g][d][k], summed in double in the order of d and rounded once.  Host arithmetic.
+extern "C" int aurora_hip_compose_weight(const float* w_ctx, int N, int D, const float* w_e, int K, int groups, float* out) {
+  GUARDED({
+    REQUIRE(w_ctx && w_e && out && N > 0 && D > 0 && K > 0 && groups > 0, "compose_weight: bad argument");
+    std::vector<double> acc((size_t)K);
+    for (int g = 0; g < groups; ++g)
+      for (int n = 0; n < N; ++n) {
+        std::fill(acc.begin(), acc.end(), 0.0);
+        for (int d = 0; d < D; ++d) {
+          const double a = w_ctx[(size_t)n * D + d];
+          const float* row = w_e + ((size_t)g * D + d) * K;
+          for (int k = 0; k < K; ++k) acc[k] += a * row[k];
+        }
+        float* dst = out + ((size_t)g * N + n) * K;
+        for (int k = 0; k < K; ++k) dst[k] = (float)acc[k];
+      }
+  })
+}
+
+// out[c][n] = sum_d w_ctx[n][d] bias[c][d], likewise.
+extern "C" int aurora_hip_compose_bias(const float* w_ctx, int N, int D, const float* bias, int C, float* out) {
+  GUARDED({
+    REQUIRE(w_ctx && bias && out && N > 0 && D > 0 && C > 0, "compose_bias: bad argument");
+    for (int c = 0; c < C; ++c)
+      for (int n = 0; n < N; ++n) {
+        double acc = 0.0;
+        for (int d = 0; d < D; ++d) acc += (double)w_ctx[(size_t)n * D + d] * bias[(size_t)c * D + d];
+        out[(size_t)c * N + n] = (float)acc;
+      }
+  })
+}
+
+extern "C" int aurora_hip_compose_front_rule(int Kpad, int D, const int32_t* N, int n_layers) {
+  return compose_front_rule(Kpad, D, N, n_layers) ? 1 : 0;
+}
+
+extern "C" int aurora_hip_composed_value_bound(float v_l1, float embed_l1, float embed_bias_max, float composed_v_l1,
+                                               float composed_vb_max, float out[6]) {
+  GUARDED({
+    REQUIRE(out && v_l1 > 0.f && embed_l1 > 0.f && composed_v_l1 > 0.f && embed_bias_max >= 0.f && composed_vb_max >= 0.f,
+            "composed_value_bound: bad argument");
+    const ValueBound staged{v_l1 * embed_l1, v_l1 * embed_bias_max}, folded = composed_value_bound(v_l1, embed_l1, embed_bias_max,
+                                                                                              composed_v_l1, composed_vb_max);
+    out[0] = staged.a; out[1] = staged.c; out[2] = (F16_SAFE / v_l1 - embed_bias_max) / embed_l1;
+    out[3] = folded.a; out[4] = folded.c; out[5] = folded.word_limit();
+  })
+}
+
+extern "C" int aurora_hip_front_composed(const aurora_hip_model* m) { return m != nullptr && m->front_composed ? 1 : 0; }
 
 extern "C" int aurora_hip_pack_weights(aurora_hip_model* m, const char* name, const void* data, const int64_t* shape, int ndim,
                                        int dtype, int on_device) {

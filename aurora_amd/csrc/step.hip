@@ -14,6 +14,10 @@ namespace aurora {
 namespace {
 
 struct CtxGuard { const float* word; float a, c, limit_kv; bool pairs; };
+// The context linears of the encoder's level aggregation with the patch embedding folded in (model_weights.hip:compose_front):
+// one ComposedCtx per layer, read over the `levels` row blocks (`rows` each) of the unfolded input, level c with its own bias
+// row and -- `groups` > 1 -- its own weight.  `embed_l1`, `embed_bias_max`: of the embedding, for the bound the stages gave.
+struct ComposedFront { const ComposedCtx* layers; int levels, groups; int64_t rows; float embed_l1, embed_bias_max; };
 
 // The workspace of layer `i` of `rs` (resampler_space.h) for one call of `resampler`.
 LayerSpace layer_space(const Model& m, const Resampler& rs, size_t i, int B, int64_t cols, int64_t ctx_rows, int Lq, int Lk,
@@ -68,7 +72,8 @@ void resampler_mlp(Model& m, Launcher& L, const Resampler::Layer& ly, const Laye
 // b*kv_bstride + j*kv_lstride + l.  First layer: latents (and so q) are shared by every column.  Returns (B*cols*Lq, D).
 float* resampler(Model& m, Launcher& L, const Resampler& rs, const float* ctx, int64_t ctx_rows, int ctx_dim, const float* q0,
                  const float* latents0, int B, int64_t cols, int64_t kv_bstride, int64_t kv_lstride, int Lq, int Lk, int heads,
-                 float eps, const CtxGuard* cg = nullptr, bool out_pairs = false, int own_word = 0, bool scan_ctx = true) {
+                 float eps, const CtxGuard* cg = nullptr, bool out_pairs = false, int own_word = 0, bool scan_ctx = true,
+                 const ComposedFront* front = nullptr) {
   const int64_t n_cols = (int64_t)B * cols, n_rows = n_cols * Lq;
   // The context is as unbounded as the model inputs, so the linears that read it, or averages of its value projection,
   // pick their operand split on the device: from max |ctx|, measured here, or from the bound the caller derived from a
@@ -109,8 +114,21 @@ float* resampler(Model& m, Launcher& L, const Resampler& rs, const float* ctx, i
     };
     // |ctx| <= g_a * word + g_c < F16_SAFE  <=>  word < (F16_SAFE - g_c) / g_a; a context in pairs comes with its own limit
     REQUIRE(!ctx_pairs || ly.to_kv_s, "resampler: a pair-layout context needs pre-split to_kv weights");
-    guarded(ctx, ctx_dim, scores ? rs.vs_w.f() : ly.to_kv, scores ? rs.vs_ws.p : ly.to_kv_s, kv, kv_ld, ctx_rows, kv_ld, ctx_dim,
-            ctx_pairs ? cg->limit_kv : (F16_SAFE - g_c) / g_a, ctx_pairs);
+    if (front) {
+      // `ctx` is the unfolded, normalised input itself (fp32: the two-term kernel splits it, as the embedding did), so the
+      // guard word bounds this linear's activation operand directly; one strided-batch launch over the levels
+      const ComposedCtx& cc = front->layers[i];
+      REQUIRE(cc.N == kv_ld && front->levels * front->rows == ctx_rows, "resampler: composed context weights of another shape");
+      LinearOp op = LinearOp(ctx, ctx_dim, cc.w.f(), ctx_dim, cc.bias.f(), kv, kv_ld, front->rows, kv_ld, ctx_dim, AURORA_F32)
+                        .batched(front->levels, front->rows * ctx_dim, front->groups > 1 ? (int64_t)kv_ld * ctx_dim : 0, kv_ld,
+                                 front->rows * kv_ld);
+      if (cc.ws.p) L.guarded_pair(op, cc.ws.p, 0, ctx_max, F16_SAFE);
+      else if (ly.f16_mode == 2) L.linear(op.f32_mode(2).guarded_by(ctx_max, F16_SAFE));
+      else L.linear(op.f32_mode(ly.f16_mode));   // (a pinned mode: no guard, as in `guarded`)
+    } else {
+      guarded(ctx, ctx_dim, scores ? rs.vs_w.f() : ly.to_kv, scores ? rs.vs_ws.p : ly.to_kv_s, kv, kv_ld, ctx_rows, kv_ld, ctx_dim,
+              ctx_pairs ? cg->limit_kv : (F16_SAFE - g_c) / g_a, ctx_pairs);
+    }
     if (ly.ln_k_w)   // LayerNorm over the K half, in place (perceiver.py:144-147)
       L.layernorm(kv, 2 * inner, ly.ln_k_w, ly.ln_k_b, nullptr, 0, 0, kv, 2 * inner, nullptr, 0, ctx_rows, inner, 1e-5f,
                   AURORA_F32);
@@ -126,7 +144,10 @@ float* resampler(Model& m, Launcher& L, const Resampler& rs, const float* ctx, i
     float* att = sp.att_in_y ? y : (float*)(S + sp.att_off);
     // |att| <= max |v| <= (largest L1 row norm of W_v) * max |ctx|: same guard, tighter limit.  With pre-split to_out
     // weights the attention writes fp16 pairs iff that guard holds, and to_out multiplies them without splitting anything.
-    const float lim_out = (F16_SAFE / ly.v_l1 - g_c) / g_a;
+    // (composed: |v| <= v_l1 max|input| + max|bias| of the COMPOSED value rows, never looser than the above: model.h)
+    const float lim_out = front ? composed_value_bound(ly.v_l1, front->embed_l1, front->embed_bias_max, front->layers[i].v_l1,
+                                                       front->layers[i].vb_max).word_limit()
+                                : (F16_SAFE / ly.v_l1 - g_c) / g_a;
     float* o = (float*)S;   // (k | v and q are dead)
     if (sp.reassoc) {
       // (the launch that writes P reads k | v, and to_out's result lands on [0, unit) while P is read)
@@ -321,10 +342,24 @@ const float* encode_levels(Step& s) {
   const int Kpad_a = pa.Kpad;
   bool chain = pa.ws.p != nullptr;
   for (const auto& ly : m.enc_rs.layers) chain = chain && ly.f16_mode == 2 && ly.to_kv_s != nullptr;
+  const bool composed = !pa.composed.empty();
+  m.front_composed = composed;
   float* word = m.ctx_max.f() + 1;   // max |normalised atmospheric input|, folded in by patchify when the chain is guarded
-  patchify(s, pa, true, A_a, chain ? word : nullptr);
-  float* xa = (float*)m.arena.take((size_t)C * B * s.Lp * D * 4);
+  patchify(s, pa, true, A_a, chain || composed ? word : nullptr);
   const int64_t R = (int64_t)B * s.Lp;
+  // The embedding folded into the level aggregation's context linears: no embedding launch, no embeddings in the arena --
+  // the resampler reads the unfolded input with the composed weights.  The guard is the same word, one link shorter: the
+  // activation operand of the context linear is the input itself (limit F16_SAFE), and the attention output's bound comes
+  // from the composed value rows.  Format and kernels still switch together on that word.
+  if (composed) {
+    REQUIRE(pa.composed.size() == m.enc_rs.layers.size(), "encoder: composed context weights for %zu of %zu layers",
+            pa.composed.size(), m.enc_rs.layers.size());
+    const CtxGuard cgc{word, 1.0f, 0.0f, F16_SAFE, false};
+    const ComposedFront front{pa.composed.data(), C, pa.groups, R, pa.l1, m.enc_bias_max};
+    return resampler(m, L, m.enc_rs, A_a, (int64_t)C * R, Kpad_a, m.enc_q0.f(), m.W("encoder.atmos_latents"), B, s.Lp, s.Lp, R,
+                     s.Cl - 1, C, m.perceiver_heads, m.ln_eps, &cgc, false, 0, true, &front);
+  }
+  float* xa = (float*)m.arena.take((size_t)C * B * s.Lp * D * 4);
   // The patch embedding and the level aggregation's to_kv as one guarded chain: max |normalised input| is measured
   // once (a third of the bytes of the embeddings the resampler would otherwise scan), and if it is inside fp16's range
   // -- together with the bound it implies for the embeddings, |x| <= l1 * max|input| + max|bias| -- the embedding runs

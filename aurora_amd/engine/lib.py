@@ -1618,7 +1618,8 @@ _PS = ctypes.POINTER(ctypes.c_char_p)
 
 class HipTuning(ctypes.Structure):   # aurora_hip_config.tuning: 0 = the library's default
     _fields_ = [("fuse_ln", c_int32), ("band_split_attention", c_int32), ("qkv_planes", c_int32), ("split_k", c_int32),
-                ("perceiver_reassoc", c_int32), ("score_weights", c_int32), ("reserved", c_int32 * 2)]
+                ("perceiver_reassoc", c_int32), ("score_weights", c_int32), ("compose_front", c_int32),
+                ("reserved", c_int32 * 1)]
 
 
 def tuning_from_env() -> HipTuning:
@@ -1643,7 +1644,7 @@ def tuning_from_env() -> HipTuning:
         t.fuse_ln = v + 1            # 0 / 1 / 2 -> never / fill rule / always
     for field, var in (("band_split_attention", "AURORA_BAND_SPLIT_ATTENTION"), ("qkv_planes", "AURORA_QKV_PLANES"),
                        ("split_k", "AURORA_SPLIT_K"), ("perceiver_reassoc", "AURORA_PERCEIVER_REASSOC"),
-                       ("score_weights", "AURORA_SCORE_WEIGHTS")):
+                       ("score_weights", "AURORA_SCORE_WEIGHTS"), ("compose_front", "AURORA_COMPOSE_FRONT")):
         v = value(var, (0, 1))
         if v is not None:
             setattr(t, field, 2 if v else 1)
@@ -1732,6 +1733,11 @@ _SIGNATURES.update({
     "aurora_hip_guard_words": (c_int, [c_void_p, ctypes.POINTER(c_float), c_void_p]),
     "aurora_hip_abi_sizes": (c_int, [ctypes.POINTER(c_int32), c_int]),
     "aurora_hip_generation": (c_int64, [c_void_p]),
+    "aurora_hip_compose_weight": (c_int, [_PF, c_int, c_int, _PF, c_int, c_int, _PF]),
+    "aurora_hip_compose_bias": (c_int, [_PF, c_int, c_int, _PF, c_int, _PF]),
+    "aurora_hip_compose_front_rule": (c_int, [c_int, c_int, ctypes.POINTER(c_int32), c_int]),
+    "aurora_hip_composed_value_bound": (c_int, [c_float, c_float, c_float, c_float, c_float, _PF]),
+    "aurora_hip_front_composed": (c_int, [c_void_p]),
     "aurora_hip_output_vars": (c_int, [c_void_p, _PS, c_int]),
     "aurora_hip_set_time_ex": (c_int, [c_void_p, _PD, ctypes.POINTER(c_int32), c_int, c_void_p]),
     "aurora_hip_set_band": (c_int, [c_void_p, ctypes.POINTER(HipBand)]),

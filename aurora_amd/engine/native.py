@@ -369,6 +369,11 @@ class NativeModel:
         lib._check(lib.load().aurora_hip_guard_words(self._h, out, lib._stream()))
         return tuple(float(v) for v in out)
 
+    def front_composed(self) -> bool:
+        """Whether the last step ran its encoder front composed: the atmospheric patch embedding folded into the level
+        aggregation's context linears (include/aurora_hip.h: aurora_hip_front_composed)."""
+        return bool(lib.load().aurora_hip_front_composed(self._h))
+
     def generation(self) -> int:
         """Changes whenever the handle re-allocates device memory a captured hipGraph may point at."""
         return int(lib.load().aurora_hip_generation(self._h))

@@ -490,7 +490,10 @@ typedef struct aurora_hip_config {   /* Aurora.__init__ keywords, aurora/model/a
     int32_t perceiver_reassoc;     /* decoder de-aggregation re-associated (aurora_hip_perceiver_out; default on) */
     int32_t score_weights;         /* first Perceiver layers: to_kv's key half replaced by the Lq * heads rows W_k^T q_l (the queries
                                       are model constants), attention from those scores (default on; off: k | v, then q . k) */
-    int32_t reserved[2];
+    int32_t compose_front;         /* encoder front: the atmospheric patch embedding folded into the level aggregation's context
+                                      linears where that halves their work or better (aurora_hip_compose_front_rule; default on;
+                                      off: embedding, then to_kv -- the same map, other rounding points) */
+    int32_t reserved[1];
   } tuning;
 } aurora_hip_config;
 
@@ -565,6 +568,25 @@ int64_t aurora_hip_workspace_bytes(const aurora_hip_model* model);
  * DESIGN.md 3) means two fp16 terms, above it three bf16 terms -- same accuracy, different speed.  Synchronises `stream`. */
 #define AURORA_F16_SAFE_RANGE 16384.0f
 int aurora_hip_guard_words(const aurora_hip_model* model, float out[4], void* stream);
+/* ---- the encoder front composed: the atmospheric patch embedding is linear and read by the level aggregation's
+ * bias-free context linears alone, so kv = A (W_ctx W_e[c])^T + W_ctx (b_e + level_embed[c]) -- one GEMM of K = Kpad where
+ * one of K = Kpad and one of K = D ran.  The pieces, as pure host functions (HOST pointers, no device work), so that the
+ * composition, the rule and the guard limits can be checked without a device:
+ *   _compose_weight      out[g][n][k] = sum_d w_ctx[n][d] w_e[g][d][k] (w_ctx (N, D), w_e (groups, D, K)), summed in double, rounded once
+ *   _compose_bias        out[c][n]    = sum_d w_ctx[n][d] bias[c][d]   (bias (C, D)), likewise
+ *   _compose_front_rule  1 iff 2 sum_i Kpad N[i] <= Kpad D + sum_i D N[i]: the composed linears do at most half the multiply-adds
+ *                        of the stages they replace (patch size 4: 0.26, composed; patch size 10: 0.85, not)
+ *   _composed_value_bound  |v| <= a w + c for the attention's value rows, w = max |normalised input|: out[0..2] = a, c and the
+ *                        limit on w from the two stages (a = v_l1 embed_l1, c = v_l1 embed_bias_max), out[3..5] the same from the
+ *                        composed value rows' own L1 norm and bias maximum -- a and c never above the stages', so the limit on w
+ *                        never below
+ *   _front_composed      1 iff the handle's last step ran its encoder front composed */
+int aurora_hip_compose_weight(const float* w_ctx, int N, int D, const float* w_e, int K, int groups, float* out);
+int aurora_hip_compose_bias(const float* w_ctx, int N, int D, const float* bias, int C, float* out);
+int aurora_hip_compose_front_rule(int Kpad, int D, const int32_t* N, int n_layers);
+int aurora_hip_composed_value_bound(float v_l1, float embed_l1, float embed_bias_max, float composed_v_l1,
+                                    float composed_vb_max, float out[6]);
+int aurora_hip_front_composed(const aurora_hip_model* model);
 /* Counts the re-allocations of device memory that enqueued work points at: the workspace (it grows with the first step of
  * a larger batch / history / grid), the time buffers (a larger batch), the grid tables (aurora_hip_precompute).  A hipGraph
  * captured from aurora_hip_step is valid for as long as this number does not change. */
