@@ -249,6 +249,16 @@ struct aurora_hip_model {
 
   // per step
   aurora::DevBuf abs_enc, dyn_planes, ctx_max;
+  // what the last step compared the four words of ctx_max against (aurora_hip_guard_limits): per word the smallest limit of
+  // any launch, and how many launches carried it.  Host bookkeeping only: nothing a launch reads.
+  float guard_limit_min[4] = {INFINITY, INFINITY, INFINITY, INFINITY};
+  int guard_launches[4] = {0, 0, 0, 0};
+  void note_guard(const float* word, float limit) {
+    const ptrdiff_t i = word - ctx_max.f();
+    if (dry || word == nullptr || i < 0 || i >= 4) return;
+    guard_limit_min[i] = std::min(guard_limit_min[i], limit);
+    ++guard_launches[i];
+  }
   aurora::DevBuf tickets;   // split-K tickets of aurora_hip_linear_ws: SPLIT_TICKETS zeroed words, left zero by every launch
   // AURORA_SPLIT_K=0 at creation: no linear is ever split along K, so that a band's bf16 arithmetic is the un-sharded step's
   // bit for bit and does not depend on the device's CU count (split-K is chosen from the tile count against the CUs)
@@ -355,6 +365,7 @@ struct Launcher {
     void* ws = nullptr;
     int64_t ws_bytes = 0;
     const size_t mark = m.arena.top;
+    m.note_guard(o.guard, o.limit);
     if (m.split_k && o.dtype == AURORA_BF16 && o.batch == 1 && o.f32_gemm == -1 &&
         (ws_bytes = aurora_hip_linear_workspace(o.M, o.N, o.K, o.dtype)) > 0)
       ws = m.arena.take((size_t)ws_bytes);

@@ -396,6 +396,16 @@ extern "C" int aurora_hip_abi_sizes(int32_t* out, int capacity) {
   return n;
 }
 
+extern "C" int aurora_hip_guard_limits(const aurora_hip_model* m, float out[8]) {
+  GUARDED({
+    REQUIRE(m && out, "guard_limits: bad arguments");
+    for (int i = 0; i < 4; ++i) {
+      out[i] = m->guard_limit_min[i];
+      out[4 + i] = (float)m->guard_launches[i];
+    }
+  })
+}
+
 extern "C" int64_t aurora_hip_workspace_bytes(const aurora_hip_model* m) { return m ? (int64_t)m->arena.cap : 0; }
 
 extern "C" int aurora_hip_guard_words(const aurora_hip_model* m, float out[4], void* stream) {

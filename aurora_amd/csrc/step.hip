@@ -155,6 +155,7 @@ float* resampler(Model& m, Launcher& L, const Resampler& rs, const float* ctx, i
               "resampler: the softmax weights overlap k | v or to_out's result in the scratch region");
       float* P = (float*)(S + sp.p_off);
       void* Vp = y;
+      for (int k = 0; k < 3; ++k) m.note_guard(ctx_max, lim_out);   // probs, perceiver_out and the plain attention below
       timed(m, L.stream, K_PERCEIVER_ATTENTION, 0.0, [&] {
         if (scores)
           return aurora_hip_perceiver_probs_scores(kv, kv_ld, inner, P, Vp, B, cols, kv_bstride, kv_lstride, Lq, Lk, heads, ly.head_dim,
@@ -178,6 +179,7 @@ float* resampler(Model& m, Launcher& L, const Resampler& rs, const float* ctx, i
       });
       L.linear(LinearOp(att, inner, ly.to_out, inner, nullptr, o, Dd, n_rows, Dd, inner, AURORA_F32).f32_mode(1).guarded_by(ctx_max, lim_out));
     } else {
+      if (sp.att_pairs) m.note_guard(ctx_max, lim_out);
       timed(m, L.stream, K_PERCEIVER_ATTENTION, 0.0, [&] {
         if (scores)
           return aurora_hip_perceiver_attention_scores(kv, kv_ld, inner, att, B, cols, kv_bstride, kv_lstride, Lq, Lk, heads,
@@ -802,6 +804,8 @@ void run_step(Model& m, const StepIO& sio, void* stream) {
   // chain, 1: atmospheric / 2: surface patch-embedding inputs, 3: decoder context), cleared by ONE launch; their producers
   // fold the maxima in (patchify) or scan (absmax_fold)
   if (!m.dry) ok(aurora_hip_zero_words(m.ctx_max.f(), 4, stream));
+  if (!m.dry)   // (what aurora_hip_guard_limits reports: of this step alone)
+    for (int i = 0; i < 4; ++i) { m.guard_limit_min[i] = INFINITY; m.guard_launches[i] = 0; }
 
   // ================= encoder (encoder.py:198-366) =================
   float* xf = (float*)A.take((size_t)B * L0 * D * 4);                      // residual stream of stage 0 (fp32)

@@ -369,6 +369,13 @@ class NativeModel:
         lib._check(lib.load().aurora_hip_guard_words(self._h, out, lib._stream()))
         return tuple(float(v) for v in out)
 
+    def guard_limits(self) -> tuple[tuple[float, float, float, float], tuple[int, int, int, int]]:
+        """What the last step compared its range words against (include/aurora_hip.h: aurora_hip_guard_limits): per word
+        the smallest limit of any guarded launch (inf if none), and the number of launches that carried the word."""
+        out = (ctypes.c_float * 8)()
+        lib._check(lib.load().aurora_hip_guard_limits(self._h, out))
+        return tuple(float(v) for v in out[:4]), tuple(int(v) for v in out[4:])
+
     def front_composed(self) -> bool:
         """Whether the last step ran its encoder front composed: the atmospheric patch embedding folded into the level
         aggregation's context linears (include/aurora_hip.h: aurora_hip_front_composed)."""

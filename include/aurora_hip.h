@@ -568,6 +568,12 @@ int64_t aurora_hip_workspace_bytes(const aurora_hip_model* model);
  * DESIGN.md 3) means two fp16 terms, above it three bf16 terms -- same accuracy, different speed.  Synchronises `stream`. */
 #define AURORA_F16_SAFE_RANGE 16384.0f
 int aurora_hip_guard_words(const aurora_hip_model* model, float out[4], void* stream);
+/* What were those words compared against?  Every guarded launch of a step runs its two-term form iff word < limit, with a
+ * limit the handle derives from its weights (L1 row norms and bias maxima of the linears between the measured quantity and the
+ * launch's activation operand).  Of the handle's last step: out[i], i = 0..3, the SMALLEST limit any launch compared word i
+ * against (+inf if none did), out[4 + i] the number of launches that carried word i (a guarded pair counts twice).  word i <
+ * out[i] <=> every guarded launch on word i took two fp16 terms.  Host bookkeeping: no device work, no synchronisation. */
+int aurora_hip_guard_limits(const aurora_hip_model* model, float out[8]);
 /* ---- the encoder front composed: the atmospheric patch embedding is linear and read by the level aggregation's
  * bias-free context linears alone, so kv = A (W_ctx W_e[c])^T + W_ctx (b_e + level_embed[c]) -- one GEMM of K = Kpad where
  * one of K = Kpad and one of K = D ran.  The pieces, as pure host functions (HOST pointers, no device work), so that the

@@ -99,6 +99,7 @@ def test_constants_and_new_argument_contracts_match_the_header(built):
     assert L.aurora_hip_linear_ws(16, 8192, 16, 8192, None, 16, 2048, None, 0, None, 0, 2160, 2048, 8192, shim.BF16, 0,
                                   8, 1 << 26, 16, 4096, 0, None) == -1 and b"workspace" in err()
     assert L.aurora_hip_zero_words(None, 4, None) == -1 and L.aurora_hip_zero_words(16, 65, None) == -1
+    assert L.aurora_hip_guard_limits(None, (ctypes.c_float * 8)()) == -1 and b"guard_limits" in err()
     # the dispatch query: kernel ids as the header numbers them; with an explicit CU count it is host arithmetic, runs the
     # launch path's own argument check (the same refusals) and tells the store path from the alignment it is given
     import torch
