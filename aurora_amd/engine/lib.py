@@ -11,13 +11,15 @@ from __future__ import annotations
 import ctypes
 import os
 import threading
-from collections import OrderedDict, namedtuple
+from collections import namedtuple
 from ctypes import c_float, c_int, c_int32, c_int64, c_void_p
 from pathlib import Path
 from typing import Optional
 
 import numpy as np
 import torch
+
+from aurora_amd.engine.tables import DeviceTables, _upload
 
 F32, BF16, F64 = 0, 1, 2
 ACT_NONE, ACT_GELU, ACT_SILU = 0, 1, 2
@@ -172,8 +174,6 @@ _SIGNATURES = {
     "aurora_hip_object_separations": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p,
                                               c_void_p, c_void_p]),
 }
-
-EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -821,22 +821,25 @@ def conservative_regrid(src: list[torch.Tensor], out: torch.Tensor, tables, min_
     assert len(addresses) == n, f"conservative_regrid: the sources hold {len(addresses)} planes, out {n}"
     if n == 0:
         return
-    with torch.cuda.device(dev):
-        planes = _plane_table("conservative_regrid", tuple(addresses), dev)
-        step = 4 * n_rows * n_cols
-        dst = torch.arange(out.data_ptr(), out.data_ptr() + n * step, step, dtype=torch.int64, device=dev)
-        moved = float(n) * (n_lat * n_lon * src[0].element_size() + step)
-        with _Timed("conservative_regrid", moved):
-            _check(load().aurora_hip_conservative_regrid(_ptr(planes), F64 if dt == torch.float64 else F32, _ptr(dst), n, n_lat,
-                                                         n_lon, n_rows, n_cols, _ptr(row_first), _ptr(row_count), _ptr(row_w),
-                                                         _ptr(row_m), _ptr(col_first), _ptr(col_count), _ptr(col_w), _ptr(col_m),
-                                                         float(min_valid), _stream()))
+    planes = _planes("conservative_regrid", [], dev)
+    planes.add("source", addresses)
+    at = planes.upload()
+    step = 4 * n_rows * n_cols
+    dst = torch.arange(out.data_ptr(), out.data_ptr() + n * step, step, dtype=torch.int64, device=dev)
+    moved = float(n) * (n_lat * n_lon * src[0].element_size() + step)
+    _launch(dev, "conservative_regrid", moved, "aurora_hip_conservative_regrid", at["source"],
+            F64 if dt == torch.float64 else F32, _ptr(dst), n, n_lat, n_lon, n_rows, n_cols, _ptr(row_first), _ptr(row_count),
+            _ptr(row_w), _ptr(row_m), _ptr(col_first), _ptr(col_count), _ptr(col_w), _ptr(col_m), float(min_valid))
 
 
-# ---- verification sums (aurora_hip_scores) ----------------------------------------------------------------
-_PLANE_TABLES_MAX = 256
-_plane_tables: "OrderedDict[tuple, list]" = OrderedDict()   # plane addresses -> [device table, used in a captured graph]
-_plane_tables_lock = threading.Lock()
+# ---- what the verification wrappers below share: the planes of a call, the operand checks, the launch ----------------------
+def _upload_current(a: np.ndarray, device: torch.device) -> torch.Tensor:
+    with torch.cuda.device(device):   # (a table is uploaded, as a kernel is launched, with its device current)
+        return _upload(a, device)
+
+
+_plane_tables = DeviceTables(256, _upload_current)   # plane addresses -> the plane-pointer arrays of a call
+_twiddles = DeviceTables(64, _upload_current)        # n_lon -> the table of `spectra_twiddle`
 
 
 def _plane_addresses(fn: str, fields: list[torch.Tensor], n_lat: int, n_lon: int, what: str) -> list[int]:
@@ -853,50 +856,103 @@ def _plane_addresses(fn: str, fields: list[torch.Tensor], n_lat: int, n_lon: int
     return out
 
 
-def _cached_table(tables: OrderedDict, limit: int, key: tuple, make, device: torch.device, on_capture: str) -> torch.Tensor:
-    """Device copy of a small host table, kept in `tables` under `key` (a roll-out asks for the same one again and again, and a
-    captured graph must find its table alive and unchanged at every replay).  A miss uploads `make()` from pinned memory without
-    synchronising; during stream capture a miss is an error, and a table a graph uses is never evicted; the others leave least
-    recently used first once more than `limit` are kept."""
-    capturing = torch.cuda.is_current_stream_capturing()
-    with _plane_tables_lock:
-        hit = tables.get(key)
-        if hit is not None:
-            tables.move_to_end(key)
-            hit[1] = hit[1] or capturing
-            return hit[0]
-    if capturing:
-        raise RuntimeError(on_capture)
-    table = make().pin_memory().to(device, non_blocking=True)
-    with _plane_tables_lock:
-        tables[key] = [table, False]
-        for old in [k for k, v in tables.items() if not v[1]][: max(0, len(tables) - limit)]:
-            del tables[old]
-    return table
+class _Planes:
+    """The plane-pointer arrays of one call, list after list in ONE device table, which is cached by the addresses (a roll-out
+    passes the same tensors again and again, and a captured graph must find its table alive and unchanged at every replay):
+    `n`, the planes of each checked list, and from `upload` the device address of the array of every list by its label --
+    None for a list that was given as None."""
+
+    def __init__(self, fn: str, dev: torch.device):
+        self.fn, self.dev, self.n = fn, dev, 0
+        self.addresses: list[int] = []
+        self._offset: dict = {}   # label -> bytes from the start of the table, or None
+
+    def add(self, what: str, addresses: Optional[list[int]]) -> None:
+        """One more list, as ready addresses (0: the kernel gets NULL for that plane) or None.  The ONE place where the position
+        of a list in the table is worked out: after the lists before it, eight bytes an address."""
+        self._offset[what] = None if addresses is None else 8 * len(self.addresses)
+        self.addresses += addresses or []
+
+    def upload(self) -> dict:
+        """{label: device address of that list's array, or None}; the table stays alive as long as this object."""
+        self._table = _plane_tables.get((tuple(self.addresses),), self.dev, lambda: np.asarray(self.addresses, np.int64),
+                                        f"{self.fn}: call once on these tensors before capturing a graph (the plane-pointer table "
+                                        "is uploaded on the first call, which a captured graph cannot replay)")
+        first = self._table.data_ptr()
+        return {what: None if offset is None else first + offset for what, offset in self._offset.items()}
 
 
-def _plane_table(fn: str, addresses: tuple, device: torch.device) -> torch.Tensor:
-    """Device copy of the plane-pointer arrays of a call, cached by the addresses."""
-    return _cached_table(_plane_tables, _PLANE_TABLES_MAX, (device.index, addresses),
-                         lambda: torch.tensor(addresses, dtype=torch.int64), device,
-                         f"{fn}: call once on these tensors before capturing a graph (the plane-pointer table "
-                         "is uploaded on the first call, which a captured graph cannot replay)")
+def _planes(fn: str, lists, dev: torch.device, anchor: str = "", n_lat: int = 0, n_lon: int = 0, like: int = 0) -> _Planes:
+    """The `_Planes` of the labelled lists [(what, fields or None)] of a call, after what every plane binding checks of the lists
+    that are given: the same length, every field on `dev` (the device of the argument `anchor`) and shaped like its counterpart
+    in the given list `like`, every plane as `_plane_addresses` wants it.  A caller with lists of another kind `add`s them."""
+    given = [fs for _, fs in lists if fs is not None]
+    if given:
+        first = given[like]
+        assert all(len(fs) == len(first) for fs in given), f"{fn}: the lists differ in length"
+        for fs in given:
+            for v, p in zip(fs, first):
+                assert v.device == dev, f"{fn}: every tensor must be on the device of {anchor}"
+                assert v.shape == p.shape, f"{fn}: shapes differ ({tuple(v.shape)} against {tuple(p.shape)})"
+    planes = _Planes(fn, dev)
+    for what, fs in lists:
+        planes.add(what, None if fs is None else _plane_addresses(fn, fs, n_lat, n_lon, what))
+    if given:
+        planes.n = len(planes.addresses) // len(given)
+    return planes
 
 
-def _plane_lists(fn: str, lists, dev: torch.device, anchor: str, n_lat: int, n_lon: int, like: int = 0) -> tuple[int, list[int]]:
-    """What every plane binding checks of its labelled lists [(what, fields)] -- the same length, every field on `dev` (the
-    device of the argument `anchor`) and shaped like its counterpart in list `like` -- and the plane addresses of list 0, 1, ...
-    one after the other: (planes per list, addresses)."""
-    first = lists[like][1]
-    assert all(len(fs) == len(first) for _, fs in lists), f"{fn}: the lists differ in length"
-    for _, fs in lists:
-        for v, p in zip(fs, first):
-            assert v.device == dev, f"{fn}: every tensor must be on the device of {anchor}"
-            assert v.shape == p.shape, f"{fn}: shapes differ ({tuple(v.shape)} against {tuple(p.shape)})"
-    addresses = [a for what, fs in lists for a in _plane_addresses(fn, fs, n_lat, n_lon, what)]
-    return len(addresses) // len(lists), addresses
+def _operand(fn: str, name: str, t: torch.Tensor, dtype: torch.dtype, kind: str, *, dev: Optional[torch.device] = None,
+             anchor: str = "", dim: Optional[int] = None, shape: Optional[tuple] = None) -> None:
+    """`t` is a contiguous `dtype` tensor with `dim` dimensions or of `shape`, on `dev` (the device of the argument `anchor`) or,
+    without one, on any device.  `kind` is what the message calls such a tensor."""
+    assert (t.is_cuda if dev is None else t.device == dev) and t.dtype == dtype and t.is_contiguous() and \
+        (dim is None or t.dim() == dim) and (shape is None or tuple(t.shape) == tuple(shape)), \
+        f"{fn}: {name} must be a contiguous {kind} on the device" + (f" of {anchor}" if anchor else "")
 
 
+def _label_maps(fn: str, name: str, labels: torch.Tensor) -> tuple:
+    """`labels` is a stack of label maps on the device: (its device, (n_lat, n_lon), the leading shape)."""
+    assert labels.is_cuda and labels.dtype == torch.int32 and labels.dim() >= 2 and labels.is_contiguous(), \
+        f"{fn}: {name} must be a contiguous (..., n_lat, n_lon) int32 tensor on the device"
+    return labels.device, labels.shape[-2:], tuple(labels.shape[:-2])
+
+
+_TENSOR = "{what} must be a contiguous {dtype} tensor of shape {shape} on the device of {anchor}"
+
+
+def _like(fn: str, what: str, t: torch.Tensor, shape, dtype: torch.dtype, dev: torch.device, anchor: str, text: str = _TENSOR) -> None:
+    """`t` is a contiguous `dtype` tensor of `shape` on `dev`, the device of the argument `anchor`."""
+    assert t.device == dev and t.dtype == dtype and tuple(t.shape) == tuple(shape) and t.is_contiguous(), \
+        f"{fn}: " + text.format(what=what, dtype=dtype, shape=tuple(shape), anchor=anchor)
+
+
+def _outputs(fn: str, out, specs, dev: torch.device, anchor: str, text: str = _TENSOR) -> tuple:
+    """The outputs of a call, `specs` = ((shape, dtype, name), ...): new tensors, or the caller's `out` after `_like`."""
+    if out is None:
+        return tuple(torch.empty(shape, dtype=dtype, device=dev) for shape, dtype, _ in specs)
+    for t, (shape, dtype, what) in zip(out, specs):
+        _like(fn, what, t, shape, dtype, dev, anchor, text)
+    return out
+
+
+def _workspace(fn: str, workspace: Optional[torch.Tensor], dev: torch.device, anchor: str, query, *sizes) -> torch.Tensor:
+    """A new workspace of `query(*sizes)` bytes, or the caller's after a check of what the library cannot check."""
+    if workspace is None:
+        return torch.empty(query(*sizes), dtype=torch.uint8, device=dev)
+    assert workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous(), \
+        f"{fn}: the workspace must be a contiguous uint8 tensor on the device of {anchor}"
+    return workspace
+
+
+def _launch(dev: torch.device, name: str, work: float, entry: str, *args) -> None:
+    """`entry(*args, the current stream of dev)` with `dev` current, timed as `name` when profiling is on."""
+    with torch.cuda.device(dev):
+        with _Timed(name, work):
+            _check(getattr(load(), entry)(*args, _stream()))
+
+
+# ---- verification sums (aurora_hip_scores) ----------------------------------------------------------------
 def scores_workspace_bytes(n_planes: int, n_lat: int, n_lon: int) -> int:
     return int(load().aurora_hip_scores_workspace_bytes(n_planes, n_lat, n_lon))
 
@@ -910,22 +966,18 @@ def scores_sums(pred: list[torch.Tensor], truth: list[torch.Tensor], clim: Optio
     pred / truth / clim: lists of fp32 (..., n_lat, n_lon) tensors on one device with row-major contiguous planes (any
     leading strides, any 4-byte plane alignment), the same leading shapes in each list; row_w: (n_lat,) fp64 on that
     device.  Nothing of plane size is allocated and the host does not wait for the device."""
-    assert row_w.is_cuda and row_w.dtype == torch.float64 and row_w.dim() == 1 and row_w.is_contiguous(), \
-        "scores_sums: row_w must be a contiguous fp64 vector on the device"
+    _operand("scores_sums", "row_w", row_w, torch.float64, "fp64 vector", dim=1)
     dev, n_lat = row_w.device, row_w.shape[0]
-    lists = [("prediction", pred), ("truth", truth)] + ([("climatology", clim)] if clim is not None else [])
     n_lon = pred[0].shape[-1] if pred else 1
-    n, addresses = _plane_lists("scores_sums", lists, dev, "row_w", n_lat, n_lon)
+    planes = _planes("scores_sums", [("prediction", pred), ("truth", truth), ("climatology", clim)], dev, "row_w", n_lat, n_lon)
+    n = planes.n
     sums = torch.empty(n, 8, dtype=torch.float64, device=dev)
     if n == 0:
         return sums
-    with torch.cuda.device(dev):
-        table = _plane_table("scores_sums", tuple(addresses), dev)
-        workspace = torch.empty(scores_workspace_bytes(n, n_lat, n_lon), dtype=torch.uint8, device=dev)
-        base = table.data_ptr()
-        with _Timed("scores", 0.0):
-            _check(load().aurora_hip_scores(base, base + 8 * n, base + 16 * n if clim is not None else None, n, n_lat, n_lon,
-                                            _ptr(row_w), _ptr(sums), _ptr(workspace), _stream()))
+    at = planes.upload()
+    workspace = torch.empty(scores_workspace_bytes(n, n_lat, n_lon), dtype=torch.uint8, device=dev)
+    _launch(dev, "scores", 0.0, "aurora_hip_scores", at["prediction"], at["truth"], at["climatology"], n, n_lat, n_lon,
+            _ptr(row_w), _ptr(sums), _ptr(workspace))
     return sums
 
 
@@ -947,25 +999,22 @@ def ensemble_scores_sums(members: list[list[torch.Tensor]], truth: list[torch.Te
     contiguous planes (any leading strides, any 4-byte plane alignment) and the leading shapes of `truth`; row_w: (n_lat,)
     fp64 on that device.  The plane-pointer table is cached by address as in `scores_sums`.  Nothing of plane size is
     allocated and the host does not wait for the device."""
-    assert row_w.is_cuda and row_w.dtype == torch.float64 and row_w.dim() == 1 and row_w.is_contiguous(), \
-        "ensemble_scores_sums: row_w must be a contiguous fp64 vector on the device"
+    _operand("ensemble_scores_sums", "row_w", row_w, torch.float64, "fp64 vector", dim=1)
     M = len(members)
     assert 2 <= M <= ENSEMBLE_MAX_MEMBERS, f"ensemble_scores_sums: members must hold 2..{ENSEMBLE_MAX_MEMBERS} lists, got {M}"
     dev, n_lat = row_w.device, row_w.shape[0]
     n_lon = truth[0].shape[-1] if truth else 1
     lists = [(f"member {m}", fs) for m, fs in enumerate(members)] + [("truth", truth)]
-    n, addresses = _plane_lists("ensemble_scores_sums", lists, dev, "row_w", n_lat, n_lon, like=-1)
+    planes = _planes("ensemble_scores_sums", lists, dev, "row_w", n_lat, n_lon, like=-1)
+    n = planes.n
     sums = torch.empty(n, 8, dtype=torch.float64, device=dev)
     hist = torch.empty(n, M + 2, dtype=torch.int64, device=dev)
     if n == 0:
         return sums, hist
-    with torch.cuda.device(dev):
-        table = _plane_table("ensemble_scores_sums", tuple(addresses), dev)
-        workspace = torch.empty(ensemble_scores_workspace_bytes(M, n, n_lat, n_lon), dtype=torch.uint8, device=dev)
-        base = table.data_ptr()
-        with _Timed("ensemble_scores", 0.0):
-            _check(load().aurora_hip_ensemble_scores(base, base + 8 * M * n, M, n, n_lat, n_lon, _ptr(row_w), _ptr(sums),
-                                                     _ptr(hist), _ptr(workspace), _stream()))
+    at = planes.upload()
+    workspace = torch.empty(ensemble_scores_workspace_bytes(M, n, n_lat, n_lon), dtype=torch.uint8, device=dev)
+    _launch(dev, "ensemble_scores", 0.0, "aurora_hip_ensemble_scores", at["member 0"], at["truth"], M, n, n_lat, n_lon,
+            _ptr(row_w), _ptr(sums), _ptr(hist), _ptr(workspace))
     return sums, hist
 
 
@@ -994,28 +1043,55 @@ def ensemble_quantiles(members: list[list[torch.Tensor]], truth: Optional[list[t
     assert 1 <= Q <= QUANTILES_MAX, f"ensemble_quantiles: 1..{QUANTILES_MAX} values of q, got {Q}"
     assert rank_out is None or truth is not None, "ensemble_quantiles: rank_out without a truth"
     dev, (n_lat, n_lon) = members[0][0].device, members[0][0].shape[-2:]
-    lists = [(f"member {m}", fs) for m, fs in enumerate(members)] + ([("truth", truth)] if truth is not None else [])
-    n, addresses = _plane_lists("ensemble_quantiles", lists, dev, "the first member", n_lat, n_lon)
-    for what, t, shape, dt in (("out", out, (n, Q, n_lat, n_lon), torch.float32), ("rank_out", rank_out, (n, n_lat, n_lon), torch.int8)):
-        assert t is None or (t.device == dev and t.dtype == dt and tuple(t.shape) == shape and t.is_contiguous()), \
-            f"ensemble_quantiles: {what} must be a contiguous {dt} tensor of {shape} on the device of the members"
-    if out is None:
-        out = torch.empty(n, Q, n_lat, n_lon, dtype=torch.float32, device=dev)
-    if truth is not None and rank_out is None:
-        rank_out = torch.empty(n, n_lat, n_lon, dtype=torch.int8, device=dev)
-    with torch.cuda.device(dev):
-        table = _plane_table("ensemble_quantiles", tuple(addresses), dev)
-        base = table.data_ptr()
-        moved = float(n * n_lat * n_lon * (4 * M + 4 * Q + (5 if truth is not None else 0)))
-        with _Timed("ensemble_quantiles", moved):
-            _check(load().aurora_hip_ensemble_quantiles(base, base + 8 * M * n if truth is not None else None, M, n, n_lat, n_lon,
-                                                        qs.ctypes.data, Q, _ptr(out), _ptr(rank_out), _stream()))
+    lists = [(f"member {m}", fs) for m, fs in enumerate(members)] + [("truth", truth)]
+    planes = _planes("ensemble_quantiles", lists, dev, "the first member", n_lat, n_lon)
+    n = planes.n
+    text = "{what} must be a contiguous {dtype} tensor of {shape} on the device of {anchor}"
+    out, = _outputs("ensemble_quantiles", None if out is None else (out,), [((n, Q, n_lat, n_lon), torch.float32, "out")], dev,
+                    "the members", text)
+    if truth is not None:
+        rank_out, = _outputs("ensemble_quantiles", None if rank_out is None else (rank_out,),
+                             [((n, n_lat, n_lon), torch.int8, "rank_out")], dev, "the members", text)
+    at = planes.upload()
+    moved = float(n * n_lat * n_lon * (4 * M + 4 * Q + (5 if truth is not None else 0)))
+    _launch(dev, "ensemble_quantiles", moved, "aurora_hip_ensemble_quantiles", at["member 0"], at["truth"], M, n, n_lat, n_lon,
+            qs.ctypes.data, Q, _ptr(out), _ptr(rank_out))
     return out, rank_out
+
+
+# ---- event probabilities of an ensemble (aurora_hip_probability_scores) -----------------------------------------------
+def probability_rows(members: list[list[torch.Tensor]], truth: list[torch.Tensor], thresholds: torch.Tensor,
+                     below: bool = False) -> torch.Tensor:
+    """The integer table of include/aurora_hip.h -- per row of every plane, threshold and (event observed o, k of M members
+    forecasting it) the number of valid points -- in ONE aurora_hip_probability_scores call: an (n_planes, n_lat, T, 2, M + 1)
+    int32 tensor on the device.
+
+    members: M lists (2 <= M <= 64), each like `truth`: fp32 (..., n_lat, n_lon) tensors on one device with row-major
+    contiguous planes (any leading strides, any 4-byte plane alignment) and the leading shapes of `truth`; thresholds:
+    contiguous (n_planes, T) fp32 on that device (NaN: no event).  The plane-pointer table is cached by address as in
+    `scores_sums`.  Nothing but the result is allocated and the host does not wait for the device."""
+    _operand("probability_rows", "thresholds", thresholds, torch.float32, "(n_planes, T) fp32 matrix", dim=2)
+    dev, (n_thr_planes, T) = thresholds.device, thresholds.shape
+    M = len(members)
+    assert 2 <= M <= ENSEMBLE_MAX_MEMBERS, f"probability_rows: members must hold 2..{ENSEMBLE_MAX_MEMBERS} lists, got {M}"
+    assert 1 <= T <= EVENT_MAX_THRESHOLDS, f"probability_rows: 1..{EVENT_MAX_THRESHOLDS} thresholds, got {T}"
+    assert truth and all(len(fs) == len(truth) for fs in members), "probability_rows: the lists differ in length or are empty"
+    n_lat, n_lon = truth[0].shape[-2:]
+    lists = [(f"member {m}", fs) for m, fs in enumerate(members)] + [("truth", truth)]
+    planes = _planes("probability_rows", lists, dev, "thresholds", n_lat, n_lon, like=-1)
+    n = planes.n
+    assert n == n_thr_planes, f"probability_rows: {n} planes but thresholds for {n_thr_planes}"
+    rows = torch.empty(n, n_lat, T, 2, M + 1, dtype=torch.int32, device=dev)
+    if n == 0:
+        return rows
+    at = planes.upload()
+    _launch(dev, "probability_scores", 0.0, "aurora_hip_probability_scores", at["member 0"], at["truth"], M, n, n_lat, n_lon,
+            _ptr(thresholds), T, 1 if below else 0, _ptr(rows))
+    return rows
 
 
 # ---- zonal power spectra (aurora_hip_spectra) -------------------------------------------------------------------------
 SPECTRA_MAX_BANDS, SPECTRA_MAX_LON = 8, 4096
-_twiddles: "OrderedDict[tuple, list]" = OrderedDict()   # (n_lon, device) -> [(n_lon, 2) fp64 device table, used in a captured graph]
 
 
 def spectra_twiddle(n_lon: int, device: torch.device) -> torch.Tensor:
@@ -1023,9 +1099,9 @@ def spectra_twiddle(n_lon: int, device: torch.device) -> torch.Tensor:
     (n_lon, device)."""
     def make():
         a = 2.0 * np.pi * np.arange(n_lon, dtype=np.float64) / n_lon
-        return torch.from_numpy(np.stack([np.cos(a), np.sin(a)], axis=1))
+        return np.stack([np.cos(a), np.sin(a)], axis=1)
 
-    return _cached_table(_twiddles, 64, (int(n_lon), str(device)), make, device,
+    return _twiddles.get((int(n_lon),), device, make,
                          "spectra_power: call once for this n_lon before capturing a graph (the twiddle table is "
                          "uploaded on the first call, which a captured graph cannot replay)")
 
@@ -1044,29 +1120,25 @@ def spectra_power(pred: list[torch.Tensor], truth: Optional[list[torch.Tensor]],
     strides, any 4-byte plane alignment), the same leading shapes in each list; band_w: (n_bands, n_lat) fp64 on that
     device, the row weight inside the band and 0 outside.  The plane-pointer table is cached by address as in `scores_sums`,
     the twiddle table per n_lon; the only temporary is the workspace of partials.  The host does not wait for the device."""
-    assert band_w.is_cuda and band_w.dtype == torch.float64 and band_w.dim() == 2 and band_w.is_contiguous(), \
-        "spectra_power: band_w must be a contiguous (n_bands, n_lat) fp64 matrix on the device"
+    _operand("spectra_power", "band_w", band_w, torch.float64, "(n_bands, n_lat) fp64 matrix", dim=2)
     dev, (n_bands, n_lat) = band_w.device, band_w.shape
     assert 1 <= n_bands <= SPECTRA_MAX_BANDS, f"spectra_power: 1..{SPECTRA_MAX_BANDS} bands, got {n_bands}"
-    lists = [("prediction", pred)] + ([("truth", truth)] if truth is not None else [])
     n_lon = pred[0].shape[-1] if pred else 2
     assert 2 <= n_lon <= SPECTRA_MAX_LON, f"spectra_power: n_lon must be in 2..{SPECTRA_MAX_LON}, got {n_lon}"
-    n, addresses = _plane_lists("spectra_power", lists, dev, "band_w", n_lat, n_lon)
-    F, K = len(lists) * 2 - 1, n_lon // 2 + 1
+    planes = _planes("spectra_power", [("prediction", pred), ("truth", truth)], dev, "band_w", n_lat, n_lon)
+    n, n_lists = planes.n, 1 if truth is None else 2
+    F, K = n_lists * 2 - 1, n_lon // 2 + 1
     power = torch.empty(n, F, n_bands, K, dtype=torch.float64, device=dev)
     rows = torch.empty(n, n_bands, dtype=torch.int64, device=dev)
     if n == 0:
         return power, rows
-    with torch.cuda.device(dev):
-        table = _plane_table("spectra_power", tuple(addresses), dev)
-        twiddle = spectra_twiddle(n_lon, dev)
-        nbytes = spectra_workspace_bytes(n, n_lat, n_lon, n_bands, truth is not None)
-        workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)   # (from torch's caching allocator: no hipMalloc warm)
-        base = table.data_ptr()
-        with _Timed("spectra", 2.0 * (len(lists) * n * n_lat) * K * (2 * K)):   # folded transform: K products per output
-            _check(load().aurora_hip_spectra(base, base + 8 * n if truth is not None else None, n, n_lat, n_lon, n_bands,
-                                             _ptr(band_w), _ptr(twiddle), _ptr(power), _ptr(rows), _ptr(workspace), nbytes,
-                                             _stream()))
+    at = planes.upload()
+    twiddle = spectra_twiddle(n_lon, dev)
+    nbytes = spectra_workspace_bytes(n, n_lat, n_lon, n_bands, truth is not None)
+    workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)   # (from torch's caching allocator: no hipMalloc warm)
+    _launch(dev, "spectra", 2.0 * (n_lists * n * n_lat) * K * (2 * K),   # folded transform: K products per output
+            "aurora_hip_spectra", at["prediction"], at["truth"], n, n_lat, n_lon, n_bands, _ptr(band_w), _ptr(twiddle),
+            _ptr(power), _ptr(rows), _ptr(workspace), nbytes)
     return power, rows
 
 
@@ -1090,8 +1162,7 @@ def event_rowsums(pred: list[torch.Tensor], truth: list[torch.Tensor], threshold
     that device (NaN: no event); scales: odd, ascending, distinct window sizes starting with 1, each <= 63 and <= n_lon.
     The plane-pointer table is cached by address as in `scores_sums`.  Nothing of plane size is allocated and the host does
     not wait for the device."""
-    assert thresholds.is_cuda and thresholds.dtype == torch.float32 and thresholds.dim() == 2 and thresholds.is_contiguous(), \
-        "event_rowsums: thresholds must be a contiguous (n_planes, T) fp32 matrix on the device"
+    _operand("event_rowsums", "thresholds", thresholds, torch.float32, "(n_planes, T) fp32 matrix", dim=2)
     dev, (n_thr_planes, T) = thresholds.device, thresholds.shape
     scales = [int(n) for n in scales]
     S = len(scales)
@@ -1099,19 +1170,16 @@ def event_rowsums(pred: list[torch.Tensor], truth: list[torch.Tensor], threshold
     assert 1 <= S <= EVENT_MAX_SCALES, f"event_rowsums: 1..{EVENT_MAX_SCALES} scales, got {S}"
     assert len(truth) == len(pred) and pred, "event_rowsums: the lists differ in length or are empty"
     n_lat, n_lon = pred[0].shape[-2:]
-    n, addresses = _plane_lists("event_rowsums", [("prediction", pred), ("truth", truth)], dev, "thresholds", n_lat, n_lon)
+    planes = _planes("event_rowsums", [("prediction", pred), ("truth", truth)], dev, "thresholds", n_lat, n_lon)
+    n = planes.n
     assert n == n_thr_planes, f"event_rowsums: {n} planes but thresholds for {n_thr_planes}"
     rowsums = torch.empty(n, T, S, n_lat, 3, dtype=torch.int64, device=dev)
     valid = torch.empty(n, n_lat, dtype=torch.int64, device=dev)
     if n == 0:
         return rowsums, valid
-    host_scales = (c_int32 * S)(*scales)
-    with torch.cuda.device(dev):
-        table = _plane_table("event_rowsums", tuple(addresses), dev)
-        base = table.data_ptr()
-        with _Timed("event_scores", 0.0):
-            _check(load().aurora_hip_event_scores(base, base + 8 * n, n, n_lat, n_lon, _ptr(thresholds), T, host_scales, S,
-                                                  1 if below else 0, _ptr(rowsums), _ptr(valid), None, 0, _stream()))
+    at = planes.upload()
+    _launch(dev, "event_scores", 0.0, "aurora_hip_event_scores", at["prediction"], at["truth"], n, n_lat, n_lon,
+            _ptr(thresholds), T, (c_int32 * S)(*scales), S, 1 if below else 0, _ptr(rowsums), _ptr(valid), None, 0)
     return rowsums, valid
 
 
@@ -1131,31 +1199,25 @@ def conditional_sums(pred: list[torch.Tensor], truth: list[torch.Tensor], centre
     alignment), the same leading shapes in each list; edges: contiguous (n_planes, E) fp32 on that device, 1 <= E <= 8 (NaN:
     no edge); row_w: (n_lat,) fp64 on that device.  The plane-pointer table is cached by address as in `scores_sums`.
     Nothing of plane size is allocated and the host does not wait for the device."""
-    assert row_w.is_cuda and row_w.dtype == torch.float64 and row_w.dim() == 1 and row_w.is_contiguous(), \
-        "conditional_sums: row_w must be a contiguous fp64 vector on the device"
-    assert edges.is_cuda and edges.dtype == torch.float32 and edges.dim() == 2 and edges.is_contiguous(), \
-        "conditional_sums: edges must be a contiguous (n_planes, E) fp32 matrix on the device"
+    _operand("conditional_sums", "row_w", row_w, torch.float64, "fp64 vector", dim=1)
+    _operand("conditional_sums", "edges", edges, torch.float32, "(n_planes, E) fp32 matrix", dim=2)
     dev, n_lat, (n_edge_planes, E) = row_w.device, row_w.shape[0], edges.shape
     assert edges.device == dev, "conditional_sums: every tensor must be on the device of row_w"
     assert 1 <= E <= EVENT_MAX_THRESHOLDS, f"conditional_sums: 1..{EVENT_MAX_THRESHOLDS} edges, got {E}"
-    lists = [("prediction", pred), ("truth", truth)] + [(what, fs) for what, fs in (("centre", centre), ("scale", scale))
-                                                        if fs is not None]
+    lists = [("prediction", pred), ("truth", truth), ("centre", centre), ("scale", scale)]
     n_lon = pred[0].shape[-1] if pred else 1
-    n, addresses = _plane_lists("conditional_sums", lists, dev, "row_w", n_lat, n_lon)
+    planes = _planes("conditional_sums", lists, dev, "row_w", n_lat, n_lon)
+    n = planes.n
     assert n == n_edge_planes, f"conditional_sums: {n} planes but edges for {n_edge_planes}"
     sums = torch.empty(n, E + 1, 5, dtype=torch.float64, device=dev)
     if n == 0:
         return sums
-    with torch.cuda.device(dev):
-        table = _plane_table("conditional_sums", tuple(addresses), dev)
-        workspace = torch.empty(conditional_scores_workspace_bytes(n, n_lat, n_lon, E), dtype=torch.uint8, device=dev)
-        base = table.data_ptr()
-        centre_at = base + 16 * n if centre is not None else None
-        scale_at = base + 8 * n * (len(lists) - 1) if scale is not None else None
-        with _Timed("conditional_scores", float(n * n_lat * n_lon * 4 * len(lists))):   # bytes read
-            _check(load().aurora_hip_conditional_scores(base, base + 8 * n, centre_at, scale_at, n, n_lat, n_lon, _ptr(edges), E,
-                                                        1 if by_pred else 0, _ptr(row_w), _ptr(sums), _ptr(workspace),
-                                                        _stream()))
+    at = planes.upload()
+    workspace = torch.empty(conditional_scores_workspace_bytes(n, n_lat, n_lon, E), dtype=torch.uint8, device=dev)
+    read = n * n_lat * n_lon * 4 * sum(fs is not None for _, fs in lists)   # bytes
+    _launch(dev, "conditional_scores", float(read), "aurora_hip_conditional_scores", at["prediction"], at["truth"],
+            at["centre"], at["scale"], n, n_lat, n_lon, _ptr(edges), E, 1 if by_pred else 0, _ptr(row_w), _ptr(sums),
+            _ptr(workspace))
     return sums
 
 
@@ -1177,35 +1239,29 @@ def region_sums(pred: list[torch.Tensor], truth: list[torch.Tensor], clim: Optio
     (n_lat, n_lon) uint8, contiguous, on that device, any alignment; 1 <= n_regions <= 8; row_w: (n_lat,) fp64 on that device.
     The plane-pointer table is cached by address as in `scores_sums`.  Nothing of plane size is allocated and the host does
     not wait for the device."""
-    assert row_w.is_cuda and row_w.dtype == torch.float64 and row_w.dim() == 1 and row_w.is_contiguous(), \
-        "region_sums: row_w must be a contiguous fp64 vector on the device"
+    _operand("region_sums", "row_w", row_w, torch.float64, "fp64 vector", dim=1)
     dev, n_lat = row_w.device, row_w.shape[0]
     assert 1 <= n_regions <= REGION_MAX_PER_CALL, f"region_sums: 1..{REGION_MAX_PER_CALL} regions per call, got {n_regions}"
-    lists = [("prediction", pred), ("truth", truth)] + ([("climatology", clim)] if clim is not None else [])
     n_lon = pred[0].shape[-1] if pred else col_bits.shape[0]
     for what, t, shape in (("row_bits", row_bits, (n_lat,)), ("col_bits", col_bits, (n_lon,)), ("mask_bits", mask_bits, (n_lat, n_lon))):
         if t is not None:
             assert t.dtype == torch.uint8 and tuple(t.shape) == shape and t.is_contiguous(), \
                 f"region_sums: {what} must be a contiguous uint8 tensor of shape {shape}, got {t.dtype} {tuple(t.shape)}"
             assert t.device == dev, "region_sums: every tensor must be on the device of row_w"
-    n, addresses = _plane_lists("region_sums", lists, dev, "row_w", n_lat, n_lon)
+    planes = _planes("region_sums", [("prediction", pred), ("truth", truth), ("climatology", clim)], dev, "row_w", n_lat, n_lon)
+    n = planes.n
     sums = torch.empty(n, n_regions, 8, dtype=torch.float64, device=dev)
     if n == 0:
         return sums
-    with torch.cuda.device(dev):
-        table = _plane_table("region_sums", tuple(addresses), dev)
-        workspace = torch.empty(region_scores_workspace_bytes(n, n_lat, n_lon, n_regions), dtype=torch.uint8, device=dev)
-        base = table.data_ptr()
-        read = n * n_lat * n_lon * (4 * len(lists) + (1 if mask_bits is not None else 0))
-        with _Timed("region_scores", float(read)):   # bytes read, were every row in some region
-            _check(load().aurora_hip_region_scores(base, base + 8 * n, base + 16 * n if clim is not None else None, n, n_lat,
-                                                   n_lon, _ptr(row_bits), _ptr(col_bits),
-                                                   None if mask_bits is None else _ptr(mask_bits), n_regions, _ptr(row_w),
-                                                   _ptr(sums), _ptr(workspace), _stream()))
+    at = planes.upload()
+    workspace = torch.empty(region_scores_workspace_bytes(n, n_lat, n_lon, n_regions), dtype=torch.uint8, device=dev)
+    read = n * n_lat * n_lon * (4 * (2 if clim is None else 3) + (1 if mask_bits is not None else 0))
+    _launch(dev, "region_scores", float(read),   # bytes read, were every row in some region
+            "aurora_hip_region_scores", at["prediction"], at["truth"], at["climatology"], n, n_lat, n_lon, _ptr(row_bits),
+            _ptr(col_bits), _ptr(mask_bits), n_regions, _ptr(row_w), _ptr(sums), _ptr(workspace))
     return sums
 
 
-# ---- event probabilities of an ensemble (aurora_hip_probability_scores) -----------------------------------------------
 # ---- threshold objects: connected components and their table (aurora_hip_objects) ------------------------------------------
 OBJECT_MAX_THRESHOLDS, OBJECT_MAX_LON, OBJECT_COLUMNS, OBJECT_MAX_POINTS = 8, 4096, 10, 2 ** 31 - 2
 
@@ -1227,37 +1283,26 @@ def object_labels(fields: list[torch.Tensor], thresholds: torch.Tensor, unit: to
     those shapes; workspace: a uint8 tensor of at least `objects_workspace_bytes` bytes -- both are allocated when not given
     (the workspace is plane-sized: 4 bytes per point and threshold).  The plane-pointer table is cached by address as in
     `scores_sums`.  The host does not wait for the device."""
-    assert thresholds.is_cuda and thresholds.dtype == torch.float32 and thresholds.dim() == 2 and thresholds.is_contiguous(), \
-        "object_labels: thresholds must be a contiguous (n_planes, T) fp32 matrix on the device"
+    _operand("object_labels", "thresholds", thresholds, torch.float32, "(n_planes, T) fp32 matrix", dim=2)
     dev, (n_thr_planes, T) = thresholds.device, thresholds.shape
     assert 1 <= T <= OBJECT_MAX_THRESHOLDS, f"object_labels: 1..{OBJECT_MAX_THRESHOLDS} thresholds, got {T}"
     assert fields, "object_labels: the list of fields is empty"
     n_lat, n_lon = fields[0].shape[-2:]
-    assert unit.device == dev and unit.dtype == torch.int64 and tuple(unit.shape) == (n_lat,) and unit.is_contiguous(), \
-        "object_labels: unit must be a contiguous (n_lat,) int64 vector on the device of thresholds"
+    _operand("object_labels", "unit", unit, torch.int64, "(n_lat,) int64 vector", dev=dev, anchor="thresholds", shape=(n_lat,))
     max_objects = int(max_objects)
-    n, addresses = _plane_lists("object_labels", [("field", fields)], dev, "thresholds", n_lat, n_lon)
+    planes = _planes("object_labels", [("field", fields)], dev, "thresholds", n_lat, n_lon)
+    n = planes.n
     assert n == n_thr_planes, f"object_labels: {n} planes but thresholds for {n_thr_planes}"
-    shapes = ((n, T, n_lat, n_lon), (n, T), (n, T, max(max_objects, 0), OBJECT_COLUMNS))
-    dtypes = (torch.int32, torch.int32, torch.int64)
-    if out is None:
-        out = tuple(torch.empty(s, dtype=d, device=dev) for s, d in zip(shapes, dtypes))
-    for t, s, d, what in zip(out, shapes, dtypes, ("labels", "count", "table")):
-        assert t.device == dev and t.dtype == d and tuple(t.shape) == s and t.is_contiguous(), \
-            f"object_labels: {what} must be a contiguous {d} tensor of shape {s} on the device of thresholds"
-    labels, count, table = out
+    labels, count, table = _outputs("object_labels", out, (((n, T, n_lat, n_lon), torch.int32, "labels"), ((n, T), torch.int32, "count"),
+                                                           ((n, T, max(max_objects, 0), OBJECT_COLUMNS), torch.int64, "table")),
+                                    dev, "thresholds")
     if n == 0:
         return labels, count, table
-    with torch.cuda.device(dev):
-        planes = _plane_table("object_labels", tuple(addresses), dev)
-        if workspace is None:
-            workspace = torch.empty(objects_workspace_bytes(n, n_lat, n_lon, T), dtype=torch.uint8, device=dev)
-        assert workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous(), \
-            "object_labels: the workspace must be a contiguous uint8 tensor on the device of thresholds"
-        with _Timed("objects", 0.0):
-            _check(load().aurora_hip_objects(planes.data_ptr(), n, n_lat, n_lon, _ptr(thresholds), T, _ptr(unit),
-                                             1 if below else 0, int(connectivity), 1 if wrap else 0, max_objects, _ptr(labels),
-                                             _ptr(count), _ptr(table), _ptr(workspace), workspace.numel(), _stream()))
+    at = planes.upload()
+    workspace = _workspace("object_labels", workspace, dev, "thresholds", objects_workspace_bytes, n, n_lat, n_lon, T)
+    _launch(dev, "objects", 0.0, "aurora_hip_objects", at["field"], n, n_lat, n_lon, _ptr(thresholds), T, _ptr(unit),
+            1 if below else 0, int(connectivity), 1 if wrap else 0, max_objects, _ptr(labels), _ptr(count), _ptr(table),
+            _ptr(workspace), workspace.numel())
     return labels, count, table
 
 
@@ -1280,33 +1325,20 @@ def object_pairs(labels_a: torch.Tensor, labels_b: torch.Tensor, unit: torch.Ten
     the rows.  out: (pairs, count) to write into, contiguous and of those shapes; workspace: a uint8 tensor of at least
     `object_matches_workspace_bytes` bytes -- both are allocated when not given (the workspace holds hash tables only: 48 to 96
     bytes per pair of max_pairs and item).  The host does not wait for the device."""
-    assert labels_a.is_cuda and labels_a.dtype == torch.int32 and labels_a.dim() >= 2 and labels_a.is_contiguous(), \
-        "object_pairs: labels_a must be a contiguous (..., n_lat, n_lon) int32 tensor on the device"
-    dev, (n_lat, n_lon), lead = labels_a.device, labels_a.shape[-2:], tuple(labels_a.shape[:-2])
+    dev, (n_lat, n_lon), lead = _label_maps("object_pairs", "labels_a", labels_a)
     assert labels_b.device == dev and labels_b.dtype == torch.int32 and labels_b.shape == labels_a.shape and labels_b.is_contiguous(), \
         f"object_pairs: labels_b must be a contiguous int32 tensor of shape {tuple(labels_a.shape)} on the device of labels_a"
-    assert unit.device == dev and unit.dtype == torch.int64 and tuple(unit.shape) == (n_lat,) and unit.is_contiguous(), \
-        "object_pairs: unit must be a contiguous (n_lat,) int64 vector on the device of labels_a"
+    _operand("object_pairs", "unit", unit, torch.int64, "(n_lat,) int64 vector", dev=dev, anchor="labels_a", shape=(n_lat,))
     max_objects_a, max_objects_b, max_pairs = int(max_objects_a), int(max_objects_b), int(max_pairs)
     n = int(np.prod(lead, dtype=np.int64))
-    shapes, dtypes = ((*lead, max(max_pairs, 0), OBJECT_PAIR_COLUMNS), lead), (torch.int64, torch.int32)
-    if out is None:
-        out = tuple(torch.empty(s, dtype=d, device=dev) for s, d in zip(shapes, dtypes))
-    for t, s, d, what in zip(out, shapes, dtypes, ("pairs", "count")):
-        assert t.device == dev and t.dtype == d and tuple(t.shape) == s and t.is_contiguous(), \
-            f"object_pairs: {what} must be a contiguous {d} tensor of shape {s} on the device of labels_a"
-    pairs, count = out
+    pairs, count = _outputs("object_pairs", out, (((*lead, max(max_pairs, 0), OBJECT_PAIR_COLUMNS), torch.int64, "pairs"),
+                                                  (lead, torch.int32, "count")), dev, "labels_a")
     if n == 0:
         return pairs, count
-    with torch.cuda.device(dev):
-        if workspace is None:
-            workspace = torch.empty(object_matches_workspace_bytes(n, max_pairs), dtype=torch.uint8, device=dev)
-        assert workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous(), \
-            "object_pairs: the workspace must be a contiguous uint8 tensor on the device of labels_a"
-        with _Timed("object_matches", float(8 * n * n_lat * n_lon)):   # bytes read: both maps once
-            _check(load().aurora_hip_object_matches(_ptr(labels_a), _ptr(labels_b), n, n_lat, n_lon, _ptr(unit), max_objects_a,
-                                                    max_objects_b, max_pairs, _ptr(count), _ptr(pairs), _ptr(workspace),
-                                                    workspace.numel(), _stream()))
+    workspace = _workspace("object_pairs", workspace, dev, "labels_a", object_matches_workspace_bytes, n, max_pairs)
+    _launch(dev, "object_matches", float(8 * n * n_lat * n_lon),   # bytes read: both maps once
+            "aurora_hip_object_matches", _ptr(labels_a), _ptr(labels_b), n, n_lat, n_lon, _ptr(unit), max_objects_a, max_objects_b,
+            max_pairs, _ptr(count), _ptr(pairs), _ptr(workspace), workspace.numel())
     return pairs, count
 
 
@@ -1329,29 +1361,18 @@ def nearest_event_maps(labels: torch.Tensor, tables: torch.Tensor, wrap: bool, k
     (a HOST number, passed by value).  out: (index, key) to write into, contiguous and of those shapes; workspace: a uint8 tensor
     of at least `nearest_event_workspace_bytes` bytes -- both are allocated when not given (the workspace is plane-sized: 2 bytes
     per point).  The host does not wait for the device."""
-    assert labels.is_cuda and labels.dtype == torch.int32 and labels.dim() >= 2 and labels.is_contiguous(), \
-        "nearest_event_maps: labels must be a contiguous (..., n_lat, n_lon) int32 tensor on the device"
-    dev, (n_lat, n_lon), lead = labels.device, labels.shape[-2:], tuple(labels.shape[:-2])
-    assert tables.device == dev and tables.dtype == torch.float64 and tuple(tables.shape) == (2 * n_lat + n_lon,) and tables.is_contiguous(), \
-        "nearest_event_maps: tables must be a contiguous (2 n_lat + n_lon,) fp64 vector on the device of labels"
+    dev, (n_lat, n_lon), lead = _label_maps("nearest_event_maps", "labels", labels)
+    _operand("nearest_event_maps", "tables", tables, torch.float64, "(2 n_lat + n_lon,) fp64 vector", dev=dev, anchor="labels",
+             shape=(2 * n_lat + n_lon,))
     n = int(np.prod(lead, dtype=np.int64))
-    dtypes = (torch.int32, torch.float64)
-    if out is None:
-        out = tuple(torch.empty(labels.shape, dtype=d, device=dev) for d in dtypes)
-    for t, d, what in zip(out, dtypes, ("index", "key")):
-        assert t.device == dev and t.dtype == d and t.shape == labels.shape and t.is_contiguous(), \
-            f"nearest_event_maps: {what} must be a contiguous {d} tensor of shape {tuple(labels.shape)} on the device of labels"
-    index, key = out
+    index, key = _outputs("nearest_event_maps", out, ((labels.shape, torch.int32, "index"), (labels.shape, torch.float64, "key")),
+                          dev, "labels")
     if n == 0:
         return index, key
-    with torch.cuda.device(dev):
-        if workspace is None:
-            workspace = torch.empty(nearest_event_workspace_bytes(n, n_lat, n_lon), dtype=torch.uint8, device=dev)
-        assert workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous(), \
-            "nearest_event_maps: the workspace must be a contiguous uint8 tensor on the device of labels"
-        with _Timed("nearest_event", float(16 * n * n_lat * n_lon)):   # bytes: the map read once, the two maps written
-            _check(load().aurora_hip_nearest_event(_ptr(labels), n, n_lat, n_lon, _ptr(tables), 1 if wrap else 0, float(key_max),
-                                                   _ptr(index), _ptr(key), _ptr(workspace), workspace.numel(), _stream()))
+    workspace = _workspace("nearest_event_maps", workspace, dev, "labels", nearest_event_workspace_bytes, n, n_lat, n_lon)
+    _launch(dev, "nearest_event", float(16 * n * n_lat * n_lon),   # bytes: the map read once, the two maps written
+            "aurora_hip_nearest_event", _ptr(labels), n, n_lat, n_lon, _ptr(tables), 1 if wrap else 0, float(key_max), _ptr(index),
+            _ptr(key), _ptr(workspace), workspace.numel())
     return index, key
 
 
@@ -1363,28 +1384,20 @@ def object_separation_table(labels_a: torch.Tensor, key: torch.Tensor, index: to
 
     labels_a, index: contiguous int32 (*lead, n_lat, n_lon) on one device; key: contiguous fp64 of that shape; count_a:
     contiguous int32 (*lead).  out: (table, hausdorff) to write into.  The host does not wait for the device."""
-    assert labels_a.is_cuda and labels_a.dtype == torch.int32 and labels_a.dim() >= 2 and labels_a.is_contiguous(), \
-        "object_separation_table: labels_a must be a contiguous (..., n_lat, n_lon) int32 tensor on the device"
-    dev, (n_lat, n_lon), lead = labels_a.device, labels_a.shape[-2:], tuple(labels_a.shape[:-2])
+    dev, (n_lat, n_lon), lead = _label_maps("object_separation_table", "labels_a", labels_a)
     for t, d, s, what in ((key, torch.float64, labels_a.shape, "key"), (index, torch.int32, labels_a.shape, "index"),
                           (count_a, torch.int32, lead, "count_a")):
-        assert t.device == dev and t.dtype == d and tuple(t.shape) == tuple(s) and t.is_contiguous(), \
-            f"object_separation_table: {what} must be a contiguous {d} tensor of shape {tuple(s)} on the device of labels_a"
+        _like("object_separation_table", what, t, s, d, dev, "labels_a")
     max_objects = int(max_objects)
     n = int(np.prod(lead, dtype=np.int64))
-    shapes = ((*lead, max(max_objects, 0), SEPARATION_COLUMNS), lead)
-    if out is None:
-        out = tuple(torch.empty(s, dtype=torch.int64, device=dev) for s in shapes)
-    for t, s, what in zip(out, shapes, ("table", "hausdorff")):
-        assert t.device == dev and t.dtype == torch.int64 and tuple(t.shape) == s and t.is_contiguous(), \
-            f"object_separation_table: {what} must be a contiguous int64 tensor of shape {s} on the device of labels_a"
-    table, hausdorff = out
+    table, hausdorff = _outputs("object_separation_table", out,
+                                (((*lead, max(max_objects, 0), SEPARATION_COLUMNS), torch.int64, "table"), (lead, torch.int64, "hausdorff")),
+                                dev, "labels_a", "{what} must be a contiguous int64 tensor of shape {shape} on the device of {anchor}")
     if n == 0:
         return table, hausdorff
-    with torch.cuda.device(dev):
-        with _Timed("object_separations", float(32 * n * n_lat * n_lon)):   # bytes: label, key and index read twice
-            _check(load().aurora_hip_object_separations(_ptr(labels_a), _ptr(key), _ptr(index), _ptr(count_a), n, n_lat, n_lon,
-                                                        max_objects, _ptr(table), _ptr(hausdorff), _stream()))
+    _launch(dev, "object_separations", float(32 * n * n_lat * n_lon),   # bytes: label, key and index read twice
+            "aurora_hip_object_separations", _ptr(labels_a), _ptr(key), _ptr(index), _ptr(count_a), n, n_lat, n_lon, max_objects,
+            _ptr(table), _ptr(hausdorff))
     return table, hausdorff
 
 
@@ -1409,62 +1422,19 @@ def field_quantile_values(fields: list[torch.Tensor], q, unit: Optional[torch.Te
     Q = qs.shape[0]
     assert 1 <= Q <= QUANTILES_MAX, f"field_quantile_values: 1..{QUANTILES_MAX} values of q, got {Q}"
     dev, (n_lat, n_lon) = fields[0].device, fields[0].shape[-2:]
-    assert unit is None or (unit.device == dev and unit.dtype == torch.int64 and tuple(unit.shape) == (n_lat,) and unit.is_contiguous()), \
-        "field_quantile_values: unit must be a contiguous (n_lat,) int64 vector on the device of the fields"
-    n, addresses = _plane_lists("field_quantile_values", [("field", fields)], dev, "the first field", n_lat, n_lon)
-    shapes, dtypes = ((n, Q), (n,), (n,)), (torch.float32, torch.int64, torch.int64)
-    if out is None:
-        out = tuple(torch.empty(s, dtype=d, device=dev) for s, d in zip(shapes, dtypes))
-    for t, s, d, what in zip(out, shapes, dtypes, ("values", "valid", "total")):
-        assert t.device == dev and t.dtype == d and tuple(t.shape) == s and t.is_contiguous(), \
-            f"field_quantile_values: {what} must be a contiguous {d} tensor of shape {s} on the device of the fields"
-    values, valid, total = out
+    if unit is not None:
+        _operand("field_quantile_values", "unit", unit, torch.int64, "(n_lat,) int64 vector", dev=dev, anchor="the fields", shape=(n_lat,))
+    planes = _planes("field_quantile_values", [("field", fields)], dev, "the first field", n_lat, n_lon)
+    n = planes.n
+    values, valid, total = _outputs("field_quantile_values", out, (((n, Q), torch.float32, "values"), ((n,), torch.int64, "valid"),
+                                                                   ((n,), torch.int64, "total")), dev, "the fields")
     if n == 0:
         return values, valid, total
-    with torch.cuda.device(dev):
-        planes = _plane_table("field_quantile_values", tuple(addresses), dev)
-        if workspace is None:
-            workspace = torch.empty(field_quantiles_workspace_bytes(n, Q), dtype=torch.uint8, device=dev)
-        assert workspace.device == dev and workspace.dtype == torch.uint8 and workspace.is_contiguous(), \
-            "field_quantile_values: the workspace must be a contiguous uint8 tensor on the device of the fields"
-        with _Timed("field_quantiles", float(4 * n * n_lat * n_lon * 4)):
-            _check(load().aurora_hip_field_quantiles(planes.data_ptr(), n, n_lat, n_lon, _ptr(unit), qs.ctypes.data, Q,
-                                                     _ptr(values), _ptr(valid), _ptr(total), _ptr(workspace),
-                                                     workspace.numel(), _stream()))
+    at = planes.upload()
+    workspace = _workspace("field_quantile_values", workspace, dev, "the fields", field_quantiles_workspace_bytes, n, Q)
+    _launch(dev, "field_quantiles", float(4 * n * n_lat * n_lon * 4), "aurora_hip_field_quantiles", at["field"], n, n_lat, n_lon,
+            _ptr(unit), qs.ctypes.data, Q, _ptr(values), _ptr(valid), _ptr(total), _ptr(workspace), workspace.numel())
     return values, valid, total
-
-
-def probability_rows(members: list[list[torch.Tensor]], truth: list[torch.Tensor], thresholds: torch.Tensor,
-                     below: bool = False) -> torch.Tensor:
-    """The integer table of include/aurora_hip.h -- per row of every plane, threshold and (event observed o, k of M members
-    forecasting it) the number of valid points -- in ONE aurora_hip_probability_scores call: an (n_planes, n_lat, T, 2, M + 1)
-    int32 tensor on the device.
-
-    members: M lists (2 <= M <= 64), each like `truth`: fp32 (..., n_lat, n_lon) tensors on one device with row-major
-    contiguous planes (any leading strides, any 4-byte plane alignment) and the leading shapes of `truth`; thresholds:
-    contiguous (n_planes, T) fp32 on that device (NaN: no event).  The plane-pointer table is cached by address as in
-    `scores_sums`.  Nothing but the result is allocated and the host does not wait for the device."""
-    assert thresholds.is_cuda and thresholds.dtype == torch.float32 and thresholds.dim() == 2 and thresholds.is_contiguous(), \
-        "probability_rows: thresholds must be a contiguous (n_planes, T) fp32 matrix on the device"
-    dev, (n_thr_planes, T) = thresholds.device, thresholds.shape
-    M = len(members)
-    assert 2 <= M <= ENSEMBLE_MAX_MEMBERS, f"probability_rows: members must hold 2..{ENSEMBLE_MAX_MEMBERS} lists, got {M}"
-    assert 1 <= T <= EVENT_MAX_THRESHOLDS, f"probability_rows: 1..{EVENT_MAX_THRESHOLDS} thresholds, got {T}"
-    assert truth and all(len(fs) == len(truth) for fs in members), "probability_rows: the lists differ in length or are empty"
-    n_lat, n_lon = truth[0].shape[-2:]
-    lists = [(f"member {m}", fs) for m, fs in enumerate(members)] + [("truth", truth)]
-    n, addresses = _plane_lists("probability_rows", lists, dev, "thresholds", n_lat, n_lon, like=-1)
-    assert n == n_thr_planes, f"probability_rows: {n} planes but thresholds for {n_thr_planes}"
-    rows = torch.empty(n, n_lat, T, 2, M + 1, dtype=torch.int32, device=dev)
-    if n == 0:
-        return rows
-    with torch.cuda.device(dev):
-        table = _plane_table("probability_rows", tuple(addresses), dev)
-        base = table.data_ptr()
-        with _Timed("probability_scores", 0.0):
-            _check(load().aurora_hip_probability_scores(base, base + 8 * M * n, M, n, n_lat, n_lon, _ptr(thresholds), T,
-                                                        1 if below else 0, _ptr(rows), _stream()))
-    return rows
 
 
 # ---- per-point statistics over a sequence of planes (aurora_hip_field_stats_update) -----------------------------------
@@ -1497,23 +1467,26 @@ def field_stats_update(samples: list[list[torch.Tensor]], ref: Optional[list[tor
     assert sample_index.is_cuda and sample_index.dtype == torch.int64 and sample_index.numel() == 1, \
         "field_stats_update: sample_index must be one int64 on the device"
     n_lat, n_lon = samples[0][0].shape[-2:]
-    lists = [(f"sample {s}", fs) for s, fs in enumerate(samples)] + ([("reference", ref)] if ref is not None else [])
-    n, addresses = _plane_lists("field_stats_update", lists, dev, "sample_index", n_lat, n_lon)
+    lists = [(f"sample {s}", fs) for s, fs in enumerate(samples)] + [("reference", ref)]
+    planes = _planes("field_stats_update", lists, dev, "sample_index", n_lat, n_lon)
+    n = planes.n
+    seconds = None
     if second is not None:
         assert len(second) == S and all(len(fs) == len(samples[0]) for fs in second), \
             "field_stats_update: the second operands differ from the samples in number"
+        seconds = []
         for s, fs in enumerate(second):
             for v, p in zip(fs, samples[s]):
                 if v is None:
-                    addresses += [0] * (p.numel() // (n_lat * n_lon))
+                    seconds += [0] * (p.numel() // (n_lat * n_lon))
                     continue
                 assert v.device == dev and v.shape == p.shape, "field_stats_update: a second operand differs from its sample"
-                addresses += _plane_addresses("field_stats_update", [v], n_lat, n_lon, "second operand")
+                seconds += _plane_addresses("field_stats_update", [v], n_lat, n_lon, "second operand")
+    planes.add("second", seconds)
     T = 0
     if thresholds is not None:
-        assert thresholds.device == dev and thresholds.dtype == torch.float32 and thresholds.dim() == 2 and \
-            thresholds.is_contiguous() and thresholds.shape[0] == n, \
-            f"field_stats_update: thresholds must be a contiguous ({n}, T) fp32 matrix on the device"
+        _operand("field_stats_update", "thresholds", thresholds, torch.float32, f"({n}, T) fp32 matrix", dev=dev, dim=2,
+                 shape=(n, *thresholds.shape[1:2]))
         T = thresholds.shape[1]
         assert T <= FIELD_STATS_MAX_THRESHOLDS, f"field_stats_update: at most {FIELD_STATS_MAX_THRESHOLDS} thresholds, got {T}"
     for name, (dt, per_thr) in FIELD_STATS_STATE.items():
@@ -1525,16 +1498,11 @@ def field_stats_update(samples: list[list[torch.Tensor]], ref: Optional[list[tor
             f"field_stats_update: state {name!r} must be contiguous {dt} of {want} on the device"
     if n == 0:
         return
-    with torch.cuda.device(dev):
-        table = _plane_table("field_stats_update", tuple(addresses), dev)
-        base = table.data_ptr()
-        ref_at = base + 8 * S * n if ref is not None else None
-        second_at = base + 8 * (S + (ref is not None)) * n if second is not None else None
-        arrays = [_ptr(state[k]) if (T or not per_thr) else None for k, (_, per_thr) in FIELD_STATS_STATE.items()]
-        with _Timed("field_stats", float(n * n_lat * n_lon * (4 * S + 2 * (36 + 12 * T)))):
-            _check(load().aurora_hip_field_stats_update(base, ref_at, second_at, S, n, n_lat * n_lon,
-                                                        _ptr(thresholds) if T else None, T, 1 if below else 0,
-                                                        _ptr(sample_index), *arrays, _stream()))
+    at = planes.upload()
+    arrays = [_ptr(state[k]) if (T or not per_thr) else None for k, (_, per_thr) in FIELD_STATS_STATE.items()]
+    _launch(dev, "field_stats", float(n * n_lat * n_lon * (4 * S + 2 * (36 + 12 * T))), "aurora_hip_field_stats_update",
+            at["sample 0"], at["reference"], at["second"], S, n, n_lat * n_lon, _ptr(thresholds) if T else None, T,
+            1 if below else 0, _ptr(sample_index), *arrays)
 
 
 # ---- derived fields (aurora_hip_diagnostics) ----------------------------------------------------------------------------
@@ -1567,10 +1535,10 @@ def diagnostics(n_lat: int, n_lon: int, *, u: Optional[list[torch.Tensor]] = Non
         return
     dev = tensors[0].device
     assert all(t.device == dev for t in tensors), "diagnostics: every tensor must be on one device"
-    for what, t, shape in (("row_table", row_table, (n_lat, 4)), ("level_w", level_w, None)):
-        assert t is None or (t.device == dev and t.dtype == torch.float64 and t.is_contiguous() and
-                             (t.dim() == 1 if shape is None else tuple(t.shape) == shape)), \
-            f"diagnostics: {what} must be a contiguous fp64 {'vector' if shape is None else shape} on the device of the fields"
+    if row_table is not None:
+        _operand("diagnostics", "row_table", row_table, torch.float64, f"fp64 {(n_lat, 4)}", dev=dev, anchor="the fields", shape=(n_lat, 4))
+    if level_w is not None:
+        _operand("diagnostics", "level_w", level_w, torch.float64, "fp64 vector", dev=dev, anchor="the fields", dim=1)
     addr = {}
     for what, fs in groups:
         if fs is None:
@@ -1594,24 +1562,20 @@ def diagnostics(n_lat: int, n_lon: int, *, u: Optional[list[torch.Tensor]] = Non
             assert what not in addr or len(addr[what]) == n_cols, f"diagnostics: {what} holds {len(addr[what])} planes for {n_cols} columns"
     if n_wind == 0 and n_cols == 0:
         return
-    with torch.cuda.device(dev):
-        order = [what for what, _ in groups if what in addr]
-        table = _plane_table("diagnostics", tuple(a for what in order for a in addr[what]), dev)
-        at, first = {}, table.data_ptr()
-        for what in order:
-            at[what], first = first, first + 8 * len(addr[what])
-        moved = 4.0 * n_lat * n_lon * (n_wind * (2 + sum(k in addr for k in ("vo", "div", "ws"))) +
-                                       n_cols * (C * (1 + sum(k in addr for k in ("col_u", "col_v"))) +
-                                                 sum(k in addr for k in ("tcwv", "ivtu", "ivtv", "ivt"))))
-        with _Timed("diagnostics", moved):
-            _check(load().aurora_hip_diagnostics(at.get("u"), at.get("v"), at.get("vo"), at.get("div"), at.get("ws"), n_wind,
-                                                 _ptr(row_table), float(L), 1 if wrap else 0, at.get("q"), at.get("col_u"),
-                                                 at.get("col_v"), at.get("tcwv"), at.get("ivtu"), at.get("ivtv"), at.get("ivt"),
-                                                 n_cols, C, _ptr(level_w), n_lat, n_lon, _stream()))
+    planes = _planes("diagnostics", [], dev)
+    for what, addresses in addr.items():   # (in the order of `groups`)
+        planes.add(what, addresses)
+    at = planes.upload()
+    moved = 4.0 * n_lat * n_lon * (n_wind * (2 + sum(k in addr for k in ("vo", "div", "ws"))) +
+                                   n_cols * (C * (1 + sum(k in addr for k in ("col_u", "col_v"))) +
+                                             sum(k in addr for k in ("tcwv", "ivtu", "ivtv", "ivt"))))
+    _launch(dev, "diagnostics", moved, "aurora_hip_diagnostics", at.get("u"), at.get("v"), at.get("vo"), at.get("div"), at.get("ws"), n_wind,
+            _ptr(row_table), float(L), 1 if wrap else 0, at.get("q"), at.get("col_u"), at.get("col_v"), at.get("tcwv"), at.get("ivtu"),
+            at.get("ivtv"), at.get("ivt"), n_cols, C, _ptr(level_w), n_lat, n_lon)
 
 
 # ---- model handle (one forecast step behind the C ABI) ------------------------------------------------------
-_PD =ctypes.POINTER(ctypes.c_double)
+_PD = ctypes.POINTER(ctypes.c_double)
 _PF = ctypes.POINTER(ctypes.c_float)
 _PS = ctypes.POINTER(ctypes.c_char_p)
 

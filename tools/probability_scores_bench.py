@@ -90,13 +90,13 @@ def case(M: int, calls: int, repeats: int, plain_lib) -> dict:
     off_corner = (1 - (counts[:, 0, 0] + counts[:, 1, M]).double() / counts.sum(dim=(1, 2)).double()).tolist()
     arms = {"kernel": kernel, "ensemble": ensemble}
     if plain_lib is not None:
-        _, addresses = lib._plane_lists("probability_scores_bench", [("member", fs) for fs in X] + [("truth", Y)], thr.device, "thr",
-                                        N_LAT, N_LON)
-        table = lib._plane_table("probability_scores_bench", tuple(addresses), thr.device)
+        pointers = lib._planes("probability_scores_bench", [(f"member {m}", fs) for m, fs in enumerate(X)] + [("truth", Y)], thr.device,
+                               "thr", N_LAT, N_LON)
+        table = pointers.upload()
         rows_plain = torch.empty_like(got)
 
         def plain():
-            code = plain_lib.aurora_hip_probability_scores(table.data_ptr(), table.data_ptr() + 8 * M * N_PLANES, M, N_PLANES, N_LAT,
+            code = plain_lib.aurora_hip_probability_scores(table["member 0"], table["truth"], M, N_PLANES, N_LAT,
                                                            N_LON, thr.data_ptr(), len(THRESHOLDS), 0, rows_plain.data_ptr(),
                                                            torch.cuda.current_stream().cuda_stream)
             assert code == 0, plain_lib.aurora_hip_last_error()
