@@ -21,7 +21,8 @@ every plane by area or by count, the percentile thresholds those event modules a
 over union, best partner, object POD / FAR / CSI, centroid displacement (aurora_amd/object_matches.py), and `nearest_event` gives
 for every grid point the great-circle distance to the nearest event and which point that is, from which `object_separations`
 takes what objects that do not touch need: minimum boundary separation, Hausdorff distance, "nearest observed object within
-300 km" (aurora_amd/distances.py); the reference has no counterpart.
+300 km" (aurora_amd/distances.py), and `smooth` takes the mean of a field over a great-circle disc of R kilometres, the step
+before thresholding in object-based verification (aurora_amd/smooth.py); the reference has no counterpart.
 """
 
 from aurora_amd.batch import Batch, Metadata
@@ -50,6 +51,7 @@ from aurora_amd.quantiles import EnsembleQuantiles, ensemble_quantiles
 from aurora_amd.regions import Region, Regions, RegionScores, region_scores
 from aurora_amd.rollout import rollout, write_rollout
 from aurora_amd.scores import Scores, scores
+from aurora_amd.smooth import smooth
 from aurora_amd.spectra import Spectra, spectra
 from aurora_amd.tracker import Tracker
 
@@ -97,5 +99,6 @@ __all__ = [
     "ObjectSeparations",
     "field_quantiles",
     "FieldQuantiles",
+    "smooth",
     "Tracker",
 ]

@@ -173,6 +173,9 @@ _SIGNATURES = {
                                          c_void_p, ctypes.c_size_t, c_void_p]),
     "aurora_hip_object_separations": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_int, c_void_p,
                                               c_void_p, c_void_p]),
+    "aurora_hip_smooth_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int]),
+    "aurora_hip_smooth": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
+                                  ctypes.c_double, c_int, c_void_p, ctypes.c_size_t, c_void_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None
@@ -1399,6 +1402,63 @@ def object_separation_table(labels_a: torch.Tensor, key: torch.Tensor, index: to
             "aurora_hip_object_separations", _ptr(labels_a), _ptr(key), _ptr(index), _ptr(count_a), n, n_lat, n_lon, max_objects,
             _ptr(table), _ptr(hausdorff))
     return table, hausdorff
+
+
+# ---- fields smoothed over a great-circle disc (aurora_hip_smooth) -----------------------------------------------------------------
+SMOOTH_MAX_ROWS = 255
+SMOOTH_WORKSPACE_CAP = 128 << 20   # bytes of prefix tables in flight: inside the 256 MiB Infinity Cache
+
+
+def smooth_workspace_bytes(n_planes: int, n_lat: int, n_lon: int) -> int:
+    return int(load().aurora_hip_smooth_workspace_bytes(n_planes, n_lat, n_lon))
+
+
+def smooth_planes(fields: list[torch.Tensor], rows: torch.Tensor, w: torch.Tensor, wrap: bool, min_valid: float = 0.5,
+                  keep_mask: bool = True, *, out: Optional[torch.Tensor] = None, workspace: Optional[torch.Tensor] = None,
+                  workspace_cap: int = SMOOTH_WORKSPACE_CAP) -> torch.Tensor:
+    """Every plane of `fields` smoothed over the disc of the table (include/aurora_hip.h), as an (n_planes, n_lat, n_lon) fp32
+    tensor on the device, by aurora_hip_smooth calls (two launches each) over as many planes at a time as keep the workspace within `workspace_cap` bytes,
+    at least one.
+
+    fields: a list of fp32 (..., n_lat, n_lon) tensors on one device with row-major contiguous planes (any leading strides, any
+    4-byte plane alignment); out: a contiguous tensor of that shape to write into (it must not overlap a field), allocated when
+    not given.  rows: the contiguous
+    int32 vector [row_lo (n_lat) | row_count (n_lat) | half (n_lat x max_rows)] of `aurora_amd.smooth.disc_table` on that device;
+    w: contiguous (n_lat,) fp64.  workspace: a uint8 tensor to use for the prefix tables, of at least
+    `smooth_workspace_bytes(1, n_lat, n_lon)` bytes, or None: one of at most `workspace_cap` bytes is allocated.  The workspace
+    is PLANE-SIZED: 12 bytes per point (and per row one entry more) of the planes in flight.  A plane's bytes do not depend on
+    how the planes are divided.  The plane-pointer table is cached by address as in `scores_sums`.  The host does not wait for
+    the device."""
+    assert fields, "smooth_planes: the list of fields is empty"
+    dev, (n_lat, n_lon) = fields[0].device, fields[0].shape[-2:]
+    _operand("smooth_planes", "w", w, torch.float64, "(n_lat,) fp64 vector", dev=dev, anchor="the fields", shape=(n_lat,))
+    _operand("smooth_planes", "rows", rows, torch.int32, "int32 vector", dev=dev, anchor="the fields", dim=1)
+    max_rows = rows.numel() // n_lat - 2
+    assert rows.numel() == n_lat * (2 + max_rows) and 1 <= max_rows <= SMOOTH_MAX_ROWS, \
+        f"smooth_planes: rows holds {rows.numel()} entries, which is no table of 1..{SMOOTH_MAX_ROWS} source rows for {n_lat} latitudes"
+    planes = _planes("smooth_planes", [("field", fields)], dev, "the first field", n_lat, n_lon)
+    n = planes.n
+    (out,) = _outputs("smooth_planes", None if out is None else (out,), (((n, n_lat, n_lon), torch.float32, "out"),), dev, "the fields")
+    if n == 0:
+        return out
+    one = smooth_workspace_bytes(1, n_lat, n_lon)
+    assert one > 0, f"smooth_planes: a plane of {n_lat} x {n_lon} points is too large"
+    if workspace is None:
+        chunk = min(n, max(1, int(workspace_cap) // one))
+        workspace = torch.empty(smooth_workspace_bytes(chunk, n_lat, n_lon), dtype=torch.uint8, device=dev)
+    else:
+        workspace = _workspace("smooth_planes", workspace, dev, "the fields", smooth_workspace_bytes, 1, n_lat, n_lon)
+        chunk = min(n, workspace.numel() // one)
+        assert chunk >= 1, f"smooth_planes: the workspace has {workspace.numel()} bytes, a plane needs {one}"
+    at = planes.upload()
+    base = rows.data_ptr()
+    for first in range(0, n, chunk):                            # on one stream: the next chunk reuses the workspace
+        m = min(chunk, n - first)
+        _launch(dev, "smooth", float(m * n_lat * n_lon * 8), "aurora_hip_smooth", at["field"] + 8 * first,
+                out.data_ptr() + 4 * first * n_lat * n_lon, m,
+                n_lat, n_lon, base, base + 4 * n_lat, base + 8 * n_lat, max_rows, _ptr(w), 1 if wrap else 0, float(min_valid),
+                1 if keep_mask else 0, _ptr(workspace), workspace.numel())
+    return out
 
 
 # ---- spatial quantiles of planes (aurora_hip_field_quantiles) ------------------------------------------------------------------

@@ -1222,6 +1222,42 @@ int aurora_hip_object_separations(const int32_t* labels_a, const double* key, co
                                   int64_t n_items, int n_lat, int n_lon, int max_objects, int64_t* table, int64_t* hausdorff,
                                   void* stream);
 
+/* ---- fields smoothed over a great-circle disc on the device (aurora_amd.smooth: the mean over all points within R km, the
+ * first step of object-based verification; not in the reference) ----------------------------------------------------------------
+ * Planes as above; out: n_planes x n_lat x n_lon device fp32, one output plane after the other (4-byte aligned).  The disc
+ * is given as a TABLE made on the host in fp64 (aurora_amd/smooth.py: disc_table), and nothing else decides membership:
+ *   row_lo[i], row_count[i]   int32 per target row i: its source rows are k = row_lo[i] + r, r < row_count[i] <= max_rows <= 255
+ *   half[i max_rows + r]      int32: the columns j - n .. j + n of source row k belong to the target (i, j); n = -1: none.  n is
+ *                             the largest gap d with sin_i sin_k + cos_i cos_k cos(d dlambda) >= cos(R / a), a = 6371.229 km
+ *   w[k]                      fp64 per row: cos(lat_k), exactly 0 for a pole row
+ * A point is VALID where it is finite; an invalid point enters as value 0 with count 0.  Per row of a plane the EXCLUSIVE
+ * PREFIX tables P[0 .. n_lon] (fp64 sums of the valid values, P[0] = 0) and N[0 .. n_lon] (int32 counts) give the sum S and
+ * the count C of a window lo = j - n, hi = j + n + 1 (aurora_amd/csrc/smooth_window.h), with W = n_lon:
+ *   wrap = 1 (full circle):  2 n + 1 >= W: P[W];   lo < 0: (P[W] - P[lo + W]) + P[hi];   hi > W: (P[W] - P[lo]) + P[hi - W];
+ *                            otherwise P[hi] - P[lo]
+ *   wrap = 0 (regional):     P[min(hi, W)] - P[max(lo, 0)]
+ * and over the source rows in ascending k, in fp64:
+ *   num = sum w_k S_k,   den = sum w_k C_k,   full = sum w_k F_k,   F = 2 n + 1 (wrap = 1: at most W)
+ *   out = (float)(num / den); NaN where den <= 0, where den / full < min_valid (columns clipped off a regional grid count as
+ *   invalid), where the result is not finite and, with keep_mask = 1, where the centre point itself is not finite.
+ * Two launches on `stream`.  prefix: a wavefront owns one row, walks it in chunks of 256 columns (a lane adds its four values
+ * in order, the lanes' totals go through an inclusive scan with a fixed shuffle tree, the running sum is carried from chunk to
+ * chunk) and writes P and N into `workspace`: aurora_hip_smooth_workspace_bytes(n_planes, n_lat, n_lon) device bytes, 12 per
+ * entry of n_planes x n_lat x (n_lon + 1), PLANE-SIZED, 8-byte aligned, no initialisation needed (0 for an argument out of
+ * range).  gather: a workgroup owns 4 target rows x 256 adjacent columns; a lane reads P and N at its window's ends and writes
+ * one fp32.  No atomics; nothing is reduced across threads; every index is clamped into its row.  16-byte loads are used for a
+ * plane whose pointer is 16-byte aligned where n_lon % 4 == 0: the same elements in the same association either way, so the
+ * output is repeatable bit for bit and depends on the plane's own values and the table alone: not on the other planes, not on
+ * n_planes, not on pointer alignment.  out must not overlap an input plane or the workspace.
+ * n_lat n_lon <= 2^31 - 1, 1 <= max_rows <= 255, 0 <= min_valid <= 1; workspace_size: the bytes at `workspace`, refused if too
+ * few.  Arguments are checked before anything is enqueued (AURORA_E_ARG and aurora_hip_last_error()).  n_planes = 0 is a
+ * no-op.  The inputs are not modified.  No host synchronisation, no allocation, no environment variable: capturable in a
+ * hipGraph. */
+size_t aurora_hip_smooth_workspace_bytes(int n_planes, int n_lat, int n_lon);
+int aurora_hip_smooth(const float* const* planes, float* out, int n_planes, int n_lat, int n_lon, const int32_t* row_lo,
+                      const int32_t* row_count, const int32_t* half, int max_rows, const double* w, int wrap,
+                      double min_valid, int keep_mask, void* workspace, size_t workspace_size, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
