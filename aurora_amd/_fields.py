@@ -16,11 +16,13 @@ from typing import Callable, Optional, Sequence
 import numpy as np
 import torch
 
+from aurora_amd import _sphere
+from aurora_amd._sphere import MAX_LON
 from aurora_amd.batch import BandBatch, Batch
 from aurora_amd.engine.tables import DeviceTables, _upload  # noqa: F401  (tests wrap `_fields._upload` to count uploads)
 
 GROUPS = ("surf_vars", "atmos_vars")
-MAX_MEMBERS, MAX_THRESHOLDS, MAX_LON = 64, 8, 4096
+MAX_MEMBERS, MAX_THRESHOLDS = 64, 8
 Layout = tuple[tuple[str, int, tuple[int, ...]], ...]   # (name, first plane, shape) per variable
 
 
@@ -60,8 +62,7 @@ def latitude_weights(lat) -> np.ndarray:
     lat = np.asarray(lat, dtype=np.float64)
     if lat.ndim != 1 or lat.size == 0:
         raise ValueError("scores: latitudes must be a non-empty vector")
-    if not np.all(np.isfinite(lat)) or lat.max() > 90 or lat.min() < -90:
-        raise ValueError("scores: latitudes must be in the range [-90, 90]")
+    _sphere.check_latitudes("scores", lat, monotonic=None)
     c = np.maximum(np.cos(np.deg2rad(lat)), 0.0)
     mean = c.mean()
     if not mean > 0:
@@ -101,11 +102,11 @@ def check_same_grid(fn: str, a: Batch, b: Batch, a_name: str, b_name: str, cropp
 
 
 def check_longitudes(lon: np.ndarray) -> None:
+    """spectra's refusal of a grid that is no `_sphere.full_circle`."""
     n = lon.shape[0]
     if not 2 <= n <= MAX_LON:
         raise ValueError(f"spectra: the grid has {n} longitudes; 2 to {MAX_LON} are supported")
-    step = 360.0 / n
-    if not np.all(np.abs(lon - lon[0] - np.arange(n, dtype=np.float64) * step) <= 1e-6 * step):
+    if not _sphere.full_circle(lon):
         raise ValueError("spectra: the longitudes must be equally spaced and cover the full circle (a zonal spectrum of a "
                          "regional or irregular grid is not defined)")
 

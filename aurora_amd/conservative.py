@@ -17,7 +17,7 @@ and lat[-1] + 0.5 (lat[-1] - lat[-2]), clipped to [-90, 90] (a row at a pole is 
 sin(edge in radians), with +-90 mapped to exactly +-1; a cell is [lo, hi] with lo < hi in that measure.
 
 Longitude cells.  Longitudes are strictly increasing in [0, 360), at least two.  A grid is a full circle where
-`_fields.check_longitudes` accepts it: then the west edge of the first cell is 0.5 ((lon[-1] - 360) + lon[0]) and the east edge
+`_sphere.full_circle` says so: then the west edge of the first cell is 0.5 ((lon[-1] - 360) + lon[0]) and the east edge
 of the last cell is that plus 360.  Otherwise it is regional, with outer edges half the adjacent spacing beyond the end
 columns.  Interior edges are midpoints; the measure is degrees.
 
@@ -60,6 +60,7 @@ import numpy as np
 import torch
 
 from aurora_amd import _fields
+from aurora_amd._sphere import check_latitudes, full_circle
 from aurora_amd._fields import _host
 from aurora_amd.batch import Batch, derive_metadata
 
@@ -91,11 +92,7 @@ class Plan(NamedTuple):
 def _check_lat(lat: np.ndarray, what: str) -> None:
     if lat.ndim != 1 or lat.shape[0] < 2:
         raise ValueError(f"{FN}: the latitudes of {what} must be a vector of at least 2 values")
-    if not np.all(np.isfinite(lat)) or np.abs(lat).max() > 90:
-        raise ValueError(f"{FN}: the latitudes of {what} must be in the range [-90, 90]")
-    steps = np.diff(lat)
-    if not (np.all(steps > 0) or np.all(steps < 0)):
-        raise ValueError(f"{FN}: the latitudes of {what} must be strictly monotonic")
+    check_latitudes(FN, lat, of=f" of {what}")
 
 
 def _check_lon(lon: np.ndarray, what: str) -> None:
@@ -105,14 +102,6 @@ def _check_lon(lon: np.ndarray, what: str) -> None:
         raise ValueError(f"{FN}: the longitudes of {what} must be in the range [0, 360)")
     if not np.all(np.diff(lon) > 0):
         raise ValueError(f"{FN}: the longitudes of {what} must be strictly increasing")
-
-
-def full_circle(lon: np.ndarray) -> bool:
-    try:
-        _fields.check_longitudes(lon)
-        return True
-    except ValueError:
-        return False
 
 
 def lat_cells(lat: np.ndarray) -> tuple[np.ndarray, np.ndarray]:

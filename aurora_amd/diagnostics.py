@@ -23,8 +23,8 @@ Arithmetic (include/aurora_hip.h has it in full): inputs fp32, every expression 
 is not finite is NaN.  Horizontal derivatives are centred differences on the sphere (a = 6 371 229 m) with the three-point
 formula for unequal latitude spacing, one-sided in the first and last row; the true latitudes enter, so ascending and
 descending grids need no flag.  Pole rows (|lat| >= 90 - 1e-9) are NaN -- every scorer here skips them -- and there is no
-polar-cap formula.  Longitudes must be equally spaced: a grid that covers the full circle wraps, any other is taken as
-regional and its first and last column use one-sided differences.  Vertical integrals are trapezoids over the batch's
+polar-cap formula.  Longitudes follow THE GRID RULE of aurora_amd/_sphere.py: a grid that wraps by it takes its differences
+across the seam, a regional one uses one-sided differences in its first and last column.  Vertical integrals are trapezoids over the batch's
 pressure levels (2 to 64, any order, distinct; g = 9.80665 m s^-2); nothing is extrapolated to the surface or to the top,
 and no level is masked below the ground (the model has no surface pressure).  A NaN or an infinity that a formula reads
 makes that point NaN and no other.
@@ -43,13 +43,14 @@ from typing import Optional, Sequence, Union
 import numpy as np
 import torch
 
-from aurora_amd import _fields
+from aurora_amd import _fields, _sphere
 from aurora_amd._fields import _host
+from aurora_amd._sphere import EARTH_RADIUS
 from aurora_amd.batch import Batch
 
 __all__ = ["diagnostics", "EARTH_RADIUS", "GRAVITY", "MAX_LEVELS", "NAMES"]
 
-EARTH_RADIUS, GRAVITY = 6371229.0, 9.80665
+GRAVITY = 9.80665
 MAX_LEVELS = 64
 # name -> (group, kind, components)
 NAMES = {"ws": ("atmos_vars", "ws", ("u", "v")), "vo": ("atmos_vars", "vo", ("u", "v")), "d": ("atmos_vars", "div", ("u", "v")),
@@ -99,20 +100,8 @@ def level_weights(levels) -> np.ndarray:
 
 
 def _grid(lat: np.ndarray, lon: np.ndarray) -> tuple[float, bool]:
-    """(L = 1 / (2 dlambda), wrap) of a checked grid."""
-    n_lat, n_lon = lat.shape[0], lon.shape[0]
-    if n_lat < 2 or n_lon < 2:
-        raise ValueError(f"diagnostics: the grid has {n_lat} latitudes and {n_lon} longitudes; at least 2 of each are needed")
-    steps = np.diff(lat)
-    if not (np.all(steps > 0) or np.all(steps < 0)):
-        raise ValueError("diagnostics: the latitudes must be strictly monotonic")
-    try:
-        _fields.check_longitudes(lon)
-        wrap, step = True, 360.0 / n_lon
-    except ValueError:
-        wrap, step = False, (lon[-1] - lon[0]) / (n_lon - 1)
-    if not step > 0 or not np.all(np.abs(lon - lon[0] - np.arange(n_lon, dtype=np.float64) * step) <= 1e-6 * step):
-        raise ValueError("diagnostics: the longitudes must be equally spaced")
+    """(L = 1 / (2 dlambda), wrap) of a grid checked by THE GRID RULE (aurora_amd/_sphere.py); the range of the latitudes is left unchecked."""
+    step, wrap = _sphere.regular_grid("diagnostics", lat, lon, least=2, in_range=False)
     return 1.0 / (2.0 * np.deg2rad(step)), wrap
 
 

@@ -24,8 +24,7 @@ THE RULE (both paths, aurora_amd/csrc/nearest_event_search.h and the tests refer
  1. Tables, made once on the host in numpy fp64 from the coordinates of the `Objects`: s[i] = sin(rad(lat_i)),
     c[i] = max(cos(rad(lat_i)), 0), cd[d] = cos(rad(d dlon)) for d = 0 .. W - 1 with cd[0] = 1 exactly.  dlon is the longitude step:
     360 / W on a wrapping grid (`o.wrap`), (lon[W - 1] - lon[0]) / (W - 1) otherwise.  Longitudes must be equally spaced by that
-    step, to the tolerance of `_fields.check_longitudes` (a millionth of a step), latitudes strictly monotone within [-90, 90];
-    otherwise ValueError.
+    step and latitudes strictly monotone within [-90, 90], both by THE GRID RULE of aurora_amd/_sphere.py; otherwise ValueError.
  2. An EVENT is a point with label > 0; that includes objects numbered above `max_objects`.  The GAP of columns j and j' is
     d = |j - j'|, on a wrapping grid min(d, W - d).
  3. The ROW CANDIDATE of target column j in source row k is the event of row k with the smallest gap, of two at the same gap the
@@ -38,7 +37,7 @@ THE RULE (both paths, aurora_amd/csrc/nearest_event_search.h and the tests refer
  6. `max_km`, if given, is a positive finite number, converted once on the host to key_max = 1 - cos(min(max_km 1000 /
     EARTH_RADIUS, pi)) in fp64; candidates with key > key_max are ignored.
  7. label = labels at index, 0 for none.  distance_km = EARTH_RADIUS / 1000 * 2 asin(sqrt(key / 2)) with the `_sqrt` and `_asin`
-    of `object_matches`, torch code shared by both devices; NaN for none.
+    of aurora_amd/_sphere.py, torch code shared by both devices; NaN for none.
 
 The nearest is defined through row candidates on purpose.  For equally spaced longitudes the candidate is the nearest point of
 its row -- for two fixed rows the distance grows with the gap -- so this is the true nearest point; and it stays well defined
@@ -66,17 +65,15 @@ finalised from them.
 from __future__ import annotations
 
 import dataclasses
-import functools
 import math
 from typing import Optional
 
 import numpy as np
 import torch
 
-from aurora_amd import _fields
-from aurora_amd.diagnostics import EARTH_RADIUS
-from aurora_amd.object_matches import _asin, _same_values, _sqrt
-from aurora_amd.objects import Objects
+from aurora_amd import _fields, _sphere
+from aurora_amd._sphere import EARTH_RADIUS, _km
+from aurora_amd.objects import Objects, Result, check_pair, final_properties
 
 __all__ = ["nearest_event", "NearestEvent", "object_separations", "ObjectSeparations", "COLUMNS", "MARGIN"]
 
@@ -92,18 +89,15 @@ _ON_CAPTURE = ("nearest_event: call once on this grid before capturing a graph (
 def tables_of(lat: np.ndarray, lon: np.ndarray, wrap: bool) -> tuple[np.ndarray, np.ndarray, np.ndarray]:
     """(s, c, cd) of THE RULE, point 1."""
     lat, lon = np.asarray(lat, dtype=np.float64), np.asarray(lon, dtype=np.float64)
-    H, W = lat.shape[0], lon.shape[0]
-    if not np.all(np.isfinite(lat)) or lat.max() > 90 or lat.min() < -90:
-        raise ValueError("nearest_event: latitudes must be in the range [-90, 90]")
-    if H > 1 and not (np.all(np.diff(lat) > 0) or np.all(np.diff(lat) < 0)):
-        raise ValueError("nearest_event: the latitudes must be strictly monotone (the row walk relies on rows farther away in "
-                         "index being farther away in latitude)")
+    W = lon.shape[0]
+    _sphere.check_latitudes("nearest_event", lat, monotonic="monotone (the row walk relies on rows farther away in index being "
+                            "farther away in latitude)")
     if not 1 <= W <= _fields.MAX_LON:
         raise ValueError(f"nearest_event: the grid has {W} longitudes; 1 to {_fields.MAX_LON} are supported")
     step = 0.0
     if W > 1:
         step = 360.0 / W if wrap else float(lon[-1] - lon[0]) / (W - 1)
-        if not np.all(np.isfinite(lon)) or step == 0 or not np.all(np.abs(lon - lon[0] - np.arange(W, dtype=np.float64) * step) <= 1e-6 * abs(step)):
+        if not np.all(np.isfinite(lon)) or step == 0 or not _sphere.equally_spaced(lon, step):
             how = "and cover the full circle on a wrapping grid" if wrap else "(the nearest event of a row is found by its column gap)"
             raise ValueError(f"nearest_event: the longitudes must be equally spaced {how}")
     s = np.sin(np.deg2rad(lat))
@@ -239,22 +233,13 @@ def _separations_host(la: np.ndarray, key: np.ndarray, index: np.ndarray, count:
 
 
 # ---- finalisation: the same torch code on either device ----------------------------------------------------------------
-def _km(key: torch.Tensor) -> torch.Tensor:
-    """EARTH_RADIUS / 1000 * 2 asin(sqrt(key / 2)) for finite keys in [0, 2], +inf for +inf; products, sums and quotients of
-    tensors alone (`_sqrt`, `_asin`), so the same bits on either device.  (key * 0.5 is exact.)"""
-    finite = torch.isfinite(key)
-    half = torch.where(finite, key, torch.zeros_like(key)) * 0.5
-    km = (2.0 * EARTH_RADIUS / 1000.0) * _asin(_sqrt(half.clamp(0.0, 1.0)))
-    return torch.where(finite, km, torch.full_like(km, float("inf")))
-
-
 def _gather_points(values: torch.Tensor, point: torch.Tensor) -> torch.Tensor:
     """values (*lead, H, W) at the flat indices point (*lead, M); where point is -1, at 0 (the caller masks)."""
     return values.reshape(*values.shape[:-2], -1).gather(-1, point.clamp(min=0).to(torch.int64))
 
 
 @dataclasses.dataclass(eq=False)
-class NearestEvent:
+class NearestEvent(Result):
     """Result of `nearest_event`: every property is a dict name -> tensor with the leading shape (B,) for a surface variable and
     (B, C) for an atmospheric one, on the device of the `Objects`."""
 
@@ -262,12 +247,9 @@ class NearestEvent:
     key_table: torch.Tensor                               # (n_planes, T, H, W) fp64
     objects: Objects
     max_km: Optional[float]
+    _owner = "objects"
 
-    def _field(self, t: torch.Tensor) -> dict[str, torch.Tensor]:
-        return _fields.by_variable(self.objects.layout, t)
-
-    @functools.cached_property
-    def _final(self) -> dict[str, torch.Tensor]:
+    def _finalise(self) -> dict[str, torch.Tensor]:
         none = self.index_table < 0
         flat = self.index_table.reshape(*self.index_table.shape[:-2], -1)
         label = _gather_points(self.objects.labels_table, flat).reshape(self.index_table.shape)
@@ -316,7 +298,7 @@ def _finalise(table: torch.Tensor, hausdorff: torch.Tensor, a: Objects, b: Objec
 
 
 @dataclasses.dataclass(eq=False)
-class ObjectSeparations:
+class ObjectSeparations(Result):
     """Result of `object_separations`: every property is a dict name -> tensor with the leading shape (B,) for a surface
     variable and (B, C) for an atmospheric one, on the device of the two `Objects`."""
 
@@ -326,12 +308,9 @@ class ObjectSeparations:
     b: Objects
     nearest: NearestEvent                                 # of b
     max_km: Optional[float]
+    _owner = "a"
 
-    def _field(self, t: torch.Tensor) -> dict[str, torch.Tensor]:
-        return _fields.by_variable(self.a.layout, t)
-
-    @functools.cached_property
-    def _final(self) -> dict[str, torch.Tensor]:
+    def _finalise(self) -> dict[str, torch.Tensor]:
         return _finalise(self.table_table, self.hausdorff_table, self.a, self.b)
 
     @property
@@ -353,12 +332,8 @@ class ObjectSeparations:
                                    b=nearest.objects, nearest=nearest)
 
 
-def _final_property(name: str) -> property:
-    return property(lambda self: self._field(self._final[name]), doc=f"`{name}` of THE RULE, point 10; see the module's text.")
-
-
-for _name in ("distance_km", "nearest_b", "a_lat", "a_lon", "b_lat", "b_lon", "hausdorff_km"):
-    setattr(ObjectSeparations, _name, _final_property(_name))
+final_properties(ObjectSeparations, ("distance_km", "nearest_b", "a_lat", "a_lon", "b_lat", "b_lon", "hausdorff_km"),
+                 "of THE RULE, point 10; see the module's text.")
 
 
 # ---- public functions ------------------------------------------------------------------------------------------------------
@@ -398,21 +373,9 @@ def object_separations(a: Objects, b: Objects, max_km: Optional[float] = None) -
     for name, o in (("a", a), ("b", b)):
         if not isinstance(o, Objects):
             raise TypeError(f"object_separations: {name} must be an Objects (the result of aurora_amd.objects), got {type(o).__name__}")
-    if a.layout != b.layout:
-        raise ValueError(f"object_separations: a and b differ in layout (variable, first plane, shape): {a.layout} against {b.layout}")
-    sa, sb = tuple(a.labels_table.shape), tuple(b.labels_table.shape)
-    if sa[1] != sb[1]:
-        raise ValueError(f"object_separations: a and b differ in the number of thresholds: {sa[1]} against {sb[1]}")
-    if sa[2:] != sb[2:]:
-        raise ValueError(f"object_separations: a and b differ in grid: {sa[2]} x {sa[3]} against {sb[2]} x {sb[3]} points; regrid first")
-    da, db = a.labels_table.device, b.labels_table.device
-    if da != db:
-        raise ValueError(f"object_separations: a is on {da} and b on {db}; move both to the CPU (.cpu()) or label both on one GPU")
-    for c in ("lat", "lon"):
-        if not _same_values(getattr(a, c), getattr(b, c)):
-            raise ValueError(f"object_separations: a and b differ in {c} (same length, different values); regrid first")
+    check_pair("object_separations", a, b)
     n = nearest_event(b, max_km)
-    if da.type == "cpu":
+    if a.labels_table.device.type == "cpu":
         table, hausdorff = (torch.from_numpy(x) for x in _separations_host(
             a.labels_table.numpy(), n.key_table.numpy(), n.index_table.numpy(), a.count_table.numpy(), a.max_objects))
     else:

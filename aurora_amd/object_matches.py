@@ -42,11 +42,10 @@ THE RULE (both paths, aurora_amd/csrc/pairs_hash.h and the tests refer to this t
                       csi = n_b_matched / (n_b + n_a - n_a_matched), NaN where the denominator is 0; in an item that overflows
                       the matched counts are -1 and the three scores NaN
       distance_km     the great-circle distance between the two objects' `centroid_lat` / `centroid_lon` as `Objects`
-                      finalises them, by the haversine formula with the Earth radius of `diagnostics`.  Sine, arcsine and
-                      the square root are evaluated HERE from elementwise fp64 products, sums and quotients of tensors alone
-                      (a library sin or asin may round differently on the GPU than on the CPU, and torch's fp64 sqrt does), so
-                      this too has the same bits on either device; they agree with the correctly rounded functions to a few
-                      ulps.
+                      finalises them: `haversine_km` of aurora_amd/_sphere.py, whose sine, arcsine and square root are
+                      elementwise fp64 products, sums and quotients of tensors alone (a library sin or asin may round differently
+                      on the GPU than on the CPU, and torch's fp64 sqrt does), so this too has the same bits on either device;
+                      they agree with the correctly rounded functions to a few ulps.
 
 `Objects` on one GPU are matched by ONE aurora_hip_object_matches call (a bounded, lock-free hash aggregation over planes:
 aurora_amd/csrc/object_matches.hip) with nothing read back; the area units come from the table that `objects` uploaded.  `Objects`
@@ -57,15 +56,13 @@ on the CPU are matched in numpy: np.unique on la.astype(int64) << 32 | lb over t
 from __future__ import annotations
 
 import dataclasses
-import functools
-import math
 
 import numpy as np
 import torch
 
 from aurora_amd import _fields
-from aurora_amd.diagnostics import EARTH_RADIUS
-from aurora_amd.objects import _AREA, Objects, area_units
+from aurora_amd._sphere import haversine_km
+from aurora_amd.objects import _AREA, Objects, Result, area_units, check_pair, device_units, final_properties
 
 __all__ = ["object_matches", "ObjectMatches", "COLUMNS", "MAX_PAIRS"]
 
@@ -107,63 +104,6 @@ def _pairs_host(labels_a: np.ndarray, labels_b: np.ndarray, unit: np.ndarray, ma
 
 
 # ---- finalisation: the same torch code on either device ----------------------------------------------------------------
-def _sin(x: torch.Tensor) -> torch.Tensor:
-    """sin x for |x| <= pi / 2 (fp64): the Taylor polynomial to x^27 by Horner's rule in x^2 -- products and sums only, so the
-    same bits on every device; the first term left out is below 2e-23."""
-    x2 = x * x
-    s = torch.full_like(x, -1.0 / math.factorial(27))
-    sign = 1.0
-    for k in range(25, 0, -2):
-        s = s * x2 + sign / math.factorial(k)
-        sign = -sign
-    return s * x
-
-
-def _sqrt(x: torch.Tensor) -> torch.Tensor:
-    """sqrt x for x >= 0 (fp64, normal numbers or 0) to an ulp or two, from integer operations, products and sums alone:
-    `torch.sqrt` of an fp64 tensor is correctly rounded on the CPU and not on the GPU (measured on an MI355X: one value in 70
-    differs in the last bit).  The reciprocal root starts from the shifted bit pattern (off by at most 3.5 %), takes five Newton
-    steps r <- r (3/2 - x/2 r^2), which square the error each time, and one correction of x r with the residual."""
-    safe = torch.where(x > 0, x, torch.ones_like(x))
-    r = (0x5FE6EB50C7B537A9 - (safe.view(torch.int64) >> 1)).view(torch.float64)
-    half = 0.5 * safe
-    for _ in range(5):
-        r = r * (1.5 - half * (r * r))
-    root = safe * r
-    root = root + (0.5 * r) * (safe - root * root)
-    return torch.where(x > 0, root, torch.zeros_like(x))
-
-
-def _asin(s: torch.Tensor) -> torch.Tensor:
-    """asin s for 0 <= s <= 1 (fp64): the angle is halved twice, sin(y / 2) = s / sqrt(2 (1 + sqrt(1 - s^2))), which brings the
-    argument below sin(pi / 8) = 0.383; there the Maclaurin series to t^61 (the first term left out is below 1e-28); products,
-    sums, quotients of tensors and `_sqrt` only, so the same bits on every device."""
-    t = s
-    for _ in range(2):
-        t = t / _sqrt(2.0 * (1.0 + _sqrt((1.0 - t * t).clamp(min=0.0))))
-    t2 = t * t
-    coefficient = [1.0]                                    # of t^(2 k + 1): prod (2 i - 1) / (2 i) over i <= k, over 2 k + 1
-    for k in range(1, 31):
-        coefficient.append(coefficient[-1] * (2 * k - 1) / (2 * k))
-    coefficient = [c / (2 * k + 1) for k, c in enumerate(coefficient)]
-    y = torch.full_like(t, coefficient[-1])
-    for c in reversed(coefficient[:-1]):
-        y = y * t2 + c
-    return 4.0 * (y * t)
-
-
-def haversine_km(lat1: torch.Tensor, lon1: torch.Tensor, lat2: torch.Tensor, lon2: torch.Tensor) -> torch.Tensor:
-    """The great-circle distance of THE RULE, degrees in, kilometres out."""
-    rad = math.pi / 180.0
-    dlon = lon2 - lon1
-    dlon = dlon - 360.0 * torch.round(dlon * (1.0 / 360.0))   # into [-180, 180]; (a tensor divided by a number is multiplied by
-    #                                                            the number's reciprocal on the GPU and divided on the CPU)
-    cos = lambda x: 1.0 - 2.0 * _sin(0.5 * x) ** 2         # noqa: E731
-    sa, sb = _sin(0.5 * rad * (lat2 - lat1)), _sin(0.5 * rad * dlon)
-    h = sa * sa + cos(rad * lat1) * cos(rad * lat2) * (sb * sb)
-    return (2.0 * EARTH_RADIUS / 1000.0) * _asin(_sqrt(h.clamp(0.0, 1.0)))
-
-
 def _best(idx: torch.Tensor, other: torch.Tensor, units: torch.Tensor, live: torch.Tensor, own_area: torch.Tensor,
           own_count: torch.Tensor) -> tuple[torch.Tensor, torch.Tensor]:
     """Per object of one side (rows idx = k - 1 of its (..., M) table): the partner `other` of its pair with the most units,
@@ -200,7 +140,7 @@ def _finalise(pairs: torch.Tensor, count: torch.Tensor, a: Objects, b: Objects) 
 
 
 @dataclasses.dataclass(eq=False)
-class ObjectMatches:
+class ObjectMatches(Result):
     """Result of `object_matches`: every property is a dict name -> tensor with the leading shape (B,) for a surface variable
     and (B, C) for an atmospheric one, on the device of the two `Objects`."""
 
@@ -209,12 +149,9 @@ class ObjectMatches:
     a: Objects
     b: Objects
     max_pairs: int
+    _owner = "a"
 
-    def _field(self, t: torch.Tensor) -> dict[str, torch.Tensor]:
-        return _fields.by_variable(self.a.layout, t)
-
-    @functools.cached_property
-    def _final(self) -> dict[str, torch.Tensor]:
+    def _finalise(self) -> dict[str, torch.Tensor]:
         return _finalise(self.pairs_table, self.count_table, self.a, self.b)
 
     @property
@@ -262,21 +199,11 @@ class ObjectMatches:
                                    b=self.b.cpu())
 
 
-def _final_property(name: str) -> property:
-    return property(lambda self: self._field(self._final[name]), doc=f"`{name}` of THE RULE, point 6; see the module's text.")
-
-
-for _name in ("intersection", "iou", "fraction_of_a", "fraction_of_b", "distance_km", "best_b", "best_b_fraction", "best_a",
-              "best_a_fraction"):
-    setattr(ObjectMatches, _name, _final_property(_name))
+final_properties(ObjectMatches, ("intersection", "iou", "fraction_of_a", "fraction_of_b", "distance_km", "best_b", "best_b_fraction",
+                                 "best_a", "best_a_fraction"), "of THE RULE, point 6; see the module's text.")
 
 
 # ---- public function -----------------------------------------------------------------------------------------------------
-def _same_values(x: torch.Tensor, y: torch.Tensor) -> bool:
-    """Bit-equal coordinates; `objects` keeps one device copy per content, so on a device this is `x is y` and waits for nothing."""
-    return x is y or (x.shape == y.shape and torch.equal(x.view(torch.int64), y.view(torch.int64)))
-
-
 def object_matches(a: Objects, b: Objects, max_pairs: int = 4096) -> ObjectMatches:
     """The overlap pairs of the objects of `a` and `b` and what follows from them; see the module's text for THE RULE."""
     for name, o in (("a", a), ("b", b)):
@@ -284,20 +211,9 @@ def object_matches(a: Objects, b: Objects, max_pairs: int = 4096) -> ObjectMatch
             raise TypeError(f"object_matches: {name} must be an Objects (the result of aurora_amd.objects), got {type(o).__name__}")
     if isinstance(max_pairs, bool) or not isinstance(max_pairs, (int, np.integer)) or not 1 <= max_pairs <= MAX_PAIRS:
         raise ValueError(f"object_matches: max_pairs must be a whole number from 1 to {MAX_PAIRS}, got {max_pairs!r}")
-    if a.layout != b.layout:
-        raise ValueError(f"object_matches: a and b differ in layout (variable, first plane, shape): {a.layout} against {b.layout}")
-    sa, sb = tuple(a.labels_table.shape), tuple(b.labels_table.shape)
-    if sa[1] != sb[1]:
-        raise ValueError(f"object_matches: a and b differ in the number of thresholds: {sa[1]} against {sb[1]}")
-    if sa[2:] != sb[2:]:
-        raise ValueError(f"object_matches: a and b differ in grid: {sa[2]} x {sa[3]} against {sb[2]} x {sb[3]} points; regrid first")
-    da, db = a.labels_table.device, b.labels_table.device
-    if da != db:
-        raise ValueError(f"object_matches: a is on {da} and b on {db}; move both to the CPU (.cpu()) or label both on one GPU")
-    for c in ("lat", "lon"):
-        if not _same_values(getattr(a, c), getattr(b, c)):
-            raise ValueError(f"object_matches: a and b differ in {c} (same length, different values); regrid first")
+    check_pair("object_matches", a, b)
     max_pairs = int(max_pairs)
+    da = a.labels_table.device
     if da.type == "cpu":
         pairs, count = (torch.from_numpy(x) for x in _pairs_host(a.labels_table.numpy(), b.labels_table.numpy(),
                                                                  area_units(a.lat.numpy()), a.max_objects, b.max_objects, max_pairs))
@@ -305,6 +221,6 @@ def object_matches(a: Objects, b: Objects, max_pairs: int = 4096) -> ObjectMatch
         from aurora_amd.engine import lib
 
         lat = _fields._host(a.lat)                          # remembered per tensor: `objects` hands out one copy per grid
-        unit = _fields.tables.get(("object units", lat.tobytes()), da, lambda: area_units(lat), _ON_CAPTURE)
+        unit = device_units(lat, da, _ON_CAPTURE)
         pairs, count = lib.object_pairs(a.labels_table, b.labels_table, unit, a.max_objects, b.max_objects, max_pairs)
     return ObjectMatches(pairs, count, a, b, max_pairs)

@@ -22,8 +22,8 @@ THE RULE (both paths and the tests refer to this text)
  1. A point is an EVENT where its value v is finite and v >= t (`below=True`: v <= t).  NaN, +-Inf and non-events are background.
     Neighbours are grid neighbours: 4 (rows and columns) or 8 (diagonals too, `connectivity`).  There are none across the poles:
     rows 0 and H - 1 have none beyond them.  On a WRAPPING grid column W - 1 and column 0 are neighbours (diagonally too with 8).
-    `wrap=None` takes the grid as wrapping where `diagnostics` does: equally spaced longitudes that cover the full circle
-    (`_fields.check_longitudes`); `wrap=True` / `False` overrides that.
+    `wrap=None` takes the grid as wrapping where THE GRID RULE does (`_sphere.full_circle`); `wrap=True` / `False` overrides
+    that.
     An OBJECT is a maximal connected set of events of one plane and one threshold.
  2. Its FIRST POINT is its smallest row-major flat index i W + j.
  3. Objects are numbered 1, 2, ... in ascending order of their first points.
@@ -71,6 +71,7 @@ import numpy as np
 import torch
 
 from aurora_amd import _fields
+from aurora_amd._sphere import full_circle
 from aurora_amd.batch import Batch
 
 __all__ = ["objects", "Objects", "COLUMNS"]
@@ -88,13 +89,9 @@ def area_units(lat) -> np.ndarray:
     return np.rint(_fields.latitude_weights(lat) * 2.0 ** 32).astype(np.int64)
 
 
-def wraps(lon: np.ndarray) -> bool:
-    """Does the grid wrap in longitude, by the rule of `diagnostics`?"""
-    try:
-        _fields.check_longitudes(lon)
-        return True
-    except ValueError:
-        return False
+def device_units(lat: np.ndarray, device: torch.device, on_capture: str) -> torch.Tensor:
+    """`area_units(lat)` on `device`: one table per grid, which `objects` uploads and `object_matches` finds again."""
+    return _fields.tables.get(("object units", lat.tobytes()), device, lambda: area_units(lat), on_capture)
 
 
 # ---- the CPU path ----------------------------------------------------------------------------------------------------------
@@ -255,8 +252,55 @@ def _finalise(table: torch.Tensor, count: torch.Tensor, lat: torch.Tensor, lon: 
                                 torch.full((), -1, dtype=torch.int64, device=table.device))}
 
 
+class Result:
+    """What `Objects`, `ObjectMatches`, `NearestEvent` and `ObjectSeparations` share: a property is a dict name -> tensor, cut
+    from a table by the layout of the `Objects` that the field named `_owner` holds (None: the result itself); the finalised
+    ones are made once, by the class's `_finalise()`, and looked up by `final_properties`."""
+
+    _owner = None
+
+    def _field(self, t: torch.Tensor) -> dict[str, torch.Tensor]:
+        return _fields.by_variable((getattr(self, self._owner) if self._owner else self).layout, t)
+
+    @functools.cached_property
+    def _final(self) -> dict[str, torch.Tensor]:
+        return self._finalise()
+
+
+def _final_property(name: str, doc: str) -> property:
+    return property(lambda self: self._field(self._final[name]), doc=f"`{name}` {doc}")
+
+
+def final_properties(cls: type, names: tuple[str, ...], doc: str) -> None:
+    """Give `cls` one property per name of its `_final`; `doc`: what follows the name in the property's text."""
+    for name in names:
+        setattr(cls, name, _final_property(name, doc))
+
+
+def check_pair(fn: str, a: "Objects", b: "Objects") -> None:
+    """`a` and `b` have the same layout, number of thresholds, grid and device, and bit-equal coordinates."""
+    if a.layout != b.layout:
+        raise ValueError(f"{fn}: a and b differ in layout (variable, first plane, shape): {a.layout} against {b.layout}")
+    sa, sb = tuple(a.labels_table.shape), tuple(b.labels_table.shape)
+    if sa[1] != sb[1]:
+        raise ValueError(f"{fn}: a and b differ in the number of thresholds: {sa[1]} against {sb[1]}")
+    if sa[2:] != sb[2:]:
+        raise ValueError(f"{fn}: a and b differ in grid: {sa[2]} x {sa[3]} against {sb[2]} x {sb[3]} points; regrid first")
+    da, db = a.labels_table.device, b.labels_table.device
+    if da != db:
+        raise ValueError(f"{fn}: a is on {da} and b on {db}; move both to the CPU (.cpu()) or label both on one GPU")
+    for c in ("lat", "lon"):
+        if not _same_values(getattr(a, c), getattr(b, c)):
+            raise ValueError(f"{fn}: a and b differ in {c} (same length, different values); regrid first")
+
+
+def _same_values(x: torch.Tensor, y: torch.Tensor) -> bool:
+    """Bit-equal coordinates; `objects` keeps one device copy per content, so on a device this is `x is y` and waits for nothing."""
+    return x is y or (x.shape == y.shape and torch.equal(x.view(torch.int64), y.view(torch.int64)))
+
+
 @dataclasses.dataclass(eq=False)
-class Objects:
+class Objects(Result):
     """Result of `objects`: every property is a dict name -> tensor with the leading shape (B,) for a surface variable and
     (B, C) for an atmospheric one, on the device of the batch."""
 
@@ -272,11 +316,7 @@ class Objects:
     wrap: bool
     max_objects: int
 
-    def _field(self, t: torch.Tensor) -> dict[str, torch.Tensor]:
-        return _fields.by_variable(self.layout, t)
-
-    @functools.cached_property
-    def _final(self) -> dict[str, torch.Tensor]:
+    def _finalise(self) -> dict[str, torch.Tensor]:
         return _finalise(self.table_table, self.count_table, self.lat, self.lon, self.wrap, self.below)
 
     @property
@@ -312,13 +352,8 @@ class Objects:
         return dataclasses.replace(self, **moved)
 
 
-def _final_property(name: str) -> property:
-    return property(lambda self: self._field(self._final[name]), doc=f"`{name}` of every object; see the module's text.")
-
-
-for _name in ("points", "area", "centroid_row", "centroid_col", "centroid_lat", "centroid_lon", "peak", "peak_row", "peak_col",
-              "peak_lat", "peak_lon", "bbox"):
-    setattr(Objects, _name, _final_property(_name))
+final_properties(Objects, ("points", "area", "centroid_row", "centroid_col", "centroid_lat", "centroid_lon", "peak", "peak_row",
+                           "peak_col", "peak_lat", "peak_lon", "bbox"), "of every object; see the module's text.")
 
 
 # ---- public function -----------------------------------------------------------------------------------------------------
@@ -349,7 +384,7 @@ def objects(batch: Batch, thresholds: Mapping[str, object], below: bool = False,
     thr = _fields.threshold_table("objects", thresholds, layout)
     device = _fields.place("objects", [("batch", names, fields[0])], n_lat, n_lon, _fields.TAKES_TASK)
     lat, lon = _fields._host(batch.metadata.lat), _fields._host(batch.metadata.lon)
-    wrap = wraps(lon) if wrap is None else bool(wrap)
+    wrap = full_circle(lon) if wrap is None else bool(wrap)
     below, connectivity, max_objects = bool(below), int(connectivity), int(max_objects)
     if device == "cpu":
         labels, count, table = (torch.from_numpy(x) for x in _objects_host(
@@ -359,7 +394,7 @@ def objects(batch: Batch, thresholds: Mapping[str, object], below: bool = False,
         from aurora_amd.engine import lib
 
         thr_t = _fields.device_thresholds("objects", thr, device)
-        unit = _fields.tables.get(("object units", lat.tobytes()), device, lambda: area_units(lat), _ON_CAPTURE)
+        unit = device_units(lat, device, _ON_CAPTURE)
         lat_t = _fields.tables.get(("coordinate", lat.tobytes()), device, lambda: np.array(lat), _ON_CAPTURE)
         lon_t = _fields.tables.get(("coordinate", lon.tobytes()), device, lambda: np.array(lon), _ON_CAPTURE)
         labels, count, table = lib.object_labels(fields[0], thr_t, unit, below, connectivity, wrap, max_objects)

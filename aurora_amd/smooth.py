@@ -32,8 +32,7 @@ THE RULE (both paths follow it; include/aurora_hip.h has it for the device).
                 centre point itself is not finite, so the land of the wave model stays land.
     LIMITS      radius_km finite and > 0; min_valid in [0, 1]; at most 255 source rows per target row.
 
-Latitudes must be strictly monotonic, ascending or descending; longitudes equally spaced: a grid that covers the full circle
-wraps, any other is taken as regional (the rule of `diagnostics`).
+The grid is checked by THE GRID RULE of aurora_amd/_sphere.py, which also says when it wraps.
 
 Fields on one GPU are smoothed by aurora_hip_smooth (aurora_amd/csrc/smooth.hip): a prefix launch (a wavefront scans a row)
 and a gather launch (a lane reads the prefix tables at the ends of its windows); nothing is read back.  The workspace is
@@ -53,39 +52,17 @@ from typing import Optional, Sequence
 import numpy as np
 import torch
 
-from aurora_amd import _fields
+from aurora_amd import _fields, _sphere
 from aurora_amd._fields import _host
 from aurora_amd.batch import Batch
 
 __all__ = ["smooth", "disc_table", "EARTH_RADIUS_KM", "MAX_ROWS"]
 
-EARTH_RADIUS_KM = 6371.229
+EARTH_RADIUS_KM = _sphere.EARTH_RADIUS / 1000.0
 MAX_ROWS = 255
 
 
-# ---- the grid and the table -----------------------------------------------------------------------------------------------
-def _grid(lat: np.ndarray, lon: np.ndarray) -> tuple[float, bool]:
-    """(dlambda in radians, wrap) of a checked grid: the rule of `diagnostics._grid`, which a single row or column also passes."""
-    n_lat, n_lon = lat.shape[0], lon.shape[0]
-    if n_lat < 1 or n_lon < 1:
-        raise ValueError(f"smooth: the grid has {n_lat} latitudes and {n_lon} longitudes; at least 1 of each is needed")
-    if not np.all(np.isfinite(lat)) or lat.max() > 90 or lat.min() < -90:
-        raise ValueError("smooth: latitudes must be in the range [-90, 90]")
-    steps = np.diff(lat)
-    if not (np.all(steps > 0) or np.all(steps < 0)):
-        raise ValueError("smooth: the latitudes must be strictly monotonic")
-    if n_lon == 1:
-        return 0.0, False
-    try:
-        _fields.check_longitudes(lon)
-        wrap, step = True, 360.0 / n_lon
-    except ValueError:
-        wrap, step = False, (lon[-1] - lon[0]) / (n_lon - 1)
-    if not step > 0 or not np.all(np.abs(lon - lon[0] - np.arange(n_lon, dtype=np.float64) * step) <= 1e-6 * step):
-        raise ValueError("smooth: the longitudes must be equally spaced")
-    return float(np.deg2rad(step)), wrap
-
-
+# ---- the table ---------------------------------------------------------------------------------------------------------------
 def disc_table(lat, dlambda: float, n_lon: int, wrap: bool, radius_km: float):
     """THE RULE's membership as a table: (row_lo (H,), row_count (H,), half (H, max_rows) int32 -- -1 where a row has no column
     or past row_count -- and w (H,) fp64) for latitudes in degrees, the longitude step in radians and the radius."""
@@ -202,7 +179,8 @@ def smooth(batch: Batch, radius_km: float, *, only: Optional[Sequence[str]] = No
     md = batch.metadata
     lat, lon = _host(md.lat), _host(md.lon)
     n_lat, n_lon = lat.shape[0], lon.shape[0]
-    dlambda, wrap = _grid(lat, lon)
+    step, wrap = _sphere.regular_grid("smooth", lat, lon, least=1, in_range=True)      # (a single row or column passes)
+    dlambda = float(np.deg2rad(step))
     names, fields, layout = _fields.select_one("smooth", batch, "batch", only)
     if not names:
         raise ValueError("smooth: batch holds no surface or atmospheric variable to smooth")
