@@ -356,6 +356,16 @@ struct LinearOp {
   LinearOp& batched(int n, int64_t a, int64_t w, int64_t b, int64_t c) { batch = n; sa = a; sw = w; sbias = b; sc = c; return *this; }
 };
 
+// The grid columns a Perceiver launch runs over, and where their keys lie: key j of column (b, l) is context row
+// b * kv_bstride + j * kv_lstride + l; Lq queries and Lk keys per column.
+struct PerceiverCols {
+  int B;
+  int64_t cols, kv_bstride, kv_lstride;
+  int Lq, Lk, heads;
+  int64_t n_cols() const { return (int64_t)B * cols; }
+  int64_t n_rows() const { return n_cols() * Lq; }
+};
+
 // launches (skipped in a dry run)
 struct Launcher {
   Model& m;
@@ -390,6 +400,16 @@ struct Launcher {
     op.W = Wf;
     linear(op.f32_mode(1));
   }
+  // A linear whose activation operand is bounded only through a device word, in a layer of fp32 GEMM mode `mode`:
+  // pre-split weights -> the guarded pair above; mode 2 without them -> ONE guarded call, the device word picks the two- or
+  // the three-term kernel; a pinned mode (AURORA_F32_GEMM) or weights outside the two-term range -> NO guard: a mode-1
+  // launch that carries a guard is the three-term half of a guarded pair and runs only if the guard FAILS
+  // (include/aurora_hip.h).
+  void guarded_linear(LinearOp op, const void* Ws, int splits, int mode, const float* word, float limit) {
+    if (Ws) guarded_pair(op, Ws, splits, word, limit);
+    else if (mode == 2) linear(op.f32_mode(2).guarded_by(word, limit));
+    else linear(op.f32_mode(mode));
+  }
   // the qkv linear of a block with its result in head planes (bf16)
   void linear_planes(const void* A, int64_t lda, const void* Wt, int64_t ldw, const float* bias, void* C, int64_t plane_stride,
                      int heads, int64_t M, int N, int K) {
@@ -402,6 +422,57 @@ struct Launcher {
                  int dtype) {
     timed(m, stream, K_LAYERNORM, 0.0, [&] {
       return aurora_hip_layernorm(y, ldy, gain, shift, res, ldr, res_mod, out_f32, ldo, out_t, ldt, M, D, eps, dtype, stream);
+    });
+  }
+  // fp32 rows in; the residual as fp32 or (`res_is_split`) fp16 pairs; the result as fp32 (`out_f32`) and / or pairs (`out_split`)
+  void layernorm_split(const float* y, int64_t ldy, const float* gain, const float* shift, const void* res, int64_t ldr,
+                       int64_t res_mod, int res_is_split, float* out_f32, int64_t ldo, void* out_split, int64_t ld_split,
+                       int64_t M, int D, float eps) {
+    timed(m, stream, K_LAYERNORM, 0.0, [&] {
+      return aurora_hip_layernorm_split(y, ldy, gain, shift, res, ldr, res_mod, res_is_split, out_f32, ldo, out_split, ld_split, M, D,
+                                        eps, stream);
+    });
+  }
+  // ---- the Perceiver launches over the columns `g` (fp32).  `pair_word`: the rows leave as fp16 pairs iff *pair_word <
+  // pair_limit (null: fp32); `skip_word`: the launch retires at once iff *skip_word < skip_limit (null: never). ----
+  // attention on keys k | v (the `_unless` form where a skip word is given)
+  void perceiver_attention(const PerceiverCols& g, int head_dim, const float* q, int64_t q_stride, const float* kv, float* att,
+                           const float* pair_word, float pair_limit, const float* skip_word, float skip_limit) {
+    timed(m, stream, K_PERCEIVER_ATTENTION, 0.0, [&] {
+      if (skip_word)
+        return aurora_hip_perceiver_attention_unless(q, q_stride, kv, att, g.B, g.cols, g.kv_bstride, g.kv_lstride, g.Lq, g.Lk, g.heads,
+                                                     head_dim, AURORA_F32, pair_word, pair_limit, skip_word, skip_limit, stream);
+      return aurora_hip_perceiver_attention_ex(q, q_stride, kv, att, g.B, g.cols, g.kv_bstride, g.kv_lstride, g.Lq, g.Lk, g.heads,
+                                               head_dim, AURORA_F32, pair_word, pair_limit, stream);
+    });
+  }
+  // attention from score rows [v | scores] (`ld_vs` floats apart, scores from column `s_off`)
+  void perceiver_attention_scores(const PerceiverCols& g, int head_dim, const float* vs, int64_t ld_vs, int s_off, float* att,
+                                  const float* pair_word, float pair_limit, const float* skip_word, float skip_limit) {
+    timed(m, stream, K_PERCEIVER_ATTENTION, 0.0, [&] {
+      return aurora_hip_perceiver_attention_scores(vs, ld_vs, s_off, att, g.B, g.cols, g.kv_bstride, g.kv_lstride, g.Lq, g.Lk, g.heads,
+                                                   head_dim, pair_word, pair_limit, skip_word, skip_limit, stream);
+    });
+  }
+  // the softmax weights P and the value rows Vp (fp16 pairs) of the re-associated form, iff *word < limit: from keys
+  // (`q` given) or from score rows
+  void perceiver_probs(const PerceiverCols& g, int head_dim, const float* q, const float* kv, int64_t ld_vs, int s_off, float* P,
+                       void* Vp, const float* word, float limit) {
+    timed(m, stream, K_PERCEIVER_ATTENTION, 0.0, [&] {
+      if (q)
+        return aurora_hip_perceiver_probs(q, kv, P, Vp, g.B, g.cols, g.kv_bstride, g.kv_lstride, g.Lq, g.Lk, g.heads, head_dim, word,
+                                          limit, stream);
+      return aurora_hip_perceiver_probs_scores(kv, ld_vs, s_off, P, Vp, g.B, g.cols, g.kv_bstride, g.kv_lstride, g.Lq, g.Lk, g.heads,
+                                               head_dim, word, limit, stream);
+    });
+  }
+  // to_out (`W_pairs`, N x inner) of the value rows, combined with P, iff *word < limit
+  // (work: the three value rows of a column through to_out, and the Lq x Lk combinations per head)
+  void perceiver_out(const PerceiverCols& g, int head_dim, const void* Vp, const void* W_pairs, int inner, const float* P, float* out,
+                     int N, const float* word, float limit) {
+    timed(m, stream, K_PERCEIVER_OUT, 2.0 * (double)g.n_cols() * g.Lk * N * inner + 2.0 * (double)g.n_rows() * N * g.heads * g.Lk, [&] {
+      return aurora_hip_perceiver_out(Vp, W_pairs, inner, P, nullptr, out, N, g.n_cols(), g.Lq, g.Lk, g.heads, head_dim, N, word, limit,
+                                      stream);
     });
   }
 };

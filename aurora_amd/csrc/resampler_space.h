@@ -1,4 +1,5 @@
-// Workspace layout of one resampler layer (step.hip:resampler).  Plain values in, byte offsets out: nothing here knows
+// Workspace layout of one resampler layer (step.hip:resampler_layer takes it from the arena; the stages of `resampler` use
+// it in the order tests/resampler_space_check.cpp replays).  Plain values in, byte offsets out: nothing here knows
 // HIP or the model, so that a host program can replay the layout without a device (tests/resampler_space_check.cpp).
 #pragma once
 #include <algorithm>

@@ -13,41 +13,187 @@ namespace aurora {
 
 namespace {
 
-struct CtxGuard { const float* word; float a, c, limit_kv; bool pairs; };
+// Where the guard word of a resampler call comes from.  The context is as unbounded as the model inputs, so the linears that
+// read it, or averages of its value projection, pick their operand split on the device: |ctx| <= a * word + c.  `scan`: this
+// call measures max |ctx| into the word itself (a = 1, c = 0), else the caller measured the word upstream and derived the
+// bound.  `pairs`: the context arrives as fp16 pairs, and `limit_kv` is the limit the caller wrote them under.
+struct CtxGuard { float* word; float a, c, limit_kv; bool pairs, scan; };
 // The context linears of the encoder's level aggregation with the patch embedding folded in (model_weights.hip:compose_front):
 // one ComposedCtx per layer, read over the `levels` row blocks (`rows` each) of the unfolded input, level c with its own bias
 // row and -- `groups` > 1 -- its own weight.  `embed_l1`, `embed_bias_max`: of the embedding, for the bound the stages gave.
 struct ComposedFront { const ComposedCtx* layers; int levels, groups; int64_t rows; float embed_l1, embed_bias_max; };
 
-// The workspace of layer `i` of `rs` (resampler_space.h) for one call of `resampler`.
-LayerSpace layer_space(const Model& m, const Resampler& rs, size_t i, int B, int64_t cols, int64_t ctx_rows, int Lq, int Lk,
-                       int heads) {
+// One call of the PerceiverResampler (perceiver.py:212-233) for all grid columns `g` at once.  ctx: (ctx_rows, ctx_dim), key j of
+// column (b, l) at row b*kv_bstride + j*kv_lstride + l.  First layer: the latents `latents0` (and so the queries `q0`) are
+// shared by every column.  `out_pairs`: the last layer's result leaves as fp16 pairs where that layer can write them.
+// `front` (or null): the context is the unfolded input, read through the composed weights.
+struct ResamplerCall {
+  const Resampler* rs;
+  const float* ctx;
+  int64_t ctx_rows;
+  int ctx_dim;
+  const float *q0, *latents0;
+  PerceiverCols g;
+  float eps;
+  bool out_pairs;
+  const ComposedFront* front;
+  CtxGuard guard;
+};
+
+// What the stages of layer `i` of a call share: its workspace (resampler_space.h), the guard word and to_out's limit.
+struct ResamplerLayer {
+  const ResamplerCall& call;
+  size_t i;
+  const Resampler::Layer& ly;
+  LayerSpace sp;
+  const float* lat;             // the previous layer's result (null in the first)
+  const float* word;            // the call's guard word, and the limit to_out's activation operand is held to against it
+  float lim_out;
+  float *y, *lat1;              // the regions Y, L and S of the layer's workspace, and the arena mark behind Y
+  char* S;
+  size_t after_y;
+  float *kv, *qb, *att, *P, *o; // what lives in them, in launch order: set and explained in `resampler_layer`
+  void* Vp;
+  const float* q;               // the queries of this layer, `q_stride` rows apart from column to column
+  int64_t q_stride;
+};
+
+// The workspace of layer `i` of the call (taken from the arena: Y, L, S in this order) and the limit of its to_out guard.
+ResamplerLayer resampler_layer(Model& m, const ResamplerCall& c, size_t i, const float* lat) {
+  const Resampler& rs = *c.rs;
   const auto& ly = rs.layers[i];
   LayerShape sh{};
   sh.layer = i;
-  sh.dim = ly.dim; sh.inner = ly.inner; sh.hidden = ly.hidden; sh.head_dim = ly.head_dim; sh.heads = heads;
+  sh.dim = ly.dim; sh.inner = ly.inner; sh.hidden = ly.hidden; sh.head_dim = ly.head_dim; sh.heads = c.g.heads;
   sh.n_vs = rs.n_vs; sh.vs_lq = rs.vs_lq;
   sh.ln_k = ly.ln_k_w != nullptr; sh.to_out_s = ly.to_out_s != nullptr; sh.fc1_s = ly.fc1_s != nullptr; sh.fc2_s = ly.fc2_s != nullptr;
   sh.f16_mode = ly.f16_mode;
   sh.reassoc_out = m.reassoc_out;
-  sh.out_supported = aurora_hip_perceiver_out_supported(Lq, Lk, heads, ly.head_dim, ly.dim) != 0;
-  sh.B = B; sh.cols = cols; sh.ctx_rows = ctx_rows; sh.Lq = Lq; sh.Lk = Lk;
-  return layer_space(sh);
+  sh.out_supported = aurora_hip_perceiver_out_supported(c.g.Lq, c.g.Lk, c.g.heads, ly.head_dim, ly.dim) != 0;
+  sh.B = c.g.B; sh.cols = c.g.cols; sh.ctx_rows = c.ctx_rows; sh.Lq = c.g.Lq; sh.Lk = c.g.Lk;
+  const LayerSpace sp = layer_space(sh);
+  const CtxGuard& gd = c.guard;
+  // |att| <= max |v| <= (largest L1 row norm of W_v) * max |ctx|: the context's guard word, a tighter limit.
+  // (composed: |v| <= v_l1 max|input| + max|bias| of the COMPOSED value rows, never looser than the above: model.h)
+  const float lim_out = c.front ? composed_value_bound(ly.v_l1, c.front->embed_l1, c.front->embed_bias_max, c.front->layers[i].v_l1,
+                                                       c.front->layers[i].vb_max).word_limit()
+                                : (F16_SAFE / ly.v_l1 - gd.c) / gd.a;
+  ResamplerLayer r{c, i, ly, sp, lat, gd.word, lim_out};
+  // Y: the attention output (`att`; re-associated: the value rows `Vp` as fp16 pairs) until fc2 writes the layer's result there
+  r.y = (float*)m.arena.take(sp.unit);
+  r.after_y = m.arena.top;
+  r.Vp = r.y;
+  // L: LayerNorm 1's output, the MLP's input and residual
+  r.lat1 = (float*)m.arena.take(sp.unit);
+  // S: k | v (or v | scores) with the projected queries behind it; then to_out's result (k | v and q are dead) -- the softmax
+  // weights P of the re-associated form lie behind both --; then the MLP's hidden layer in row chunks (to_out's result is dead)
+  r.S = (char*)m.arena.take(sp.s_bytes);
+  r.kv = r.o = (float*)r.S;
+  r.qb = (float*)(r.S + round256(sp.kv_bytes));
+  r.P = (float*)(r.S + sp.p_off);
+  r.att = sp.att_in_y ? r.y : (float*)(r.S + sp.att_off);   // (wider than Y: in S, behind everything it coexists with)
+  // first layer: the queries are shared by every column
+  r.q = i > 0 ? r.qb : c.q0;
+  r.q_stride = i > 0 ? c.g.Lq : 0;
+  return r;
 }
 
-// The MLP half of a resampler layer: LayerNorm 1 of to_out's result `o` (+ residual) into `lat1`, fc1 -> fc2 in row chunks
-// through the scratch region `S` into `y`, LayerNorm 2 in place (or, `y_pairs`, to the fp16-pair layout).
-void resampler_mlp(Model& m, Launcher& L, const Resampler::Layer& ly, const LayerSpace& sp, const float* o, const float* res,
-                   int64_t res_mod, float* lat1, char* S, float* y, int64_t n_rows, float eps, bool y_pairs) {
+// Stage 1: k | v (or v | scores) of every context row.  The one place that knows the forms a context comes in.
+void project_context(Launcher& L, const ResamplerLayer& r) {
+  const ResamplerCall& c = r.call;
+  const CtxGuard& gd = c.guard;
+  const auto& ly = r.ly;
+  const int kv_ld = r.sp.kv_ld;
+  REQUIRE(!gd.pairs || ly.to_kv_s, "resampler: a pair-layout context needs pre-split to_kv weights");
+  if (c.front) {
+    // `ctx` is the unfolded, normalised input itself (fp32: the two-term kernel splits it, as the embedding did), so the
+    // guard word bounds this linear's activation operand directly; one strided-batch launch over the levels
+    const ComposedFront& f = *c.front;
+    const ComposedCtx& cc = f.layers[r.i];
+    REQUIRE(cc.N == kv_ld && f.levels * f.rows == c.ctx_rows, "resampler: composed context weights of another shape");
+    L.guarded_linear(LinearOp(c.ctx, c.ctx_dim, cc.w.f(), c.ctx_dim, cc.bias.f(), r.kv, kv_ld, f.rows, kv_ld, c.ctx_dim, AURORA_F32)
+                         .batched(f.levels, f.rows * c.ctx_dim, f.groups > 1 ? (int64_t)kv_ld * c.ctx_dim : 0, kv_ld, f.rows * kv_ld),
+                     cc.ws.p, 0, ly.f16_mode, r.word, F16_SAFE);
+  } else {
+    // |ctx| <= a * word + c < F16_SAFE  <=>  word < (F16_SAFE - c) / a; a context in pairs comes with its own limit
+    const bool scores = r.sp.scores;
+    L.guarded_linear(LinearOp(c.ctx, c.ctx_dim, scores ? c.rs->vs_w.f() : ly.to_kv, c.ctx_dim, nullptr, r.kv, kv_ld, c.ctx_rows, kv_ld,
+                              c.ctx_dim, AURORA_F32),
+                     scores ? c.rs->vs_ws.p : ly.to_kv_s, gd.pairs ? AURORA_F32_A_SPLIT : 0, ly.f16_mode, r.word,
+                     gd.pairs ? gd.limit_kv : (F16_SAFE - gd.c) / gd.a);
+  }
+}
+
+// Stage 2: LayerNorm over the K half, in place (perceiver.py:144-147)
+void norm_keys(Launcher& L, const ResamplerLayer& r) {
+  const int inner = r.ly.inner;
+  if (r.ly.ln_k_w)
+    L.layernorm(r.kv, 2 * inner, r.ly.ln_k_w, r.ly.ln_k_b, nullptr, 0, 0, r.kv, 2 * inner, nullptr, 0, r.call.ctx_rows, inner, 1e-5f,
+                AURORA_F32);
+}
+
+// Stage 3, layers after the first: the queries of the previous layer's result, with their LayerNorm
+void project_queries(Launcher& L, const ResamplerLayer& r) {
+  if (r.i == 0) return;
+  const auto& ly = r.ly;
+  const int inner = ly.inner;
+  const int64_t n_rows = r.call.g.n_rows();
+  L.linear(LinearOp(r.lat, ly.dim, ly.to_q, ly.dim, nullptr, r.qb, inner, n_rows, inner, ly.dim, AURORA_F32));
+  if (ly.ln_q_w) L.layernorm(r.qb, inner, ly.ln_q_w, ly.ln_q_b, nullptr, 0, 0, r.qb, inner, nullptr, 0, n_rows, inner, 1e-5f, AURORA_F32);
+}
+
+// Stage 4, plain: attention, then to_out.  With pre-split to_out weights the attention writes fp16 pairs iff the guard holds,
+// and to_out multiplies them without splitting anything.  `skip`: as the fall-back behind the re-associated pair -- attention
+// output in fp32, to_out on three bf16 terms, both retiring at once iff the guard HOLDS.
+void attend_plain(Launcher& L, const ResamplerLayer& r, bool skip) {
+  const PerceiverCols& g = r.call.g;
+  const auto& ly = r.ly;
+  const int inner = ly.inner;
+  const bool pairs = !skip && r.sp.att_pairs;
+  const float* pair_word = pairs ? r.word : nullptr;
+  const float pair_limit = skip ? 0.f : r.lim_out, skip_limit = skip ? r.lim_out : 0.f;
+  const float* skip_word = skip ? r.word : nullptr;
+  if (pairs) L.m.note_guard(r.word, r.lim_out);
+  if (r.sp.scores) L.perceiver_attention_scores(g, ly.head_dim, r.kv, r.sp.kv_ld, inner, r.att, pair_word, pair_limit, skip_word, skip_limit);
+  else L.perceiver_attention(g, ly.head_dim, r.q, r.q_stride, r.kv, r.att, pair_word, pair_limit, skip_word, skip_limit);
+  LinearOp to_out(r.att, inner, ly.to_out, inner, nullptr, r.o, ly.dim, g.n_rows(), ly.dim, inner, AURORA_F32);
+  if (skip) L.linear(to_out.f32_mode(1).guarded_by(r.word, r.lim_out));
+  else L.guarded_linear(to_out, ly.to_out_s, pairs ? AURORA_F32_A_SPLIT : 0, ly.f16_mode, r.word, r.lim_out);
+}
+
+// Stage 4, re-associated (perceiver_out.hip): the softmax weights and the value rows, to_out of the value rows combined in
+// registers -- and, for values outside fp16's range (the same word decides, on the device), the plain pair instead; inside
+// the range both of its launches retire at once.
+void attend_reassociated(Launcher& L, const ResamplerLayer& r) {
+  const PerceiverCols& g = r.call.g;
+  const auto& ly = r.ly;
+  const LayerSpace& sp = r.sp;
+  // (the launch that writes P reads k | v, and to_out's result lands on [0, unit) while P is read)
+  REQUIRE(sp.p_off >= sp.kv_bytes && sp.p_off >= sp.unit && sp.p_off + sp.p_bytes <= sp.s_bytes,
+          "resampler: the softmax weights overlap k | v or to_out's result in the scratch region");
+  for (int k = 0; k < 3; ++k) L.m.note_guard(r.word, r.lim_out);   // probs, perceiver_out and the plain attention behind them
+  L.perceiver_probs(g, ly.head_dim, sp.scores ? nullptr : r.q, r.kv, sp.kv_ld, ly.inner, r.P, r.Vp, r.word, r.lim_out);
+  L.perceiver_out(g, ly.head_dim, r.Vp, ly.to_out_s, ly.inner, r.P, r.o, ly.dim, r.word, r.lim_out);
+  attend_plain(L, r, true);
+}
+
+// Stage 5, the MLP half: LayerNorm 1 of to_out's result (+ residual: the previous layer's result, or the shared latents) into
+// `lat1`, fc1 -> fc2 in row chunks through the scratch region into `y`, LayerNorm 2 in place (or, `y_pairs`, to the fp16-pair
+// layout).
+void resampler_mlp(Launcher& L, const ResamplerLayer& r) {
+  const ResamplerCall& c = r.call;
+  const auto& ly = r.ly;
+  const LayerSpace& sp = r.sp;
   const int Dd = ly.dim;
-  if (sp.pairs)
-    timed(m, L.stream, K_LAYERNORM, 0.0, [&] {
-      return aurora_hip_layernorm_split(o, Dd, ly.ln1_w, ly.ln1_b, res, Dd, res_mod, 0, nullptr, 0, lat1, Dd, n_rows, Dd, eps, L.stream);
-    });
-  else L.layernorm(o, Dd, ly.ln1_w, ly.ln1_b, res, Dd, res_mod, lat1, Dd, nullptr, 0, n_rows, Dd, eps, AURORA_F32);
+  const int64_t n_rows = c.g.n_rows();
+  const float* res = r.i == 0 ? c.latents0 : r.lat;
+  const int64_t res_mod = r.i == 0 ? c.g.Lq : 0;
+  float *lat1 = r.lat1, *y = r.y;
+  if (sp.pairs) L.layernorm_split(r.o, Dd, ly.ln1_w, ly.ln1_b, res, Dd, res_mod, 0, nullptr, 0, lat1, Dd, n_rows, Dd, c.eps);
+  else L.layernorm(r.o, Dd, ly.ln1_w, ly.ln1_b, res, Dd, res_mod, lat1, Dd, nullptr, 0, n_rows, Dd, c.eps, AURORA_F32);
   // fc1 sees a LayerNorm output (|x| <= sqrt(D) * gain), fc2 its GELU: bounded whatever the inputs are.  Row chunks of the
   // pair fc1 -> fc2, so that the hidden layer of a chunk fits the scratch region (to_out's result is dead by now).
-  float* hid = (float*)S;
+  float* hid = (float*)r.S;
   const int64_t chunk_rows = sp.chunk_rows;
   REQUIRE(chunk_rows >= 1 && (size_t)chunk_rows * sp.hid_row <= sp.s_bytes, "resampler: scratch region too small for the MLP");
   const int all = 2 | AURORA_F32_A_SPLIT | AURORA_F32_W_SPLIT;
@@ -60,139 +206,27 @@ void resampler_mlp(Model& m, Launcher& L, const Resampler::Layer& ly, const Laye
   }
   // (`y_pairs`: the LAST layer's result leaves in the fp16-pair layout, in place -- a row is in registers before any of
   // it is written --, for a consumer that multiplies it without splitting anything: the decoder's output heads)
-  if (sp.pairs)
-    timed(m, L.stream, K_LAYERNORM, 0.0, [&] {
-      return aurora_hip_layernorm_split(y, Dd, ly.ln2_w, ly.ln2_b, lat1, Dd, 0, 1, y_pairs ? nullptr : y, Dd, y_pairs ? y : nullptr, Dd,
-                                        n_rows, Dd, eps, L.stream);
-    });
-  else L.layernorm(y, Dd, ly.ln2_w, ly.ln2_b, lat1, Dd, 0, y, Dd, nullptr, 0, n_rows, Dd, eps, AURORA_F32);
+  const bool y_pairs = c.out_pairs && sp.pairs && r.i + 1 == c.rs->layers.size();
+  if (sp.pairs) L.layernorm_split(y, Dd, ly.ln2_w, ly.ln2_b, lat1, Dd, 0, 1, y_pairs ? nullptr : y, Dd, y_pairs ? y : nullptr, Dd, n_rows, Dd, c.eps);
+  else L.layernorm(y, Dd, ly.ln2_w, ly.ln2_b, lat1, Dd, 0, y, Dd, nullptr, 0, n_rows, Dd, c.eps, AURORA_F32);
 }
 
-// PerceiverResampler (perceiver.py:212-233) for all grid columns at once.  ctx: key j of column (b, l) at row
-// b*kv_bstride + j*kv_lstride + l.  First layer: latents (and so q) are shared by every column.  Returns (B*cols*Lq, D).
-float* resampler(Model& m, Launcher& L, const Resampler& rs, const float* ctx, int64_t ctx_rows, int ctx_dim, const float* q0,
-                 const float* latents0, int B, int64_t cols, int64_t kv_bstride, int64_t kv_lstride, int Lq, int Lk, int heads,
-                 float eps, const CtxGuard* cg = nullptr, bool out_pairs = false, int own_word = 0, bool scan_ctx = true,
-                 const ComposedFront* front = nullptr) {
-  const int64_t n_cols = (int64_t)B * cols, n_rows = n_cols * Lq;
-  // The context is as unbounded as the model inputs, so the linears that read it, or averages of its value projection,
-  // pick their operand split on the device: from max |ctx|, measured here, or from the bound the caller derived from a
-  // word it measured upstream (`cg`).
-  const float* ctx_max = cg ? cg->word : m.ctx_max.f() + own_word;
-  const float g_a = cg ? cg->a : 1.0f, g_c = cg ? cg->c : 0.0f;
-  const bool ctx_pairs = cg && cg->pairs;
-  // (the words were cleared at the start of the step; of the two decoder Perceivers of a `separate_perceiver` model only the
-  // first scans their common context: `scan_ctx`)
-  if (!cg && scan_ctx)
-    timed(m, L.stream, K_ABSMAX, 0.0, [&] { return aurora_hip_absmax_fold(ctx, ctx_rows * ctx_dim, m.ctx_max.f() + own_word, L.stream); });
+// The layers of a resampler call as their stages.  Returns the last layer's result (B*cols*Lq, D).
+float* resampler(Model& m, Launcher& L, const ResamplerCall& c) {
+  // (the words were cleared at the start of the step)
+  if (c.guard.scan)
+    timed(m, L.stream, K_ABSMAX, 0.0, [&] { return aurora_hip_absmax_fold(c.ctx, c.ctx_rows * c.ctx_dim, c.guard.word, L.stream); });
   float* lat = nullptr;
-  for (size_t i = 0; i < rs.layers.size(); ++i) {
-    const auto& ly = rs.layers[i];
-    const int inner = ly.inner, Dd = ly.dim;
-    const LayerSpace sp = layer_space(m, rs, i, B, cols, ctx_rows, Lq, Lk, heads);
-    const bool scores = sp.scores;
-    const int kv_ld = sp.kv_ld;
-    float* y = (float*)m.arena.take(sp.unit);
-    const size_t after_y = m.arena.top;
-    float* lat1 = (float*)m.arena.take(sp.unit);
-    char* S = (char*)m.arena.take(sp.s_bytes);
-    float* kv = (float*)S;
-    // guarded linears with pre-split weights: the two-term launch runs iff the guard holds, the three-term one (fp32
-    // weights) iff it does not
-    auto guarded = [&](const float* A, int64_t lda, const float* Wf, const void* Ws, float* C_, int64_t ldc, int64_t M_, int N_,
-                       int K_, float limit, bool a_pairs = false) {
-      LinearOp op(A, lda, Wf, K_, nullptr, C_, ldc, M_, N_, K_, AURORA_F32);
-      if (Ws) {
-        L.guarded_pair(op, Ws, a_pairs ? AURORA_F32_A_SPLIT : 0, ctx_max, limit);
-      } else if (ly.f16_mode == 2) {   // one guarded call: the device word picks the two- or the three-term kernel
-        L.linear(op.f32_mode(2).guarded_by(ctx_max, limit));
-      } else {
-        // a pinned mode (AURORA_F32_GEMM) or weights outside the two-term range: NO guard -- a mode-1 launch that carries a
-        // guard is the three-term half of a guarded pair and runs only if the guard FAILS (include/aurora_hip.h)
-        L.linear(op.f32_mode(ly.f16_mode));
-      }
-    };
-    // |ctx| <= g_a * word + g_c < F16_SAFE  <=>  word < (F16_SAFE - g_c) / g_a; a context in pairs comes with its own limit
-    REQUIRE(!ctx_pairs || ly.to_kv_s, "resampler: a pair-layout context needs pre-split to_kv weights");
-    if (front) {
-      // `ctx` is the unfolded, normalised input itself (fp32: the two-term kernel splits it, as the embedding did), so the
-      // guard word bounds this linear's activation operand directly; one strided-batch launch over the levels
-      const ComposedCtx& cc = front->layers[i];
-      REQUIRE(cc.N == kv_ld && front->levels * front->rows == ctx_rows, "resampler: composed context weights of another shape");
-      LinearOp op = LinearOp(ctx, ctx_dim, cc.w.f(), ctx_dim, cc.bias.f(), kv, kv_ld, front->rows, kv_ld, ctx_dim, AURORA_F32)
-                        .batched(front->levels, front->rows * ctx_dim, front->groups > 1 ? (int64_t)kv_ld * ctx_dim : 0, kv_ld,
-                                 front->rows * kv_ld);
-      if (cc.ws.p) L.guarded_pair(op, cc.ws.p, 0, ctx_max, F16_SAFE);
-      else if (ly.f16_mode == 2) L.linear(op.f32_mode(2).guarded_by(ctx_max, F16_SAFE));
-      else L.linear(op.f32_mode(ly.f16_mode));   // (a pinned mode: no guard, as in `guarded`)
-    } else {
-      guarded(ctx, ctx_dim, scores ? rs.vs_w.f() : ly.to_kv, scores ? rs.vs_ws.p : ly.to_kv_s, kv, kv_ld, ctx_rows, kv_ld, ctx_dim,
-              ctx_pairs ? cg->limit_kv : (F16_SAFE - g_c) / g_a, ctx_pairs);
-    }
-    if (ly.ln_k_w)   // LayerNorm over the K half, in place (perceiver.py:144-147)
-      L.layernorm(kv, 2 * inner, ly.ln_k_w, ly.ln_k_b, nullptr, 0, 0, kv, 2 * inner, nullptr, 0, ctx_rows, inner, 1e-5f,
-                  AURORA_F32);
-    const float* q = q0;
-    int64_t q_stride = 0;
-    if (i > 0) {
-      float* qb = (float*)(S + round256(sp.kv_bytes));
-      L.linear(LinearOp(lat, Dd, ly.to_q, Dd, nullptr, qb, inner, n_rows, inner, Dd, AURORA_F32));
-      if (ly.ln_q_w) L.layernorm(qb, inner, ly.ln_q_w, ly.ln_q_b, nullptr, 0, 0, qb, inner, nullptr, 0, n_rows, inner, 1e-5f, AURORA_F32);
-      q = qb;
-      q_stride = Lq;
-    }
-    float* att = sp.att_in_y ? y : (float*)(S + sp.att_off);
-    // |att| <= max |v| <= (largest L1 row norm of W_v) * max |ctx|: same guard, tighter limit.  With pre-split to_out
-    // weights the attention writes fp16 pairs iff that guard holds, and to_out multiplies them without splitting anything.
-    // (composed: |v| <= v_l1 max|input| + max|bias| of the COMPOSED value rows, never looser than the above: model.h)
-    const float lim_out = front ? composed_value_bound(ly.v_l1, front->embed_l1, front->embed_bias_max, front->layers[i].v_l1,
-                                                       front->layers[i].vb_max).word_limit()
-                                : (F16_SAFE / ly.v_l1 - g_c) / g_a;
-    float* o = (float*)S;   // (k | v and q are dead)
-    if (sp.reassoc) {
-      // (the launch that writes P reads k | v, and to_out's result lands on [0, unit) while P is read)
-      REQUIRE(sp.p_off >= sp.kv_bytes && sp.p_off >= sp.unit && sp.p_off + sp.p_bytes <= sp.s_bytes,
-              "resampler: the softmax weights overlap k | v or to_out's result in the scratch region");
-      float* P = (float*)(S + sp.p_off);
-      void* Vp = y;
-      for (int k = 0; k < 3; ++k) m.note_guard(ctx_max, lim_out);   // probs, perceiver_out and the plain attention below
-      timed(m, L.stream, K_PERCEIVER_ATTENTION, 0.0, [&] {
-        if (scores)
-          return aurora_hip_perceiver_probs_scores(kv, kv_ld, inner, P, Vp, B, cols, kv_bstride, kv_lstride, Lq, Lk, heads, ly.head_dim,
-                                                   ctx_max, lim_out, L.stream);
-        return aurora_hip_perceiver_probs(q, kv, P, Vp, B, cols, kv_bstride, kv_lstride, Lq, Lk, heads, ly.head_dim, ctx_max, lim_out,
-                                          L.stream);
-      });
-      // (work: the three value rows of a column through to_out, and the Lq x Lk combinations per head)
-      timed(m, L.stream, K_PERCEIVER_OUT, 2.0 * (double)n_cols * Lk * Dd * inner + 2.0 * (double)n_rows * Dd * heads * Lk, [&] {
-        return aurora_hip_perceiver_out(Vp, ly.to_out_s, inner, P, nullptr, o, Dd, n_cols, Lq, Lk, heads, ly.head_dim, Dd, ctx_max,
-                                        lim_out, L.stream);
-      });
-      // Values outside fp16's range (the same word decides, on the device): the plain pair -- attention output in fp32, to_out
-      // on three bf16 terms -- runs instead; inside the range both launches retire at once.
-      timed(m, L.stream, K_PERCEIVER_ATTENTION, 0.0, [&] {
-        if (scores)
-          return aurora_hip_perceiver_attention_scores(kv, kv_ld, inner, att, B, cols, kv_bstride, kv_lstride, Lq, Lk, heads,
-                                                       ly.head_dim, nullptr, 0.f, ctx_max, lim_out, L.stream);
-        return aurora_hip_perceiver_attention_unless(q, q_stride, kv, att, B, cols, kv_bstride, kv_lstride, Lq, Lk, heads,
-                                                     ly.head_dim, AURORA_F32, nullptr, 0.f, ctx_max, lim_out, L.stream);
-      });
-      L.linear(LinearOp(att, inner, ly.to_out, inner, nullptr, o, Dd, n_rows, Dd, inner, AURORA_F32).f32_mode(1).guarded_by(ctx_max, lim_out));
-    } else {
-      if (sp.att_pairs) m.note_guard(ctx_max, lim_out);
-      timed(m, L.stream, K_PERCEIVER_ATTENTION, 0.0, [&] {
-        if (scores)
-          return aurora_hip_perceiver_attention_scores(kv, kv_ld, inner, att, B, cols, kv_bstride, kv_lstride, Lq, Lk, heads,
-                                                       ly.head_dim, sp.att_pairs ? ctx_max : nullptr, lim_out, nullptr, 0.f, L.stream);
-        return aurora_hip_perceiver_attention_ex(q, q_stride, kv, att, B, cols, kv_bstride, kv_lstride, Lq, Lk, heads, ly.head_dim,
-                                                 AURORA_F32, sp.att_pairs ? ctx_max : nullptr, lim_out, L.stream);
-      });
-      guarded(att, inner, ly.to_out, ly.to_out_s, o, Dd, n_rows, Dd, inner, lim_out, sp.att_pairs);
-    }
-    resampler_mlp(m, L, ly, sp, o, i == 0 ? latents0 : lat, i == 0 ? Lq : 0, lat1, S, y, n_rows, eps,
-                  out_pairs && sp.pairs && i + 1 == rs.layers.size());
-    m.arena.top = after_y;            // temporaries of this layer are dead (a previous layer's result stays below y)
-    lat = y;
+  for (size_t i = 0; i < c.rs->layers.size(); ++i) {
+    const ResamplerLayer r = resampler_layer(m, c, i, lat);
+    project_context(L, r);
+    norm_keys(L, r);
+    project_queries(L, r);
+    if (r.sp.reassoc) attend_reassociated(L, r);
+    else attend_plain(L, r, false);
+    resampler_mlp(L, r);
+    m.arena.top = r.after_y;   // temporaries of this layer are dead (a previous layer's result stays below y)
+    lat = r.y;
   }
   return lat;
 }
@@ -349,6 +383,16 @@ const float* encode_levels(Step& s) {
   float* word = m.ctx_max.f() + 1;   // max |normalised atmospheric input|, folded in by patchify when the chain is guarded
   patchify(s, pa, true, A_a, chain || composed ? word : nullptr);
   const int64_t R = (int64_t)B * s.Lp;
+  // the level aggregation: three latent queries per column over its C levels, level c of column (b, l) at row c R + b Lp + l
+  ResamplerCall call{};
+  call.rs = &m.enc_rs;
+  call.ctx_rows = (int64_t)C * R;
+  call.q0 = m.enc_q0.f();
+  call.latents0 = m.W("encoder.atmos_latents");
+  call.g.B = B; call.g.cols = s.Lp; call.g.kv_bstride = s.Lp; call.g.kv_lstride = R;
+  call.g.Lq = s.Cl - 1; call.g.Lk = C; call.g.heads = m.perceiver_heads;
+  call.eps = m.ln_eps;
+  call.out_pairs = false;
   // The embedding folded into the level aggregation's context linears: no embedding launch, no embeddings in the arena --
   // the resampler reads the unfolded input with the composed weights.  The guard is the same word, one link shorter: the
   // activation operand of the context linear is the input itself (limit F16_SAFE), and the attention output's bound comes
@@ -356,10 +400,12 @@ const float* encode_levels(Step& s) {
   if (composed) {
     REQUIRE(pa.composed.size() == m.enc_rs.layers.size(), "encoder: composed context weights for %zu of %zu layers",
             pa.composed.size(), m.enc_rs.layers.size());
-    const CtxGuard cgc{word, 1.0f, 0.0f, F16_SAFE, false};
     const ComposedFront front{pa.composed.data(), C, pa.groups, R, pa.l1, m.enc_bias_max};
-    return resampler(m, L, m.enc_rs, A_a, (int64_t)C * R, Kpad_a, m.enc_q0.f(), m.W("encoder.atmos_latents"), B, s.Lp, s.Lp, R,
-                     s.Cl - 1, C, m.perceiver_heads, m.ln_eps, &cgc, false, 0, true, &front);
+    call.ctx = A_a;
+    call.ctx_dim = Kpad_a;
+    call.front = &front;
+    call.guard = CtxGuard{word, 1.0f, 0.0f, F16_SAFE, false, false};
+    return resampler(m, L, call);
   }
   float* xa = (float*)m.arena.take((size_t)C * B * s.Lp * D * 4);
   // The patch embedding and the level aggregation's to_kv as one guarded chain: max |normalised input| is measured
@@ -369,19 +415,21 @@ const float* encode_levels(Step& s) {
   // three bf16 terms over fp32 buffers.  One word and one limit decide format and kernels together.
   // All C levels are ONE strided-batch launch: level c reads rows [c R, (c + 1) R) of the unfolded input, its own bias
   // (level embedding + patch bias) and -- level-conditioned models (levelcond.py:36-69) -- its own weight.
-  CtxGuard cg{};
   const int64_t sw = pa.groups > 1 ? (int64_t)D * Kpad_a : 0;
   const LinearOp embed = LinearOp(A_a, Kpad_a, pa.w.f(), Kpad_a, m.enc_bias.f(), xa, D, R, D, Kpad_a, AURORA_F32)
                              .batched(C, R * Kpad_a, sw, D, R * D);
+  call.ctx = xa;
+  call.ctx_dim = D;
+  call.front = nullptr;
   if (chain) {
     const float l1 = pa.l1, cb = m.enc_bias_max;
-    cg = CtxGuard{word, l1, cb, std::min(F16_SAFE, (F16_SAFE - cb) / l1), true};
-    L.guarded_pair(embed, pa.ws.p, AURORA_F32_C_SPLIT, cg.word, cg.limit_kv);
+    call.guard = CtxGuard{word, l1, cb, std::min(F16_SAFE, (F16_SAFE - cb) / l1), true, false};
+    L.guarded_pair(embed, pa.ws.p, AURORA_F32_C_SPLIT, call.guard.word, call.guard.limit_kv);
   } else {
     L.linear(embed);
+    call.guard = CtxGuard{m.ctx_max.f(), 1.0f, 0.0f, F16_SAFE, false, true};   // the resampler scans the embeddings itself
   }
-  return resampler(m, L, m.enc_rs, xa, (int64_t)C * R, D, m.enc_q0.f(), m.W("encoder.atmos_latents"), B, s.Lp, s.Lp, R, s.Cl - 1, C,
-                   m.perceiver_heads, m.ln_eps, chain ? &cg : nullptr);
+  return resampler(m, L, call);
 }
 
 // ---- assemble tokens + position / scale / time embeddings into the residual stream (and its bf16 shadow) ----
@@ -741,8 +789,22 @@ void decode_group(Step& s, const HeadGroup& hg, const Resampler& rs, const float
   const auto& last_ly = rs.layers.back();
   const bool last_pairs = last_ly.fc1_s && last_ly.fc2_s && last_ly.dim % 32 == 0;
   const bool two_term = hg.n_pad > 0 && last_pairs && out_bound < F16_SAFE;
-  float* lat = resampler(m, s.L, rs, ctx, (int64_t)B * (Cl - 1) * Lp, D2, q, m.dec_queries.f(), B, Lp, (int64_t)(Cl - 1) * Lp, Lp, C,
-                         Cl - 1, m.perceiver_heads, m.ln_eps, nullptr, two_term, 3, scan_ctx);
+  // one query per level and column over the Cl - 1 latent levels, latent level j of column (b, l) at row b (Cl - 1) Lp + j Lp + l
+  ResamplerCall call{};
+  call.rs = &rs;
+  call.ctx = ctx;
+  call.ctx_rows = (int64_t)B * (Cl - 1) * Lp;
+  call.ctx_dim = D2;
+  call.q0 = q;
+  call.latents0 = m.dec_queries.f();
+  call.g.B = B; call.g.cols = Lp; call.g.kv_bstride = (int64_t)(Cl - 1) * Lp; call.g.kv_lstride = Lp;
+  call.g.Lq = C; call.g.Lk = Cl - 1; call.g.heads = m.perceiver_heads;
+  call.eps = m.ln_eps;
+  call.out_pairs = two_term;
+  call.front = nullptr;
+  // (of the two decoder Perceivers of a `separate_perceiver` model only the first scans their common context: `scan_ctx`)
+  call.guard = CtxGuard{m.ctx_max.f() + 3, 1.0f, 0.0f, F16_SAFE, false, scan_ctx};
+  float* lat = resampler(m, s.L, call);
   const int n_a = two_term ? hg.n_pad : (int)hg.names.size() * s.PP, ld_a = round_up(n_a, 4);
   const float* hw = two_term ? (const float*)hg.ws.p : hg.w.f();
   const float* hb = two_term ? hg.bs.f() : hg.b.f();

@@ -1,4 +1,5 @@
-// Replays, on the host, the order in which `resampler` (aurora_amd/csrc/step.hip) uses the regions that `layer_space`
+// Replays, on the host, the order in which the stages of `resampler` (aurora_amd/csrc/step.hip: project_context, project_queries,
+// attend_reassociated / attend_plain, resampler_mlp, over the pointers `resampler_layer` sets) use the regions that `layer_space`
 // (aurora_amd/csrc/resampler_space.h) lays out, over every level count, both Perceivers' widths and every switch, and checks
 // launch by launch that nothing a launch writes overlaps what the same launch reads or what is still live, and that every
 // range lies inside its region.  Prints one line per violating tuple; exit status 1 if there was one.
@@ -78,7 +79,7 @@ int replay(const LayerShape& sh, const char* side) {
   std::vector<Range> kvq = qs;
   kvq.push_back(kv);
 
-  c.launch("1 to_kv", {}, {}, {kv});                       // (the key LayerNorm works in place)
+  c.launch("1 to_kv", {}, {}, {kv});                       // project_context (the key LayerNorm, norm_keys, works in place)
   if (sh.layer > 0) c.launch("2 to_q", {}, {kv}, {q});
   if (sp.reassoc) {
     c.launch("3 probs", kvq, {}, {P, Vp});

@@ -189,6 +189,22 @@ def test_bf16_backbone_at_three_levels_matches_oracle(monkeypatch):
         assert e16[k] <= 2 * b16[k] + 5e-4, (k, e16[k], b16[k])
 
 
+def test_second_perceiver_layers_match_oracle():
+    """`enc_depth=2, dec_depth=2`: the only way to a resampler layer behind the first -- its query projection from the previous
+    layer's result, keys instead of score rows, that result as the residual, no re-association.  The smallest shapes at which
+    every pre-split weight of a layer exists (tests/test_gpu_encoder_front.py: embed_dim 256, 4 x 8 patches, 4 levels), against
+    the oracle in fp64 on the same fp32 weights."""
+    from tests import test_gpu_encoder_front as front
+
+    case = dict(front.CASES["era5"], kwargs=dict(front._SMALL, enc_depth=2, dec_depth=2))
+    sd, batch, ref = front._case(case)
+    assert any(".level_agg.layers.1." in k for k in sd) and any(".level_decoder.layers.1." in k for k in sd)
+    model = aurora_amd.Aurora(**case["kwargs"])
+    model.load_state_dict(sd, strict=True)
+    out = _engine(model.to(DEV).eval(), batch)
+    _assert_matches_oracle(_oracle_errors(out, ref, "Aurora 16x32 4 levels, two layers per Perceiver"))
+
+
 def test_air_pollution_second_decoder_perceiver_at_four_levels(monkeypatch):
     """AuroraAirPollution decodes its pollution variables with a second Perceiver (`dec_rs_alt`) over the same context, through
     the same workspace: 4 of its 13 condition levels (each level has its own patch embedding and head, so a subset is a valid

@@ -4,6 +4,9 @@ rank of R latitude bands (one rank at a time here, its neighbours' halos not exc
 numbers are the handle's own host cost without a transport).
 
     python tools/host_time.py [R ...]       (default 8; run on the GPU box)
+    python tools/host_time.py small         (the launch-bound end: the 4-level small case of tools/step_trace.py, fp32, un-sharded,
+                                             5 windows of 20 steps -- a step there is ~250 launches of a few microseconds each, so
+                                             the handle's host walk is what the step takes)
 """
 import json
 import sys
@@ -43,6 +46,14 @@ def measure(step, n=10):
     return {"host_ms_per_step": host / n * 1e3, "step_ms": total / n * 1e3}
 
 
+if sys.argv[1:] == ["small"]:
+    from tools.step_trace import SMALL_CASES, build_small
+
+    with torch.inference_mode():
+        model, batch = build_small(*SMALL_CASES["small 4 levels compose=1 reassoc=1 scores=1"])
+    for _ in range(5):
+        print(json.dumps({"case": "small 4 levels", **measure(lambda: model.forward(batch), n=20)}), flush=True)
+    sys.exit(0)
 model = bench.build_model("cuda")
 batch = bench.synthetic_batch(model.config, 721, 1440, 1, "cuda").crop(model.patch_size)
 print(json.dumps({"ranks": 1, **measure(lambda: model.forward(batch))}), flush=True)
