@@ -28,7 +28,9 @@ arithmetic above puts a victim behind its writer, with 5 to 10 % mean-rel error 
 and the cases with the victim in front passed; the docstrings of the tests have the figures.
 
 Bounds: those of tests/test_gpu_production.py -- fp32 engine against the fp32 oracle mean-rel <= 1e-4 and max-rel <= 1e-3 per
-variable; a switched path against the plain one 0 < worst mean-rel < 2e-6 (the same function summed in another order; `0 <`
+variable, and per surface variable and (variable, level) in units of normalisation.scales against the oracle in fp64 on the same
+weights, within 4x of what the fp32 oracle deviates from it by (tests/normalised_error.py; one fp64 run per cached geometry, 6 to 7 s
+on 8 cores at these sizes); a switched path against the plain one 0 < worst mean-rel < 2e-6 (the same function summed in another order; `0 <`
 proves that the switch took another path); bf16 within twice the oracle's own autocast deviation + 5e-4.
 
 Both models run with one Swin block per stage, so that the oracle takes seconds; the Perceiver widths are the constructors'.
@@ -42,6 +44,7 @@ import torch
 import aurora_amd
 from aurora_amd import Batch, Metadata
 from tests import helpers
+from tests import normalised_error as ne
 from tests.test_gpu_production import DEV, LEVELS13, _engine, _inputs, _oracle, _seeded_model
 
 pytestmark = pytest.mark.gpu
@@ -52,6 +55,11 @@ LEVELS = {2: (500, 850), 3: (250, 500, 850), 4: (100, 250, 500, 850), 5: (50, 25
 assert all(set(v) <= set(LEVELS13) for v in LEVELS.values())
 
 _REFS = {}   # (class, H, W, levels, B, autocast) -> the oracle's result; read-only
+
+
+class _Ref32(dict):
+    """The fp32 oracle's fields of a geometry, with the fp64 oracle's and the per-entry deviation between the two."""
+    fp64, baseline, levels = None, None, None
 
 
 def _batch(cfg, H, W, levels, B=1, positive=()):
@@ -69,7 +77,13 @@ def _reference(model, batch, key, autocast=False):
     key = (*key, autocast)
     if key not in _REFS:
         sd = {k: v.detach().cpu() for k, v in model.state_dict().items()}
-        _REFS[key] = _oracle(model, sd, batch, autocast=autocast)
+        ref = _oracle(model, sd, batch, autocast=autocast)
+        if not autocast:
+            ref = _Ref32(ref)
+            ref.levels = batch.metadata.atmos_levels
+            ref.fp64 = _oracle(model, {k: v.double() for k, v in sd.items()}, batch, autocast=False)
+            ref.baseline = ne.per_level_errors(ref, ref.fp64, ref.levels)
+        _REFS[key] = ref
     return _REFS[key]
 
 
@@ -90,14 +104,15 @@ def _oracle_errors(out, ref, what):
     m = {k: helpers.rel_err(out[k], ref[k]) for k in ref}
     finite = all(bool(torch.isfinite(out[k]).all()) for k in ref)
     print(f"{what}: fp32 vs oracle worst mean-rel {max(e.values()):.3e} max-rel {max(m.values()):.3e}{'' if finite else ' NOT FINITE'}")
-    return what, e, m, finite
+    return what, e, m, finite, out, ref
 
 
 def _assert_matches_oracle(errors):
-    what, e, m, finite = errors
+    what, e, m, finite, out, ref = errors
     assert finite, what
     for k in e:
         assert e[k] <= 1e-4 and m[k] <= 1e-3, (what, k, e[k], m[k])
+    ne.check(what + " vs fp64 oracle", out, ref.fp64, ref.levels, ref.baseline)
 
 
 def _worst(a, b):
@@ -202,7 +217,11 @@ def test_second_perceiver_layers_match_oracle():
     model = aurora_amd.Aurora(**case["kwargs"])
     model.load_state_dict(sd, strict=True)
     out = _engine(model.to(DEV).eval(), batch)
-    _assert_matches_oracle(_oracle_errors(out, ref, "Aurora 16x32 4 levels, two layers per Perceiver"))
+    ref32 = _Ref32(_oracle(model, sd, batch, autocast=False))      # `ref` is the oracle in fp64 here: the fp32 run is the baseline
+    ref32.fp64, ref32.levels = ref, batch.metadata.atmos_levels
+    ref32.baseline = ne.per_level_errors(ref32, ref, ref32.levels)
+    what, e, m, finite, _, _ = _oracle_errors(out, ref, "Aurora 16x32 4 levels, two layers per Perceiver")
+    _assert_matches_oracle((what, e, m, finite, out, ref32))
 
 
 def test_air_pollution_second_decoder_perceiver_at_four_levels(monkeypatch):

@@ -6,6 +6,10 @@ mean|out - ref| / mean|ref| per variable, plus a max-norm guard):
   fp32 engine  vs fp64 reference goldens : <= 1e-4  (upstream accepts 1e-4 .. 5e-3 in fp64)
   bf16 engine (autocast=True) vs the same: <= 3e-2, and within 3x of what the reference's own
         CPU autocast path (the oracle with autocast=True) deviates from fp32.
+
+Beside them, per surface variable and per (atmospheric variable, level) in units of normalisation.scales
+(tests/normalised_error.py): fp32 within 4x of what the fp32 oracle deviates from the same golden by (or of one fp32 ulp of the
+entry's largest value), bf16 within 3x of the oracle's autocast deviation of that entry, never tighter than the fp32 bound.
 """
 import dataclasses
 from datetime import timedelta
@@ -18,6 +22,7 @@ import aurora_amd
 from aurora_amd import Batch, Metadata, normalisation, rollout
 from oracle import aurora_oracle as oracle
 from tests import helpers
+from tests import normalised_error as ne
 from tests.golden_cases import CASES
 
 pytestmark = pytest.mark.gpu
@@ -39,9 +44,10 @@ def build(name, autocast=False):
 def test_fp32_engine_matches_reference_golden(name):
     case, model, batch = build(name)
     gold = helpers.load_golden(name)
-    worst = {}
+    worst, preds = {}, []
     with torch.inference_mode():
         for s, pred in enumerate(rollout(model, batch, steps=case["steps"])):
+            preds.append(ne.fields({k: v.cpu() for k, v in pred.surf_vars.items()}, {k: v.cpu() for k, v in pred.atmos_vars.items()}))
             assert pred.metadata.rollout_step == s + 1
             assert pred.metadata.time == tuple(t + (s + 1) * model.timestep for t in batch.metadata.time)
             for kind, d in (("surf", pred.surf_vars), ("atmos", pred.atmos_vars)):
@@ -58,6 +64,12 @@ def test_fp32_engine_matches_reference_golden(name):
     print(name, "worst mean-rel", max(w[0] for w in worst.values()), "worst max-rel", max(w[1] for w in worst.values()))
     assert len(worst) == len(gold)
     bad = {k: w for k, w in worst.items() if w[0] > 1e-4 or w[1] > 1e-3}
+    assert not bad, bad
+    # per variable and level in normalised units, against the fp32 oracle's own deviation from the same golden
+    entries = [ne.per_level_errors(p, ne.golden(name)[s], case["levels"]) for s, p in enumerate(preds)]
+    ratios = [ne.report(f"{name} step {s}", e, ne.oracle_fp32_errors(name, s)) for s, e in enumerate(entries)]
+    print(name, "worst engine / oracle ratio over all steps", max(ratios))
+    bad = [f"step {s}: {line}" for s, e in enumerate(entries) for line in ne.failures(e, ne.fp32_bounds(name, s))]
     assert not bad, bad
 
 
@@ -107,6 +119,11 @@ def test_bf16_engine_within_autocast_tolerance(name):
     for k in errs:
         assert errs[k] < 1e-2, (k, errs[k])
         assert errs[k] < 3 * base[k] + 1e-3, (k, errs[k], base[k])
+    # per entry: 3x the oracle's autocast deviation of that entry; the entry's fp32 bound takes the place of the flat + 1e-3
+    ref = ne.golden(name)[0]
+    ne.check(f"{name} bf16", ne.fields({k: v.cpu() for k, v in pred.surf_vars.items()}, {k: v.cpu() for k, v in pred.atmos_vars.items()}),
+             ref, case["levels"], ne.per_level_errors(ne.fields(o_s, o_a), ref, case["levels"]), margin=3.0,
+             floor=ne.fp32_bounds(name, 0))
 
 
 def test_guard_words_say_which_fp32_path_a_step_took():
@@ -415,15 +432,20 @@ def test_a_subset_of_the_variables_runs_like_the_reference():
     sub = dataclasses.replace(batch, surf_vars={k: v for k, v in batch.surf_vars.items() if k != drop_s},
                               atmos_vars={k: v for k, v in batch.atmos_vars.items() if k != drop_a})
     sd = helpers.case_state_dict(model, torch.float32)
+    host = lambda d: {k: v.cpu() for k, v in d.items()}  # noqa: E731
     with torch.inference_mode():
         pred = model.forward(sub)
-        o_s, o_a, _ = oracle.forward(sd, model.config, {k: v.cpu() for k, v in sub.surf_vars.items()},
-                                     {k: v.cpu() for k, v in sub.static_vars.items()},
-                                     {k: v.cpu() for k, v in sub.atmos_vars.items()}, sub.metadata.lat.cpu(), sub.metadata.lon.cpu(),
-                                     sub.metadata.time, case["levels"], 0, normalisation.locations, normalisation.scales)
+        (o_s, o_a, _), (d_s, d_a, _) = (
+            oracle.forward(w, model.config, host(sub.surf_vars), host(sub.static_vars), host(sub.atmos_vars), sub.metadata.lat.cpu(),
+                           sub.metadata.lon.cpu(), sub.metadata.time, case["levels"], 0, normalisation.locations, normalisation.scales)
+            for w in (sd, {k: v.double() for k, v in sd.items()}))
     assert list(pred.surf_vars) == list(sub.surf_vars) and list(pred.atmos_vars) == list(sub.atmos_vars)
     for d, od in ((pred.surf_vars, o_s), (pred.atmos_vars, o_a)):
         for k, v in d.items():
             assert helpers.mean_rel_err(v.cpu(), od[k]) <= 1e-4, k
+    # per entry against the oracle in fp64 on the same fp32 weights and inputs; the baseline is the fp32 oracle above
+    ref = ne.fields(d_s, d_a)
+    ne.check("base_pad without msl and q", ne.fields(host(pred.surf_vars), host(pred.atmos_vars)), ref, case["levels"],
+             ne.per_level_errors(ne.fields(o_s, o_a), ref, case["levels"]))
     with pytest.raises(KeyError):
         model.forward(dataclasses.replace(batch, surf_vars={**batch.surf_vars, "sst": batch.surf_vars["2t"]}))

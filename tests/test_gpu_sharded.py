@@ -17,6 +17,7 @@ from aurora_amd.batch import BandBatch
 from aurora_amd.engine import native
 from aurora_amd.engine.engine import Engine, Shard
 from tests import helpers
+from tests import normalised_error as ne
 from tests.golden_cases import CASES
 
 pytestmark = pytest.mark.gpu
@@ -117,6 +118,10 @@ def stitch(bands):
     return cat("surf_vars"), cat("atmos_vars")
 
 
+def host_fields(surf, atmos):
+    return ne.fields({k: v.cpu() for k, v in surf.items()}, {k: v.cpu() for k, v in atmos.items()})
+
+
 def make(name, autocast, H=None, W=None):
     case = dict(CASES[name])
     if H:
@@ -140,7 +145,11 @@ def test_sharded_equals_unsharded(name, H, W, world, autocast):
     split-K form of a few-tile / long-K linear (aurora_hip_linear_ws) where the un-sharded step does not, and K-slices added
     in fp32 before the one rounding to bf16 differ from the un-split product by up to one bf16 ulp of that linear's output
     (tests/test_gpu_ops.py::test_linear_ws_split_k_equals_the_unsplit_product; the production-width geometry of
-    tests/test_gpu_production.py runs split-K end to end against the oracle)."""
+    tests/test_gpu_production.py runs split-K end to end against the oracle).
+
+    Per variable and level in normalised units (tests/normalised_error.py), stitched against un-sharded: fp32 within the case's
+    fp32 bound; bf16 within 3x of what the oracle's autocast run deviates from the golden by in that entry -- one more bf16
+    rounding of a linear's output is a perturbation of the size of those the autocast path makes everywhere."""
     model, batch = make(name, autocast, H, W)
     with torch.inference_mode():
         ref = model.forward(batch)
@@ -155,6 +164,9 @@ def test_sharded_equals_unsharded(name, H, W, world, autocast):
         assert helpers.rel_err(surf[k].cpu(), v.cpu()) < 2e-6, k
     for k, v in ref.atmos_vars.items():
         assert helpers.rel_err(atmos[k].cpu(), v.cpu()) < 2e-6, k
+    (ne.check_autocast if autocast else ne.check_fp32)(
+        f"{name} {H}x{W} {world} bands autocast={autocast}", host_fields(surf, atmos), name, 0,
+        ref=host_fields(ref.surf_vars, ref.atmos_vars))
     assert torch.equal(torch.cat([b.metadata.lat for b in bands]), ref.metadata.lat)
 
 
@@ -172,6 +184,7 @@ def test_sharded_variants_equal_unsharded(name):
         for k, v in want.items():
             a, b, flipped = helpers.nan_agreement(got[k].cpu(), v.cpu())
             assert flipped <= 1e-3 and helpers.rel_err(a, b) < 5e-6, (k, flipped)
+    ne.check_fp32(f"{name} 97x96 2 bands", host_fields(surf, atmos), name, 0, ref=host_fields(ref.surf_vars, ref.atmos_vars))
 
 
 def test_sharded_rollout_stays_distributed():
@@ -195,6 +208,8 @@ def test_sharded_rollout_stays_distributed():
     assert all(b.metadata.rollout_step == 2 for b in bands2)
     for k, v in ref.atmos_vars.items():
         assert helpers.rel_err(atmos[k].cpu(), v.cpu()) < 2e-6, k
+    ne.check_fp32("base_pad 192x96 2 bands, second step", host_fields(surf, atmos), "base_pad", 1,
+                  ref=host_fields(ref.surf_vars, ref.atmos_vars))
 
 
 def test_gather_rows_and_band_output_limit():
