@@ -12,9 +12,11 @@ where K u S bounds fp32 accumulation in ANY order, `operands` is what the mode l
 inputs: nothing, the reference sees the rounded values; native fp32 and three bf16 terms: 2 x 2^-24; two fp16 terms: 2 x 2^-22,
 and `subnormal` = 3e-8 (sum_k |w| + sum_k |a| / 64): fp16 remainders of activations below 0.25, and of the weights, scaled by
 64, below 0.25 / 64, are subnormal -- gemm_f32.hip).  E0 goes through the activation by its Lipschitz constant (GELU 1.13,
-SiLU 1.1); the kernel's own activation adds what csrc/common.h documents for the form it uses (gelu_sig of every bf16 kernel:
-2.6e-5 absolute; gelu_erf_fast of the operand-splitting fp32 kernels: 4e-7 absolute + 7.5e-8 |x|; erff of the native fp32 ones:
-4 ulp of erf, 2^-22 |x|; SiLU by expf and one division: 8 x 2^-24 |x|); the residual is added exactly but the sum is rounded
+SiLU 1.1); the kernel's own activation adds the bound of the form it uses, stated once in tests/activation_reference.py and
+pinned there against fp64 at exact inputs (gelu_sig of every bf16 kernel: 2.6e-5 absolute for x >= -9, plus 2.4e-12 |x| below,
+where the clamp leaves 2.305e-12 x -- no bf16 case of this table has a pre-activation below -9; gelu_erf_fast of the
+operand-splitting fp32 kernels: 4e-7 absolute + 7.5e-8 |x|; erff of the native fp32 ones: 4 ulp of erf, 2^-22 |x|; SiLU by expf
+and one division: 8 x 2^-24 |x|); the residual is added exactly but the sum is rounded
 once (2^-24); the store rounds once more (2^-24 |v| fp32; 2^-8 |v| bf16 -- eight significand bits, so half a spacing is up to
 2^-8 of a value at the bottom of its binade, which a correctly rounded CPU store reaches; the pair layout keeps 22 bits:
 2^-22 |v|).
@@ -32,6 +34,7 @@ from typing import NamedTuple, Optional
 
 import torch
 
+from tests import activation_reference as A
 from tests.attention_reference import to_planes
 from tests.perceiver_reference import hi_is_rounded_value, split_pairs, unsplit  # noqa: F401
 
@@ -305,11 +308,10 @@ def tolerance(c: Case, p: Problem, out, pre, S, store: str, three_term_twin: boo
     e0 = (C_ACC * c.K * U32 + operands) * S + sub
     if c.ksplit > 1:
         e0 = e0 + (c.ksplit - 1) * U32 * S          # the slices are added in fp32
-    x = pre.abs()
     if c.act == ACT_GELU:
-        act_err = 2.6e-5 if c.dtype == "bf16" else (2.0 ** -22 * x if native else 4e-7 + 7.5e-8 * x)
+        act_err = A.bound("gelu_sig" if c.dtype == "bf16" else "erff" if native else "gelu_erf_fast", pre)
     elif c.act == ACT_SILU:
-        act_err = 8 * U32 * x
+        act_err = A.bound("silu", pre)
     else:
         act_err = 0.0
     v = activate(pre, c.act).abs()
