@@ -22,7 +22,9 @@ over union, best partner, object POD / FAR / CSI, centroid displacement (aurora_
 for every grid point the great-circle distance to the nearest event and which point that is, from which `object_separations`
 takes what objects that do not touch need: minimum boundary separation, Hausdorff distance, "nearest observed object within
 300 km" (aurora_amd/distances.py), and `smooth` takes the mean of a field over a great-circle disc of R kilometres, the step
-before thresholding in object-based verification (aurora_amd/smooth.py); the reference has no counterpart.
+before thresholding in object-based verification (aurora_amd/smooth.py), and `extrema` finds where a field has its lows and
+highs -- the points that are the minimum or maximum of all points within R kilometres -- with the minimum / maximum filter itself
+(aurora_amd/extrema.py); the reference has no counterpart.
 """
 
 from aurora_amd.batch import Batch, Metadata
@@ -32,6 +34,7 @@ from aurora_amd.diagnostics import diagnostics
 from aurora_amd.distances import NearestEvent, ObjectSeparations, nearest_event, object_separations
 from aurora_amd.ensemble import EnsembleScores, ensemble_scores
 from aurora_amd.events import EventScores, event_scores
+from aurora_amd.extrema import Extrema, extrema
 from aurora_amd.field_quantiles import FieldQuantiles, field_quantiles
 from aurora_amd.fieldstats import FieldStats
 from aurora_amd.model.aurora import (
@@ -100,5 +103,7 @@ __all__ = [
     "field_quantiles",
     "FieldQuantiles",
     "smooth",
+    "extrema",
+    "Extrema",
     "Tracker",
 ]

@@ -1,4 +1,4 @@
-"""The sphere of the verification modules (`diagnostics`, `objects`, `object_matches`, `nearest_event`, `smooth`,
+"""The sphere of the verification modules (`diagnostics`, `objects`, `object_matches`, `nearest_event`, `smooth`, `extrema`,
 `conservative_regrid`, `spectra`): the Earth radius, THE GRID RULE -- when longitudes are equally spaced, when they cover the full
 circle, what latitudes may be -- on the host in numpy fp64, and the great-circle arithmetic in torch that gives the same bits on
 every device.  The rule is stated here and nowhere else; the modules' own texts point to it.

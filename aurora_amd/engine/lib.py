@@ -176,6 +176,9 @@ _SIGNATURES = {
     "aurora_hip_smooth_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int]),
     "aurora_hip_smooth": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int,
                                   ctypes.c_double, c_int, c_void_p, ctypes.c_size_t, c_void_p]),
+    "aurora_hip_extrema_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int]),
+    "aurora_hip_extrema": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                   c_void_p, c_int, c_int, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None
@@ -1459,6 +1462,52 @@ def smooth_planes(fields: list[torch.Tensor], rows: torch.Tensor, w: torch.Tenso
                 n_lat, n_lon, base, base + 4 * n_lat, base + 8 * n_lat, max_rows, _ptr(w), 1 if wrap else 0, float(min_valid),
                 1 if keep_mask else 0, _ptr(workspace), workspace.numel())
     return out
+
+
+# ---- local extrema over a great-circle disc (aurora_hip_extrema) --------------------------------------------------------------------
+EXTREMA_MAX_LON, EXTREMA_MAX_POINTS, EXTREMA_COLUMNS = 4096, 65536, 2
+
+
+def extrema_workspace_bytes(n_planes: int, n_lat: int, n_lon: int) -> int:
+    return int(load().aurora_hip_extrema_workspace_bytes(n_planes, n_lat, n_lon))
+
+
+def extrema_planes(fields: list[torch.Tensor], rows: torch.Tensor, wrap: bool, is_max: bool = False, max_points: int = 4096, *,
+                   out=None, workspace: Optional[torch.Tensor] = None) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The extreme point of the disc of every point of every plane of `fields` and the extrema of every plane
+    (include/aurora_hip.h), in ONE aurora_hip_extrema call (four launches): index (n_planes, n_lat, n_lon) int32, filtered, the
+    same shape in fp32, table (n_planes, max_points, 2) int64 and count (n_planes,) int32, on the device.
+
+    fields: a list of fp32 (..., n_lat, n_lon) tensors on one device with row-major contiguous planes (any leading strides, any
+    4-byte plane alignment); rows: the contiguous int32 vector [row_lo (n_lat) | row_count (n_lat) | half (n_lat x max_rows)]
+    of `aurora_amd.smooth.disc_table` on that device, the one `smooth_planes` takes.  out: (index, filtered, table, count) to
+    write into, contiguous and of those shapes (they must not overlap a field); workspace: a uint8 tensor of at least
+    `extrema_workspace_bytes` bytes -- both are allocated when not given (the workspace is NOT plane-sized: 16 bytes per row of
+    every plane).  The plane-pointer table is cached by address as in `scores_sums`.  The host does not wait for the device."""
+    assert fields, "extrema_planes: the list of fields is empty"
+    dev, (n_lat, n_lon) = fields[0].device, fields[0].shape[-2:]
+    assert 1 <= n_lon <= EXTREMA_MAX_LON, f"extrema_planes: n_lon must be in 1..{EXTREMA_MAX_LON}, got {n_lon}"
+    _operand("extrema_planes", "rows", rows, torch.int32, "int32 vector", dev=dev, anchor="the fields", dim=1)
+    max_rows = rows.numel() // n_lat - 2
+    assert rows.numel() == n_lat * (2 + max_rows) and 1 <= max_rows <= SMOOTH_MAX_ROWS, \
+        f"extrema_planes: rows holds {rows.numel()} entries, which is no table of 1..{SMOOTH_MAX_ROWS} source rows for {n_lat} latitudes"
+    max_points = int(max_points)
+    planes = _planes("extrema_planes", [("field", fields)], dev, "the first field", n_lat, n_lon)
+    n = planes.n
+    index, filtered, table, count = _outputs(
+        "extrema_planes", out, (((n, n_lat, n_lon), torch.int32, "index"), ((n, n_lat, n_lon), torch.float32, "filtered"),
+                                ((n, max(max_points, 0), EXTREMA_COLUMNS), torch.int64, "table"), ((n,), torch.int32, "count")),
+        dev, "the fields")
+    if n == 0:
+        return index, filtered, table, count
+    at = planes.upload()
+    workspace = _workspace("extrema_planes", workspace, dev, "the fields", extrema_workspace_bytes, n, n_lat, n_lon)
+    base = rows.data_ptr()
+    _launch(dev, "extrema", float(12 * n * n_lat * n_lon),   # bytes: the planes read once, the two maps written
+            "aurora_hip_extrema", at["field"], _ptr(index), _ptr(filtered), _ptr(table), _ptr(count), n, n_lat, n_lon, base,
+            base + 4 * n_lat, base + 8 * n_lat, max_rows, 1 if wrap else 0, 1 if is_max else 0, max_points, _ptr(workspace),
+            workspace.numel())
+    return index, filtered, table, count
 
 
 # ---- spatial quantiles of planes (aurora_hip_field_quantiles) ------------------------------------------------------------------

@@ -40,7 +40,7 @@ PLANE-SIZED -- 12 bytes per point of the planes in flight, plus one entry per ro
 that keep it under 128 MiB.  A plane's result does not depend on the chunking.  Fields on the CPU take the rule in numpy
 (`np.cumsum` for the prefixes, after a conversion to float32).
 
-Not offered: Gaussian or other kernels, minimum / maximum filters, latitude bands (`BandBatch`).
+Not offered: Gaussian or other kernels, latitude bands (`BandBatch`).  Minimum / maximum filters over the same disc: `extrema`.
 """
 
 from __future__ import annotations

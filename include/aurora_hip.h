@@ -1258,6 +1258,47 @@ int aurora_hip_smooth(const float* const* planes, float* out, int n_planes, int 
                       const int32_t* row_count, const int32_t* half, int max_rows, const double* w, int wrap,
                       double min_valid, int keep_mask, void* workspace, size_t workspace_size, void* stream);
 
+/* ---- local extrema over a great-circle disc on the device (aurora_amd.extrema: where a point is the minimum or maximum of
+ * all points within R km -- the candidates of cyclone detection and storm counts -- and the minimum / maximum filter itself;
+ * not in the reference) ---------------------------------------------------------------------------------------------------------
+ * Planes as above.  MEMBERSHIP is the table of aurora_hip_smooth (row_lo, row_count, half; max_rows <= 255) and nothing else:
+ * the columns j - n .. j + n of source row k, around the circle with wrap = 1 (the whole row once 2 n + 1 >= n_lon) and
+ * clipped into the row with wrap = 0; and the target point is always a member of its own disc: in its own row n counts as
+ * max(n, 0).  A point is VALID where it is finite; NaN and +-Inf are never members and never extrema.
+ * ORDER.  For the bits u of a valid value v, K = ~u where u has the sign bit, else u | 0x80000000 (ascending with v, -0 below
+ * +0; the key of aurora_hip_objects); with is_max = 1 the key is ~K.  The COMPOSITE of a valid point is the uint64
+ * (key << 32) | flat index, flat index = k n_lon + c.  The disc's extreme point is the MINIMUM composite over its valid
+ * members: the extreme value and, among equal values, the smallest flat index.  A valid point is an EXTREMUM where that
+ * minimum is its own composite.
+ *   index     n_planes x n_lat x n_lon int32: the flat index of the disc's extreme point, -1 where the disc holds no valid point
+ *   filtered  the same shape in fp32: the value at that index, bit for bit (NaN where index is -1)
+ *   count     n_planes int32: the number of extrema of the plane, also above max_points
+ *   table     n_planes x max_points x 2 int64: (flat index, K(v) widened -- K, not ~K, for either kind) of the extrema in
+ *             ascending flat index; zero from row min(count, max_points) on
+ * Everything is an integer or a copied fp32, so the outputs are repeatable bit for bit and depend on the plane's own values
+ * and the table alone: not on the other planes, not on n_planes, not on pointer alignment (planes are read 4 bytes at a time).
+ * Four launches on `stream`.  row extremes: a wavefront folds the composites of a row.  filter: a 256-thread workgroup owns 4
+ * adjacent target rows and all columns; for every source row of their union, in ascending order, it stages the composites in
+ * LDS and builds the doubling levels m[l + 1][c] = min(m[l][c], m[l][c + 2^l]) between two buffers (16 bytes per column of
+ * LDS: 64 KiB at n_lon = 4096, the limit), answering a target row at the step l = floor(log2(2 n + 1)) with two LDS reads per
+ * column (aurora_amd/csrc/extrema_window.h); a window that is the whole row reads the row's extreme instead.  scan: a
+ * workgroup per plane turns the rows' numbers of extrema into row bases and `count` and zeroes the table's tail.  number: a
+ * wavefront per row finds its extrema by ballot and writes their table rows.  No atomics; every trip count comes from the
+ * tables and every table value is clamped into its row or plane before use.
+ * `workspace`: aurora_hip_extrema_workspace_bytes(n_planes, n_lat, n_lon) = 16 n_planes n_lat device bytes -- per row of every
+ * plane the extreme composite (uint64), the number of extrema and the base (int32 each); NOT plane-sized; 8-byte aligned, no
+ * initialisation needed (0 for an argument out of range).  The outputs must not overlap an input plane, each other or the
+ * workspace.  n_lon <= 4096, n_lat n_lon <= 2^31 - 1, 1 <= max_rows <= 255, 1 <= max_points <= 65536, wrap and is_max 0 or 1;
+ * table 8-byte aligned, the other outputs and the disc table 4-byte aligned; workspace_size: the bytes at `workspace`, refused
+ * if too few.  Arguments are checked before anything is enqueued (AURORA_E_ARG and aurora_hip_last_error()).  n_planes = 0 is
+ * a no-op.  The inputs are not modified.  No host synchronisation, no allocation, no environment variable: capturable in a
+ * hipGraph. */
+size_t aurora_hip_extrema_workspace_bytes(int n_planes, int n_lat, int n_lon);
+int aurora_hip_extrema(const float* const* planes, int32_t* index, float* filtered, int64_t* table, int32_t* count,
+                       int n_planes, int n_lat, int n_lon, const int32_t* row_lo, const int32_t* row_count,
+                       const int32_t* half, int max_rows, int wrap, int is_max, int max_points, void* workspace,
+                       size_t workspace_size, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
