@@ -24,12 +24,14 @@ takes what objects that do not touch need: minimum boundary separation, Hausdorf
 300 km" (aurora_amd/distances.py), and `smooth` takes the mean of a field over a great-circle disc of R kilometres, the step
 before thresholding in object-based verification (aurora_amd/smooth.py), and `extrema` finds where a field has its lows and
 highs -- the points that are the minimum or maximum of all points within R kilometres -- with the minimum / maximum filter itself
-(aurora_amd/extrema.py); the reference has no counterpart.
+(aurora_amd/extrema.py), and `closed_contours` keeps those of them around which the field rises (falls) by at least delta on every
+path to the rim of a disc, the closed-contour criterion of storm counts (aurora_amd/contours.py); the reference has no counterpart.
 """
 
 from aurora_amd.batch import Batch, Metadata
 from aurora_amd.conditional import ConditionalScores, conditional_scores
 from aurora_amd.conservative import conservative_regrid
+from aurora_amd.contours import ClosedContours, closed_contours
 from aurora_amd.diagnostics import diagnostics
 from aurora_amd.distances import NearestEvent, ObjectSeparations, nearest_event, object_separations
 from aurora_amd.ensemble import EnsembleScores, ensemble_scores
@@ -105,5 +107,7 @@ __all__ = [
     "smooth",
     "extrema",
     "Extrema",
+    "closed_contours",
+    "ClosedContours",
     "Tracker",
 ]

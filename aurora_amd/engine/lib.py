@@ -179,6 +179,8 @@ _SIGNATURES = {
     "aurora_hip_extrema_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int]),
     "aurora_hip_extrema": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
                                    c_void_p, c_int, c_int, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p]),
+    "aurora_hip_closed_contours": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                           c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None
@@ -1508,6 +1510,62 @@ def extrema_planes(fields: list[torch.Tensor], rows: torch.Tensor, wrap: bool, i
             base + 4 * n_lat, base + 8 * n_lat, max_rows, 1 if wrap else 0, 1 if is_max else 0, max_points, _ptr(workspace),
             workspace.numel())
     return index, filtered, table, count
+
+
+# ---- the closed-contour test of local extrema (aurora_hip_closed_contours) ----------------------------------------------------------
+CONTOUR_MAX_DELTAS, CONTOUR_COLUMNS, CONTOUR_MAX_WORDS = 8, 2, 65
+CONTOUR_LDS_BUDGET = 156 * 1024    # bytes of the three bitmaps of a workgroup: kContourLdsBudget of aurora_amd/csrc/contour_fill.h
+
+
+def contour_lds_bytes(max_rows: int, max_words: int) -> int:
+    """The LDS of the three bitmaps for windows of up to `max_rows` source rows and `max_words` words a row."""
+    return 24 * (int(max_rows) + 2) * int(max_words)
+
+
+def closed_contours_planes(fields: list[torch.Tensor], table: torch.Tensor, count: torch.Tensor, deltas: torch.Tensor,
+                           rows: torch.Tensor, max_words: int, wrap: bool, is_max: bool = False, connectivity: int = 8, *,
+                           out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The closed-contour test (include/aurora_hip.h) of every candidate of every plane of `fields` for every delta, in ONE
+    aurora_hip_closed_contours call (one launch): (n_planes, T, max_points, 2) int32 on the device -- points, exits.
+
+    fields: a list of fp32 (..., n_lat, n_lon) tensors on one device with row-major contiguous planes (any leading strides, any
+    4-byte plane alignment); table: contiguous (n_planes, max_points, 2) int64 and count: contiguous (n_planes,) int32 on that
+    device, those of `extrema_planes`; deltas: contiguous (n_planes, T) fp32 on that device (NaN: none); rows: the contiguous
+    int32 vector [row_lo (n_lat) | row_count (n_lat) | half (n_lat x max_rows)] of `aurora_amd.smooth.disc_table` on that
+    device, the one `smooth_planes` takes; max_words: the most 64-column words a row of any candidate's window has
+    (`aurora_amd.contours.window_words`).  out: the tensor to write into, contiguous and of that shape (it must not overlap an
+    input), allocated when not given.  There is no workspace: the bitmaps live in LDS, `contour_lds_bytes(max_rows, max_words)`
+    bytes a workgroup, at most CONTOUR_LDS_BUDGET.  The plane-pointer table is cached by address as in `scores_sums`.  The host
+    does not wait for the device."""
+    assert fields, "closed_contours_planes: the list of fields is empty"
+    dev, (n_lat, n_lon) = fields[0].device, fields[0].shape[-2:]
+    assert 1 <= n_lon <= EXTREMA_MAX_LON, f"closed_contours_planes: n_lon must be in 1..{EXTREMA_MAX_LON}, got {n_lon}"
+    _operand("closed_contours_planes", "rows", rows, torch.int32, "int32 vector", dev=dev, anchor="the fields", dim=1)
+    max_rows = rows.numel() // n_lat - 2
+    assert rows.numel() == n_lat * (2 + max_rows) and 1 <= max_rows <= SMOOTH_MAX_ROWS, \
+        f"closed_contours_planes: rows holds {rows.numel()} entries, which is no table of 1..{SMOOTH_MAX_ROWS} source rows for {n_lat} latitudes"
+    _operand("closed_contours_planes", "deltas", deltas, torch.float32, "(n_planes, T) fp32 matrix", dev=dev, anchor="the fields", dim=2)
+    T = deltas.shape[1]
+    assert 1 <= T <= CONTOUR_MAX_DELTAS, f"closed_contours_planes: 1..{CONTOUR_MAX_DELTAS} deltas, got {T}"
+    planes = _planes("closed_contours_planes", [("field", fields)], dev, "the first field", n_lat, n_lon)
+    n = planes.n
+    assert n == deltas.shape[0], f"closed_contours_planes: {n} planes but deltas for {deltas.shape[0]}"
+    _operand("closed_contours_planes", "table", table, torch.int64, "(n_planes, max_points, 2) int64 tensor", dev=dev,
+             anchor="the fields", dim=3)
+    max_points = table.shape[1]
+    assert tuple(table.shape) == (n, max_points, EXTREMA_COLUMNS), \
+        f"closed_contours_planes: table has shape {tuple(table.shape)}, not ({n}, max_points, {EXTREMA_COLUMNS})"
+    _operand("closed_contours_planes", "count", count, torch.int32, "(n_planes,) int32 vector", dev=dev, anchor="the fields", shape=(n,))
+    (out,) = _outputs("closed_contours_planes", None if out is None else (out,),
+                      (((n, T, max_points, CONTOUR_COLUMNS), torch.int32, "out"),), dev, "the fields")
+    if n == 0:
+        return out
+    at = planes.upload()
+    base = rows.data_ptr()
+    _launch(dev, "closed_contours", 0.0, "aurora_hip_closed_contours", at["field"], _ptr(table), _ptr(count), _ptr(deltas), _ptr(out),
+            n, n_lat, n_lon, T, max_points, base, base + 4 * n_lat, base + 8 * n_lat, max_rows, int(max_words), 1 if wrap else 0,
+            1 if is_max else 0, int(connectivity))
+    return out
 
 
 # ---- spatial quantiles of planes (aurora_hip_field_quantiles) ------------------------------------------------------------------

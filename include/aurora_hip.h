@@ -1299,6 +1299,51 @@ int aurora_hip_extrema(const float* const* planes, int32_t* index, float* filter
                        const int32_t* half, int max_rows, int wrap, int is_max, int max_points, void* workspace,
                        size_t workspace_size, void* stream);
 
+/* ---- the closed-contour test of local extrema on the device (aurora_amd.closed_contours: does the field rise -- for maxima,
+ * fall -- by at least delta on every path from a candidate to the rim of a disc of R km; the DetectNodes criterion that turns
+ * the candidates of aurora_hip_extrema into storm counts; not in the reference) -------------------------------------------------
+ * Planes as above.  THE RULE, per plane and per delta:
+ *   CANDIDATE   row s < min(count, max_points) of the plane's extrema table: the flat index p0 = i0 n_lon + j0 (column 0 of the
+ *               row; column 1 is not read) and the value v0 = x[p0].
+ *   DOMAIN      the MEMBERS of the disc of row i0 around column j0 by the table of aurora_hip_smooth (row_lo, row_count, half;
+ *               max_rows <= 255) and nothing else: the columns j0 - n .. j0 + n of source row k, around the circle with
+ *               wrap = 1 (the whole row once 2 n + 1 >= n_lon), clipped into the row with wrap = 0; in row i0 n counts as
+ *               max(n, 0), so p0 is always a member.
+ *   PASSABLE    a point q is passable where x[q] is not finite, and where (double)x[q] - (double)v0 < (double)delta (is_max = 1:
+ *               (double)v0 - (double)x[q] < (double)delta): one fp64 subtraction and one comparison.  A non-finite point can
+ *               never hold a contour.
+ *   NEIGHBOURS  those of aurora_hip_objects: 4 (rows and columns) or 8 (diagonals too); none across rows 0 and n_lat - 1; with
+ *               wrap = 1 column n_lon - 1 joins column 0.
+ *   FILL        F is the smallest set that holds p0 and every passable member adjacent to a point of F.
+ *   EXIT        a point of F is an exit where a neighbour of it is passable and not a member, and, with wrap = 0 (a regional
+ *               grid: every edge is open), where it lies in row 0, row n_lat - 1, column 0 or column n_lon - 1.  With wrap = 1
+ *               the first and the last row are walls.
+ *   RESULT      out: n_planes x n_deltas x max_points x 2 int32: (points = |F|, exits = the number of exits); zero from row
+ *               min(count, max_points) on, and for a delta that is NaN (padding).  The contour is CLOSED where the row is live
+ *               and exits = 0.  Everything is an integer, so the output is repeatable bit for bit and depends on the plane's own
+ *               values and tables alone: not on the other planes, not on n_planes, not on pointer alignment (planes are read 4
+ *               bytes at a time).
+ * One launch on `stream`: a 256-thread workgroup per (plane, table row); one past min(count, max_points) stores its zero rows
+ * and exits.  The others lay out the candidate's WINDOW (aurora_amd/csrc/contour_fill.h) -- the source rows and columns of the
+ * disc and one ring of each around them -- as rows of 64-bit words in LDS and, per delta, build three bitmaps by ballot
+ * (passable member A, passable non-member X, reached R = the bit of p0), repeat R |= A & dilate(R) with a whole-run horizontal
+ * shortcut until a sweep changes nothing (at most |members| + 1 sweeps), and count points = popcount(R) and exits =
+ * popcount(R & (dilate(X) | edge)).  No atomics on global memory, no workspace, no workgroup waits for another; every trip count
+ * comes from the tables and every table value is clamped into its row or plane before use.
+ * LDS: the caller announces the largest window as max_rows source rows and max_words words of 64 local columns per row -- on a
+ * full circle n_lon columns where a disc row is the whole row, else 2 n + 3, on a regional grid at most n_lon + 2 -- and the
+ * three bitmaps take 24 (max_rows + 2) max_words bytes, at most 159744 (156 KiB of the CU's 160 KiB); more is refused here,
+ * before any launch.  A candidate whose window has more words than max_words is not filled (zero rows).
+ * n_lon <= 4096, n_lat n_lon <= 2^31 - 1, 1 <= n_deltas <= 8, 1 <= max_points <= 65536, 1 <= max_rows <= 255, 1 <= max_words <=
+ * 65, wrap and is_max 0 or 1, connectivity 4 or 8; table 8-byte aligned, the others 4-byte aligned; out must not overlap an
+ * input.  Arguments are checked before anything is enqueued (AURORA_E_ARG and aurora_hip_last_error()).  n_planes = 0 is a
+ * no-op.  The inputs are not modified.  No host synchronisation, no allocation, no environment variable: capturable in a
+ * hipGraph (after one eager call on the device, which raises the kernel's dynamic LDS limit). */
+int aurora_hip_closed_contours(const float* const* planes, const int64_t* table, const int32_t* count, const float* delta,
+                               int32_t* out, int n_planes, int n_lat, int n_lon, int n_deltas, int max_points,
+                               const int32_t* row_lo, const int32_t* row_count, const int32_t* half, int max_rows, int max_words,
+                               int wrap, int is_max, int connectivity, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
