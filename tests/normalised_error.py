@@ -21,7 +21,8 @@ Worst measured engine / oracle ratio per golden case (max error of an entry over
 at MARGIN), fp32 engine on an MI355X through `rollout`, every step: base_pad 1.50, small_b2 1.10, lora_all 2.00,
 stabilised_12h 1.37, patch10 1.33, air_pollution 1.77, wave 3.00.  bf16 against 3x the oracle's autocast deviation: 0.82
 (base_pad, small_b2), 0.77 (lora_all).  Stitched bands against the un-sharded step: fp32 at most 1.11 of the fp32 baseline,
-bf16 0.00 of the autocast baseline.  Through the C ABI: with torch tables the same figures as through `rollout` (lora_all 2.00,
+bf16 0.00 of the autocast baseline; at the production widths (tests/test_gpu_sharded_widths.py) fp32 bit for bit, bf16 at most
+0.19 of the 3x autocast bound.  Through the C ABI: with torch tables the same figures as through `rollout` (lora_all 2.00,
 air_pollution 1.77, wave 2.18); with the handle's own tables against the oracle on those tables at most 2.83 (wave), lora_all 1.39,
 air_pollution 1.66 -- against the GOLDEN those two reach 5.0 and 4.5, because their tables are other inputs (see below).
 Levels and production tests against the oracle in fp64: at most 2.08 (Aurora*Pretrained), 1.89 (AuroraHighRes), 3.38 (AuroraAirPollution 181 x 360, 4 levels), 2.26 of 5 on 361 x 720.

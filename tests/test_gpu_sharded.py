@@ -87,9 +87,9 @@ def make_engines(model, world):
     return engines
 
 
-def run_virtual_ranks(model, batch, world, engines=None):
+def run_virtual_ranks(model, batch, world, engines=None, outs=None):
     """One sharded step on `world` virtual ranks (threads); returns the per-rank BandBatches and the number of exchanges
-    posted.  `batch`: the full batch, or a list with every rank's BandBatch."""
+    posted.  `batch`: the full batch, or a list with every rank's BandBatch.  `outs`: every rank's `out` of `Engine.step`."""
     engines = engines or make_engines(model, world)
     hub = engines[0].native.transport.hub
     before = hub.exchanges
@@ -98,7 +98,7 @@ def run_virtual_ranks(model, batch, world, engines=None):
     def run(r):
         try:
             with torch.inference_mode():
-                out[r] = engines[r].step(batch if not isinstance(batch, list) else batch[r])
+                out[r] = engines[r].step(batch if not isinstance(batch, list) else batch[r], out=outs[r] if outs else None)
         except BaseException as e:  # noqa: BLE001
             errors.append(e)
 
@@ -144,8 +144,9 @@ def test_sharded_equals_unsharded(name, H, W, world, autocast):
     """2e-6 is the bound to keep, not bit equality: fp32 steps are bit-identical band by band, but a bf16 band may take the
     split-K form of a few-tile / long-K linear (aurora_hip_linear_ws) where the un-sharded step does not, and K-slices added
     in fp32 before the one rounding to bf16 differ from the un-split product by up to one bf16 ulp of that linear's output
-    (tests/test_gpu_ops.py::test_linear_ws_split_k_equals_the_unsplit_product; the production-width geometry of
-    tests/test_gpu_production.py runs split-K end to end against the oracle).
+    (tests/test_gpu_ops.py::test_linear_ws_split_k_equals_the_unsplit_product; tests/test_gpu_sharded_widths.py runs bands at
+    the production widths -- split-K and the fused linear + AdaLN kernel on band-local M -- against the un-sharded step and
+    the oracle, and asserts the fp32 bit equality claimed here; tests/test_gpu_production.py runs no band).
 
     Per variable and level in normalised units (tests/normalised_error.py), stitched against un-sharded: fp32 within the case's
     fp32 bound; bf16 within 3x of what the oracle's autocast run deviates from the golden by in that entry -- one more bf16
