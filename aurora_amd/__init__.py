@@ -25,7 +25,9 @@ takes what objects that do not touch need: minimum boundary separation, Hausdorf
 before thresholding in object-based verification (aurora_amd/smooth.py), and `extrema` finds where a field has its lows and
 highs -- the points that are the minimum or maximum of all points within R kilometres -- with the minimum / maximum filter itself
 (aurora_amd/extrema.py), and `closed_contours` keeps those of them around which the field rises (falls) by at least delta on every
-path to the rim of a disc, the closed-contour criterion of storm counts (aurora_amd/contours.py); the reference has no counterpart.
+path to the rim of a disc, the closed-contour criterion of storm counts (aurora_amd/contours.py), and `link_extrema` links the
+candidates of two steps by an all-pairs nearest search on the sphere, from which `tracks` numbers the storm tracks of a roll-out
+(aurora_amd/links.py); the reference has no counterpart.
 """
 
 from aurora_amd.batch import Batch, Metadata
@@ -39,6 +41,7 @@ from aurora_amd.events import EventScores, event_scores
 from aurora_amd.extrema import Extrema, extrema
 from aurora_amd.field_quantiles import FieldQuantiles, field_quantiles
 from aurora_amd.fieldstats import FieldStats
+from aurora_amd.links import Links, Tracks, link_extrema, tracks
 from aurora_amd.model.aurora import (
     Aurora,
     Aurora12hPretrained,
@@ -109,5 +112,9 @@ __all__ = [
     "Extrema",
     "closed_contours",
     "ClosedContours",
+    "link_extrema",
+    "Links",
+    "tracks",
+    "Tracks",
     "Tracker",
 ]

@@ -181,6 +181,8 @@ _SIGNATURES = {
                                    c_void_p, c_int, c_int, c_int, c_int, c_void_p, ctypes.c_size_t, c_void_p]),
     "aurora_hip_closed_contours": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                            c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p]),
+    "aurora_hip_link_extrema": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p,
+                                        c_int, c_int, c_int, ctypes.c_double, c_void_p, c_void_p, c_void_p]),
 }
 
 _lib: Optional[ctypes.CDLL] = None
@@ -1566,6 +1568,57 @@ def closed_contours_planes(fields: list[torch.Tensor], table: torch.Tensor, coun
             n, n_lat, n_lon, T, max_points, base, base + 4 * n_lat, base + 8 * n_lat, max_rows, int(max_words), 1 if wrap else 0,
             1 if is_max else 0, int(connectivity))
     return out
+
+
+# ---- linking the extrema of two steps (aurora_hip_link_extrema) ----------------------------------------------------------------------
+LINK_COLUMNS = 2
+
+
+def _overlaps(x: torch.Tensor, y: torch.Tensor) -> bool:
+    """Do two contiguous tensors share a byte?"""
+    x0, y0 = x.data_ptr(), y.data_ptr()
+    return x0 < y0 + y.numel() * y.element_size() and y0 < x0 + x.numel() * x.element_size()
+
+
+def link_extrema_tables(table_a: torch.Tensor, count_a: torch.Tensor, keep_a: Optional[torch.Tensor], table_b: torch.Tensor,
+                        count_b: torch.Tensor, keep_b: Optional[torch.Tensor], tables: torch.Tensor, n_lat: int, n_lon: int,
+                        wrap: bool, key_max: float = float("inf"), *, out=None) -> tuple[torch.Tensor, torch.Tensor]:
+    """The links (include/aurora_hip.h) between the rows of two stacks of extrema tables, in ONE aurora_hip_link_extrema call (one
+    launch): forward (n_planes, Ma, 2) int64 -- key bits, row of b -- and backward (n_planes, Mb, 2) int64 -- key bits, row of a
+    -- on the device; the bits of +inf and -1 for none.
+
+    table_a: contiguous (n_planes, Ma, 2) int64 and count_a: contiguous (n_planes,) int32 on the device, those of
+    `extrema_planes`; keep_a: None or a contiguous (n_planes, Ma) bool tensor; the same for b with its own Mb; tables: contiguous
+    (2 n_lat + n_lon,) fp64 on that device, those of `nearest_event_maps`; key_max: pairs beyond it are ignored (a HOST number,
+    passed by value).  out: (forward, backward) to write into, contiguous and of those shapes; they must not overlap each other
+    or an input.  No workspace.  The host does not wait for the device."""
+    fn = "link_extrema_tables"
+    _operand(fn, "table_a", table_a, torch.int64, "(n_planes, max_points, 2) int64 tensor", dim=3)
+    dev, n = table_a.device, table_a.shape[0]
+    _operand(fn, "table_b", table_b, torch.int64, "(n_planes, max_points, 2) int64 tensor", dev=dev, anchor="table_a", dim=3)
+    for what, t in (("table_a", table_a), ("table_b", table_b)):
+        assert t.shape[0] == n and t.shape[2] == EXTREMA_COLUMNS and 1 <= t.shape[1] <= EXTREMA_MAX_POINTS, \
+            f"{fn}: {what} has shape {tuple(t.shape)}, not ({n}, 1..{EXTREMA_MAX_POINTS}, {EXTREMA_COLUMNS})"
+    ma, mb = table_a.shape[1], table_b.shape[1]
+    _operand(fn, "count_a", count_a, torch.int32, "(n_planes,) int32 vector", dev=dev, anchor="table_a", shape=(n,))
+    _operand(fn, "count_b", count_b, torch.int32, "(n_planes,) int32 vector", dev=dev, anchor="table_a", shape=(n,))
+    for what, t, m in (("keep_a", keep_a, ma), ("keep_b", keep_b, mb)):
+        if t is not None:
+            _operand(fn, what, t, torch.bool, "(n_planes, max_points) bool matrix", dev=dev, anchor="table_a", shape=(n, m))
+    n_lat, n_lon = int(n_lat), int(n_lon)
+    assert 1 <= n_lon <= NEAREST_MAX_LON and n_lat >= 1, f"{fn}: n_lat must be at least 1 and n_lon in 1..{NEAREST_MAX_LON}, got {n_lat} and {n_lon}"
+    _operand(fn, "tables", tables, torch.float64, "(2 n_lat + n_lon,) fp64 vector", dev=dev, anchor="table_a", shape=(2 * n_lat + n_lon,))
+    forward, backward = _outputs(fn, out, (((n, ma, LINK_COLUMNS), torch.int64, "forward"), ((n, mb, LINK_COLUMNS), torch.int64, "backward")),
+                                 dev, "table_a")
+    if n == 0:
+        return forward, backward
+    inputs = [t for t in (table_a, count_a, keep_a, table_b, count_b, keep_b, tables) if t is not None]
+    assert not _overlaps(forward, backward) and not any(_overlaps(o, t) for o in (forward, backward) for t in inputs), \
+        f"{fn}: forward and backward must not overlap each other or an input"
+    _launch(dev, "link_extrema", 0.0, "aurora_hip_link_extrema", _ptr(table_a), _ptr(count_a), _ptr(keep_a), ma, _ptr(table_b),
+            _ptr(count_b), _ptr(keep_b), mb, n, _ptr(tables), n_lat, n_lon, 1 if wrap else 0, float(key_max), _ptr(forward),
+            _ptr(backward))
+    return forward, backward
 
 
 # ---- spatial quantiles of planes (aurora_hip_field_quantiles) ------------------------------------------------------------------

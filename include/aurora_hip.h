@@ -1344,6 +1344,36 @@ int aurora_hip_closed_contours(const float* const* planes, const int64_t* table,
                                const int32_t* row_lo, const int32_t* row_count, const int32_t* half, int max_rows, int max_words,
                                int wrap, int is_max, int connectivity, void* stream);
 
+/* ---- linking the extrema of two steps on the device (aurora_amd.link_extrema: for every candidate of step t the nearest
+ * candidate of step t + 1 within max_km and the reverse, the all-pairs search under the StitchNodes half of DetectNodes /
+ * StitchNodes; not in the reference) ---------------------------------------------------------------------------------------------
+ * table_a: n_planes x max_points_a x 2 int64 and count_a: n_planes int32 as written by aurora_hip_extrema (column 0, the flat
+ * index i n_lon + j, is read; column 1 is not); keep_a: n_planes x max_points_a bytes, non-zero = keep the row, or NULL = keep
+ * every row; the same for b, whose max_points may differ.  tables: 2 n_lat + n_lon fp64, the tables of aurora_hip_nearest_event:
+ * s[i] = sin(lat_i), c[i] = max(cos(lat_i), 0), cd[d] = cos(d dlon).  THE RULE (aurora_amd/links.py states it), per plane:
+ *   LIVE       row r of a side is live where r < min(count, max_points) (a count below 0 counts as 0) and its keep byte is set.
+ *   POINT      (i, j) = divmod(flat index, n_lon); the flat index is clamped into 0 .. n_lat n_lon - 1 before it addresses a table.
+ *   KEY        0 exactly for two rows with the same flat index; otherwise 1 - (s_i s_k + (c_i c_k) cd[gap]) with gap = |j - j'|,
+ *              with wrap = 1 min(gap, n_lon - gap): every fp64 operation rounded on its own, never a fused multiply-add, negative
+ *              results 0 -- the key of aurora_hip_nearest_event, symmetric in its two points bit for bit.
+ *   SEARCH     forward[p] = the live row q of b with the smallest (key, q) among keys <= key_max; backward[q] = the live row p of
+ *              a with the smallest (key, p).
+ *   RESULT     forward: n_planes x max_points_a x 2 int64 and backward: n_planes x max_points_b x 2 int64 -- the bits of the fp64
+ *              key, the partner's row; the bits of +inf and -1 for a row that is not live or has no partner in reach.  Every
+ *              row of both is written.  The result is repeatable bit for bit and depends on the plane's own tables alone.
+ * One launch on `stream`: a 256-thread workgroup per (chunk of 256 rows, plane, direction); a thread owns one row and scans the
+ * other side, staged through LDS in tiles of 1024 gathered rows, with cd in LDS (8 n_lon + 24576 bytes in all); the scan covers
+ * min(count, max_points) rows of the other side, and a workgroup past the rows of its own side stores "none" and exits.  No
+ * atomics, no workspace, no reduction across threads, plain vector stores.
+ * n_lon <= 4096, n_lat n_lon <= 2^31 - 1, 1 <= max_points <= 65536, wrap 0 or 1, key_max >= 0 (+inf: no limit; a HOST number);
+ * tables and outputs 8-byte aligned, counts 4-byte aligned; forward and backward must not overlap each other or an input.
+ * Arguments are checked before anything is enqueued (AURORA_E_ARG and aurora_hip_last_error()).  n_planes = 0 is a no-op.  The
+ * inputs are not modified.  No host synchronisation, no allocation, no environment variable: capturable in a hipGraph. */
+int aurora_hip_link_extrema(const int64_t* table_a, const int32_t* count_a, const uint8_t* keep_a, int max_points_a,
+                            const int64_t* table_b, const int32_t* count_b, const uint8_t* keep_b, int max_points_b,
+                            int n_planes, const double* tables, int n_lat, int n_lon, int wrap, double key_max,
+                            int64_t* forward, int64_t* backward, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
