@@ -27,7 +27,9 @@ highs -- the points that are the minimum or maximum of all points within R kilom
 (aurora_amd/extrema.py), and `closed_contours` keeps those of them around which the field rises (falls) by at least delta on every
 path to the rim of a disc, the closed-contour criterion of storm counts (aurora_amd/contours.py), and `link_extrema` links the
 candidates of two steps by an all-pairs nearest search on the sphere, from which `tracks` numbers the storm tracks of a roll-out
-(aurora_amd/links.py); the reference has no counterpart.
+(aurora_amd/links.py), and `sphere_spectra` gives the power spectra by total wavenumber -- the spherical-harmonic analysis of
+every plane -- and the kinetic-energy spectrum from vorticity and divergence (aurora_amd/sphere_spectra.py); the reference has
+no counterpart.
 """
 
 from aurora_amd.batch import Batch, Metadata
@@ -61,6 +63,7 @@ from aurora_amd.rollout import rollout, write_rollout
 from aurora_amd.scores import Scores, scores
 from aurora_amd.smooth import smooth
 from aurora_amd.spectra import Spectra, spectra
+from aurora_amd.sphere_spectra import SphereSpectra, sphere_spectra
 from aurora_amd.tracker import Tracker
 
 __all__ = [
@@ -84,6 +87,8 @@ __all__ = [
     "EnsembleQuantiles",
     "spectra",
     "Spectra",
+    "sphere_spectra",
+    "SphereSpectra",
     "event_scores",
     "EventScores",
     "probability_scores",

@@ -33,7 +33,8 @@ Fields on one GPU are formed by ONE aurora_hip_diagnostics call: one launch for 
 once for vorticity, divergence and speed) and one for the columns; nothing is read back and no temporary of plane size
 exists beside the outputs.  Fields on the CPU take the same formulas in numpy (after a conversion to float32).
 
-Not offered: latitude bands (`BandBatch`), humidity or thermodynamic quantities, spherical-harmonic derivatives.
+Not offered: latitude bands (`BandBatch`), humidity or thermodynamic quantities, spherical-harmonic derivatives
+(`sphere_spectra` has the analysis half of the transform: spectra, no synthesis).
 """
 
 from __future__ import annotations

@@ -142,6 +142,9 @@ _SIGNATURES = {
     "aurora_hip_spectra_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "aurora_hip_spectra": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                    c_void_p, ctypes.c_size_t, c_void_p]),
+    "aurora_hip_sphere_spectra_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "aurora_hip_sphere_spectra": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                          c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
     "aurora_hip_event_scores_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "aurora_hip_event_scores": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
                                         c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
@@ -1150,6 +1153,54 @@ def spectra_power(pred: list[torch.Tensor], truth: Optional[list[torch.Tensor]],
             "aurora_hip_spectra", at["prediction"], at["truth"], n, n_lat, n_lon, n_bands, _ptr(band_w), _ptr(twiddle),
             _ptr(power), _ptr(rows), _ptr(workspace), nbytes)
     return power, rows
+
+
+# ---- spherical-harmonic power spectra (aurora_hip_sphere_spectra) -----------------------------------------------------------
+SPHERE_TABLE_CAP = 1 << 30
+
+
+def sphere_spectra_workspace_bytes(n_planes: int, n_lat: int, n_lon: int, lmax: int, has_truth: bool) -> int:
+    return int(load().aurora_hip_sphere_spectra_workspace_bytes(n_planes, n_lat, n_lon, lmax, 1 if has_truth else 0))
+
+
+def sphere_spectra_power(pred: list[torch.Tensor], truth: Optional[list[torch.Tensor]], table: torch.Tensor, lmax: int,
+                         pole_rows: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """Power spectra by total wavenumber (include/aurora_hip.h) of every plane of `pred` (and of the same plane of `truth` and
+    of pred - truth, unless `truth` is None), in ONE aurora_hip_sphere_spectra call: an (n_planes, 1 or 3, lmax + 1) fp64
+    tensor, the (n_planes,) bool validity and the (n_planes,) int32 counts of dropped pole rows, on the device.
+
+    pred / truth: lists of fp32 (..., n_lat, n_lon) tensors on one device with row-major contiguous planes (any leading
+    strides, any 4-byte plane alignment), the same leading shapes in each list; table: the packed analysis table,
+    ((lmax + 1)(lmax + 2) / 2, n_lat) fp64 on that device; pole_rows: bit 0 -- row 0 is a pole, bit 1 -- the last row is one.
+    The plane-pointer table is cached by address as in `scores_sums`, the twiddle table per n_lon; the only temporary is the
+    workspace (`sphere_spectra_workspace_bytes`: 16 (lmax + 1) n_lat bytes per plane and input, plus the partial sums).  The
+    host does not wait for the device."""
+    lmax = int(lmax)
+    assert lmax >= 0, f"sphere_spectra_power: lmax must be at least 0, got {lmax}"
+    _operand("sphere_spectra_power", "table", table, torch.float64, "((lmax + 1)(lmax + 2) / 2, n_lat) fp64 matrix", dim=2)
+    dev, (n_rows, n_lat) = table.device, table.shape
+    assert n_rows == (lmax + 1) * (lmax + 2) // 2, \
+        f"sphere_spectra_power: the table has {n_rows} rows, lmax = {lmax} needs {(lmax + 1) * (lmax + 2) // 2}"
+    n_lon = pred[0].shape[-1] if pred else 2
+    assert 2 <= n_lon <= SPECTRA_MAX_LON, f"sphere_spectra_power: n_lon must be in 2..{SPECTRA_MAX_LON}, got {n_lon}"
+    assert lmax <= min((n_lat - 1) // 2, (n_lon - 1) // 2), \
+        f"sphere_spectra_power: lmax = {lmax} is above min((n_lat - 1) // 2, (n_lon - 1) // 2) on a {n_lat} x {n_lon} grid"
+    planes = _planes("sphere_spectra_power", [("prediction", pred), ("truth", truth)], dev, "table", n_lat, n_lon)
+    n, F = planes.n, 1 if truth is None else 3
+    power = torch.empty(n, F, lmax + 1, dtype=torch.float64, device=dev)
+    valid = torch.empty(n, dtype=torch.uint8, device=dev)
+    dropped = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return power, valid.view(torch.bool), dropped
+    at = planes.upload()
+    twiddle = spectra_twiddle(n_lon, dev)
+    nbytes = sphere_spectra_workspace_bytes(n, n_lat, n_lon, lmax, truth is not None)
+    workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)   # (from torch's caching allocator: no hipMalloc warm)
+    K = n_lon // 2 + 1
+    work = 2.0 * ((F + 1) // 2 * n * n_lat) * K * (2 * (lmax + 1)) + 2.0 * ((F + 1) // 2 * 2 * n) * n_lat * n_rows
+    _launch(dev, "sphere_spectra", work, "aurora_hip_sphere_spectra", at["prediction"], at["truth"], n, n_lat, n_lon, lmax,
+            int(pole_rows), _ptr(table), _ptr(twiddle), _ptr(power), _ptr(valid), _ptr(dropped), _ptr(workspace), nbytes)
+    return power, valid.view(torch.bool), dropped
 
 
 # ---- events: contingency tables and fractions skill score (aurora_hip_event_scores) -----------------------------------

@@ -869,6 +869,38 @@ int aurora_hip_spectra(const float* const* pred_planes, const float* const* trut
                        int n_bands, const double* band_w, const double* twiddle, double* power, int64_t* rows, void* workspace,
                        size_t workspace_bytes, void* stream);
 
+/* ---- spherical-harmonic power spectra on the device (aurora_amd.sphere_spectra; not in the reference) --------------------
+ * Planes as above on a full circle of N = n_lon equally spaced longitudes and H = n_lat >= 2 strictly monotonic latitudes.
+ * THE RULE of aurora_amd/sphere_spectra.py, for the device:
+ *   TABLE      `table` holds A[m][l][i] = 0.5 w_i Pbar_l^m(sin lat_i) for 0 <= m <= l <= lmax, 0 <= i < H as device doubles,
+ *              packed triangularly at (m (lmax + 1) - m (m - 1) / 2 + (l - m)) H + i; w the interpolatory quadrature weights of
+ *              the latitude nodes, Pbar the 4 pi-normalised associated Legendre functions, both formed by the caller in fp64.
+ *   LMAX       0 <= lmax <= min((H - 1) / 2, (N - 1) / 2): the quadrature is exact for every product of two basis functions
+ *              up to that degree and no further.  A table above 1 GiB is refused; the message names the largest lmax that fits.
+ *   TRANSFORM  F_m(i) = (1/N) sum_n x_i[n] exp(-2 pi i m n / N), m = 0 .. lmax, the fp32 values converted to fp64 exactly
+ *              (folded against `twiddle` as in aurora_hip_spectra);  a_lm = sum_i A[m][l][i] F_m(i);
+ *              S_l = sum_{m = 0 .. l} c_m |a_lm|^2, c_0 = 1 and c_m = 2 otherwise, m ascending.
+ *   TRUTH      unless truth_planes is NULL, the same S from a^truth and from a^pred - a^truth: F = 3 fields (pred, truth,
+ *              error), else F = 1.    power[(plane F + f) (lmax + 1) + l] = S_l.
+ *   VALIDITY   a plane is valid where every value of every input given is finite; an invalid plane gives NaN in every field
+ *              and valid[plane] = 0 (else 1).  Exception: a pole row -- row 0 where pole_rows & 1, row H - 1 where
+ *              pole_rows & 2 -- that holds a non-finite value in any input enters as zeros in every input and is counted in
+ *              pole_rows_dropped[plane]; its weight is not redistributed.
+ * Three launches: the zonal stage writes F to the workspace as (re, im) in the order [plane][field][m][i]; the Legendre stage
+ * is a triangular batch of GEMMs on v_mfma_f64_16x16x4_f64 (rows: 16 degrees, K: latitude in steps of 4, columns: planes) that
+ * adds c_m |a_lm|^2 in registers over segments of 16 consecutive m and writes one partial per segment (only the segments that
+ * reach a tile's degrees are launched); the finish adds the segments a degree has, l / 16 + 1 of them, in m order.  No floating-point atomics; the tree depends on (H, N, lmax, the presence of a truth) alone; a plane's
+ * result is repeatable bit for bit and does not depend on the other planes of the call or on pointer alignment (every load of
+ * a plane is a 4-byte load).  workspace: 16-byte aligned, no initialisation needed,
+ *   n_planes x (1 or 2) x 16 (lmax + 1) H bytes of F, then n_planes x F x ceil((lmax + 1) / 16) x (lmax + 1) doubles of
+ *   partials, then n_planes x ceil(H / 32) x 2 int32 flags, rounded up to 16 = aurora_hip_sphere_spectra_workspace_bytes(...)
+ * (0 for an argument out of range).  n_planes = 0 is a no-op.  The inputs are not modified.  No host synchronisation, no
+ * allocation, no environment variable: capturable in a hipGraph. */
+size_t aurora_hip_sphere_spectra_workspace_bytes(int n_planes, int n_lat, int n_lon, int lmax, int has_truth);
+int aurora_hip_sphere_spectra(const float* const* pred_planes, const float* const* truth_planes, int n_planes, int n_lat,
+                              int n_lon, int lmax, int pole_rows, const double* table, const double* twiddle, double* power,
+                              uint8_t* valid, int32_t* pole_rows_dropped, void* workspace, size_t workspace_bytes, void* stream);
+
 /* ---- events: contingency tables and the Fractions Skill Score on the device (aurora_amd.event_scores; not in the reference)
  * Planes as above.  A point (i, j) is VALID where pred and truth are both finite.  For plane k, threshold
  * thr = thresholds[k T + t] (fp32, compared in fp32) and the odd window size n = scales[s] = 2 h + 1:
