@@ -311,6 +311,34 @@ def by_variable(layout: Layout, t: torch.Tensor) -> dict[str, torch.Tensor]:
     return out
 
 
+class PowerViews:
+    """The views that `Spectra` and `SphereSpectra` share, over the result's `table` ((n_planes, 1 or 3, ...): pred, truth,
+    error) and `layout`.  No fields of its own."""
+
+    def _field(self, t: torch.Tensor) -> dict[str, torch.Tensor]:
+        return by_variable(self.layout, t)
+
+    @property
+    def has_truth(self) -> bool:
+        return self.table.shape[1] == 3
+
+    @property
+    def power(self) -> dict[str, torch.Tensor]:
+        return self._field(self.table[:, 0])
+
+    @property
+    def truth_power(self) -> Optional[dict[str, torch.Tensor]]:
+        return self._field(self.table[:, 1]) if self.has_truth else None
+
+    @property
+    def error_power(self) -> Optional[dict[str, torch.Tensor]]:
+        return self._field(self.table[:, 2]) if self.has_truth else None
+
+    @property
+    def ratio(self) -> Optional[dict[str, torch.Tensor]]:
+        return self._field(self.table[:, 0] / self.table[:, 1]) if self.has_truth else None
+
+
 # ---- where the fields are reduced ------------------------------------------------------------------------------------
 def stack(fs: Sequence[torch.Tensor], n_lat: int, n_lon: int) -> np.ndarray:
     """Host fields as one (n_planes, n_lat, n_lon) array."""

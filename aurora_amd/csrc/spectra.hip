@@ -1,93 +1,32 @@
 // Zonal power spectra of forecast planes on the device (aurora_amd.spectra), on the fp64 matrix pipe.
 //
-// For every row x[0 .. N-1] of a plane (n_lat x N fp32, row-major) the real DFT X[k], k = 0 .. K-1, K = N/2 + 1, is a GEMM:
-//   M          the rows of a 16-row MFMA tile: 16 grid rows of the prediction, or, with a truth, 8 grid rows of the
-//              prediction (tile rows 0-7) and the SAME 8 grid rows of the truth (tile rows 8-15), so that the error spectrum
-//              |X_pred - X_truth|^2 is a difference of two accumulators of one lane;
-//   K-dim      longitude, FOLDED: with p[j] = x[j] + x[N-j], m[j] = x[j] - x[N-j] for 0 < j < N/2, p[j] = x[j], m[j] = 0 for
-//              j = 0 and j = N/2,     Re X[k] = sum_j p[j] cos(2 pi j k / N),   -Im X[k] = sum_j m[j] sin(2 pi j k / N)
-//              over j = 0 .. K-1: half the multiplications of the direct form, one extra rounding per input pair;
-//   N-dim      the K cosine and the K sine columns.
-// Operand A: the fp32 rows are read coalesced, converted to fp64 (exact), folded, and staged in LDS 128 folded columns at a
-// time as (p, m) pairs; the next chunk's global loads are in flight while the current one is multiplied.  Operand B is never
-// a matrix in memory: B[j][k] = table[(j k) mod N] from the N-entry (cos, sin) table in LDS; a lane walks j in steps of 4
-// for its column k, so its index advances by (4 k) mod N with one conditional subtract.  Accumulation is the MFMA's own
-// fp64 accumulator, j ascending.
-//
-// One workgroup = 8 wavefronts = one chunk of 32 grid rows of one plane, tile after tile.  A wavefront owns up to 6
-// 16-column tiles (column tile = pass + 8 c + wave): 768 columns per pass over the rows, so N <= 1534 takes one pass and the
-// rows are read once; a larger N re-reads the tile's rows (from L2) once per further pass.
+// The transform of a 16-row tile -- the GEMM, the folding, the staging, the table and the passes over the column tiles -- is
+// zonal_dft.h's; this file is what becomes of a tile's accumulators.
+// One workgroup = 8 wavefronts = one chunk of 32 grid rows of one plane, tile after tile, over all K = N/2 + 1 wavenumbers:
+// N <= 1534 takes one pass.
 // Epilogue per tile: power = c_k |X|^2 / N^2 for pred, truth and pred - truth; times the band's row weight (0 for a row
 // that is invalid, outside the band or beyond the grid); summed over the tile's rows in a fixed order (registers ascending,
 // then an xor butterfly over the four 16-lane groups) and added to the chunk's partial by the one lane that owns
 // (field, band, k) -- plain loads and stores of that lane in program order, no atomics.
 // spectra_finish_kernel adds a plane's chunk partials in chunk order and divides by the band's weight sum.
 //
-// Row validity comes from the inputs: while staging, a non-finite value flags its grid row and is replaced by 0.
+// Row validity is the tile's: a grid row that it flagged as non-finite has weight 0 in every band.
 // The tree is fixed and depends on n_lat, N and has_truth only: results are repeatable bit for bit, independent of the other
-// planes of the call, and independent of pointer alignment (every global load of a plane is a 4-byte load).
-#include "planes.h"
+// planes of the call, and independent of pointer alignment.
+#include "zonal_dft.h"
 
 namespace aurora {
 namespace {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-
-constexpr int kThreads = 512;
-constexpr int kWaves = kThreads / 64;
-constexpr int kColTiles = 6;                            // 16-column tiles per wavefront and pass
-constexpr int kPassTiles = kWaves * kColTiles;          // 48 tiles = 768 columns per pass
-constexpr int kChunkJ = 128;                            // folded columns staged at a time
-constexpr int kAStride = 17;                            // (p, m) pairs per staged column: 16 tile rows + 1 (bank spread)
 constexpr int kChunkRows = 32;                          // grid rows per workgroup
 constexpr int kMaxBands = 8;
-constexpr int kMaxLon = 4096;
-constexpr int kStageQ = 16 * kChunkJ / kThreads;        // staged values per thread and chunk (4)
-
 
 __host__ __device__ inline int64_t chunks_per_plane(int n_lat) { return ((int64_t)n_lat + kChunkRows - 1) / kChunkRows; }
 // doubles of one chunk partial: (field, band, k) sums, then per band the weight sum and the count of valid rows
 __host__ __device__ inline int64_t block_doubles(int n_lon, int n_bands, int has_truth) {
   return (int64_t)(has_truth ? 3 : 1) * n_bands * (n_lon / 2 + 1) + 2 * n_bands;
 }
-inline size_t lds_bytes(int n_lon) {
-  return (size_t)(n_lon + kChunkJ * kAStride) * sizeof(f64x2) + kMaxBands * 16 * sizeof(double) + 16 * sizeof(int);
-}
-
-// One staged chunk times the table for the wavefront's six column tiles: `steps` k-steps of 4 folded columns, no branch
-// inside: seven LDS reads, then twelve MFMAs that start as their operands arrive (the workgroup keeps two wavefronts on
-// every SIMD, so one wavefront's reads are in flight under the other's MFMAs).  (A column tile beyond the last wavenumber is
-// multiplied like the others -- its table indices stay inside the table -- and never written.)
-__device__ __forceinline__ void next_operands(const f64x2* __restrict__ s_tab, int N, int (&idx)[kColTiles],
-                                              const int (&step)[kColTiles], f64x2 (&tw)[kColTiles]) {
-#pragma unroll
-  for (int c = 0; c < kColTiles; ++c) {
-    tw[c] = s_tab[idx[c]];
-    const int t = idx[c] + step[c];
-    idx[c] = t >= N ? t - N : t;
-  }
-}
-
-__device__ __forceinline__ void multiply_step(const f64x2 av, const f64x2 (&tw)[kColTiles], f64x4 (&acc_re)[kColTiles],
-                                              f64x4 (&acc_im)[kColTiles]) {
-#pragma unroll
-  for (int c = 0; c < kColTiles; ++c) {
-    acc_re[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(av.x, tw[c].x, acc_re[c], 0, 0, 0);
-    acc_im[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(av.y, tw[c].y, acc_im[c], 0, 0, 0);
-  }
-}
-
-__device__ __forceinline__ void multiply_chunk(const f64x2* __restrict__ a_ptr, const f64x2* __restrict__ s_tab, int steps,
-                                               int N, int (&idx)[kColTiles], const int (&step)[kColTiles],
-                                               f64x4 (&acc_re)[kColTiles], f64x4 (&acc_im)[kColTiles]) {
-  for (int s = 0; s < steps; ++s) {
-    f64x2 tw[kColTiles];
-    const f64x2 av = a_ptr[s * 4 * kAStride];
-    next_operands(s_tab, N, idx, step, tw);
-    multiply_step(av, tw, acc_re, acc_im);
-  }
-}
+inline size_t lds_bytes(int n_lon) { return zonal_dft_lds_bytes(n_lon) + kMaxBands * 16 * sizeof(double); }
 
 template <bool kTruth>
 __global__ __launch_bounds__(kThreads) void spectra_kernel(const float* const* __restrict__ pred_planes,
@@ -95,10 +34,9 @@ __global__ __launch_bounds__(kThreads) void spectra_kernel(const float* const* _
                                                            int n_bands, int n_chunks, const double* __restrict__ band_w,
                                                            const double* __restrict__ twiddle, double* __restrict__ partial) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  f64x2* const s_tab = reinterpret_cast<f64x2*>(smem);                 // [N] (cos, sin)
-  f64x2* const s_a = s_tab + N;                                        // [kChunkJ][kAStride] (p, m)
-  double* const s_w = reinterpret_cast<double*>(s_a + kChunkJ * kAStride);   // [kMaxBands][16] band weight of a tile's rows
-  int* const s_bad = reinterpret_cast<int*>(s_w + kMaxBands * 16);     // [16] a grid row of the tile holds a non-finite value
+  const ZonalLds lds = zonal_dft_lds(smem, N);
+  int* const s_bad = lds.bad;
+  double* const s_w = reinterpret_cast<double*>(lds.tail);            // [kMaxBands][16] band weight of a tile's rows
 
   constexpr int GR = kTruth ? 8 : 16;                                  // grid rows per tile
   constexpr int F = kTruth ? 3 : 1;
@@ -114,10 +52,7 @@ __global__ __launch_bounds__(kThreads) void spectra_kernel(const float* const* _
   double* const part = partial + (int64_t)blockIdx.x * block_doubles(N, n_bands, kTruth ? 1 : 0);
   const double n2 = (double)N * (double)N;
 
-  for (int m = tid; m < N; m += kThreads) s_tab[m] = f64x2{twiddle[2 * m], twiddle[2 * m + 1]};
-
-  // staging role of this thread: folded column jl of the chunk, tile rows sm + 4 q
-  const int jl = tid & (kChunkJ - 1), sm = tid >> 7;
+  zonal_dft_load_table(lds.tab, twiddle, N);
   const int row_begin = chunk * kChunkRows, row_end = min(row_begin + kChunkRows, n_lat);
 
   for (int row0 = row_begin; row0 < row_end; row0 += GR) {
@@ -128,56 +63,7 @@ __global__ __launch_bounds__(kThreads) void spectra_kernel(const float* const* _
     for (int pass = 0; pass < n_coltiles; pass += kPassTiles) {
       const int nct = min(kColTiles, max(0, (n_coltiles - pass - wave + kWaves - 1) / kWaves));   // wave-uniform
       f64x4 acc_re[kColTiles], acc_im[kColTiles];
-      int idx[kColTiles], step[kColTiles];
-#pragma unroll
-      for (int c = 0; c < kColTiles; ++c) {
-        acc_re[c] = f64x4{0.0, 0.0, 0.0, 0.0};
-        acc_im[c] = f64x4{0.0, 0.0, 0.0, 0.0};
-        const int k = 16 * (pass + c * kWaves + wave) + lc;
-        idx[c] = (int)(((unsigned)lg * (unsigned)k) % (unsigned)N);
-        step[c] = (int)((4u * (unsigned)k) % (unsigned)N);
-      }
-
-      float ga[kStageQ], gb[kStageQ];
-      auto fetch = [&](int j0) {                                       // the chunk's values of this thread, raw
-        const int j = j0 + jl;
-        const bool has_b = j > 0 && 2 * j != N && j < J;
-#pragma unroll
-        for (int q = 0; q < kStageQ; ++q) {
-          const int m = sm + 4 * q;
-          const int row = row0 + (kTruth ? (m & 7) : m);
-          const gptr<const float> src = (kTruth && m >= 8) ? T : P;
-          const bool in = j < J && row < n_lat;
-          const int64_t base = (int64_t)(in ? row : 0) * N;
-          ga[q] = in ? src[base + j] : 0.f;
-          gb[q] = (in && has_b) ? src[base + (N - j)] : 0.f;
-        }
-      };
-      fetch(0);
-
-      for (int j0 = 0; j0 < J; j0 += kChunkJ) {
-        __syncthreads();                                               // the previous chunk has been multiplied
-        {
-          const int j = j0 + jl;
-          const bool has_b = j > 0 && 2 * j != N && j < J;
-#pragma unroll
-          for (int q = 0; q < kStageQ; ++q) {
-            const int m = sm + 4 * q;
-            const bool ok = __builtin_isfinite(ga[q]) && __builtin_isfinite(gb[q]);
-            if (!ok) s_bad[kTruth ? (m & 7) : m] = 1;
-            const double a = (double)(ok ? ga[q] : 0.f), b = (double)(ok ? gb[q] : 0.f);
-            s_a[jl * kAStride + m] = f64x2{a + b, has_b ? a - b : 0.0};
-          }
-        }
-        __syncthreads();
-        if (j0 + kChunkJ < J) fetch(j0 + kChunkJ);
-
-        const int steps = (min(kChunkJ, J - j0) + 3) >> 2;
-        const f64x2* a_ptr = s_a + lg * kAStride + lc;
-        multiply_chunk(a_ptr, s_tab, steps, N, idx, step, acc_re, acc_im);
-      }
-
-      __syncthreads();                                                 // every row of the tile has been seen: s_bad is final
+      zonal_dft_tile<kTruth>(lds, P, T, n_lat, N, row0, pass + wave, acc_re, acc_im);   // (s_bad is final)
       if (pass == 0) {
         if (tid < n_bands * 16) {
           const int b = tid >> 4, g = tid & 15, row = row0 + g;

@@ -2,11 +2,10 @@
 // THE RULE is stated in aurora_amd/sphere_spectra.py and repeated in include/aurora_hip.h; the index arithmetic of the table
 // and of the workspace is in sphere_spectra_index.h.  Three launches:
 //
-// 1. Zonal stage (sphere_zonal_kernel): F_m(i) = (1/N) sum_n x_i[n] exp(-2 pi i m n / N) for m = 0 .. lmax of every row, as the
-//    folded DFT GEMM of spectra.hip: tile rows = 16 grid rows of the prediction or, with a truth, 8 grid rows of the prediction
-//    and the SAME 8 of the truth (a row's validity is one flag for both); K-dim = longitude folded to N / 2 + 1 columns
-//    (p[j] = x[j] + x[N-j] against the cosines, m[j] = x[j] - x[N-j] against the sines), staged in LDS 128 at a time; operand B
-//    is table[(j m) mod N] from the (cos, sin) table in LDS.  Only the column tiles with m <= lmax are multiplied.  The tile is
+// 1. Zonal stage (sphere_zonal_kernel): F_m(i) = (1/N) sum_n x_i[n] exp(-2 pi i m n / N) for m = 0 .. lmax of every row, by the
+//    folded DFT tile of zonal_dft.h, which spectra.hip multiplies with too: tile rows = 16 grid rows of the prediction or, with
+//    a truth, 8 grid rows of the prediction and the SAME 8 of the truth (a row's validity is one flag for both).  Only the
+//    column tiles with m <= lmax are multiplied, in one pass (lmax < 512 keeps them under the 48 of a pass).  The tile is
 //    written to the workspace as (re, im) in the order [plane][field][m][i].  A non-finite value is staged as 0 and flags its
 //    row: a flagged pole row is written as zeros in every field and counted, any other flagged row marks the plane invalid;
 //    both go to the (plane, row chunk) flag words of the workgroup -- plain stores, no atomics.
@@ -21,28 +20,15 @@
 //    plane's `valid` and `pole_rows_dropped` from its chunks' flag words.
 //
 // Every load of a plane is a 4-byte load; the planes of a call share nothing but the launch; nothing is read back.
-#include "planes.h"
 #include "sphere_spectra_index.h"
+#include "zonal_dft.h"
 
 namespace aurora {
 namespace {
 
-typedef double f64x4 __attribute__((ext_vector_type(4)));
-typedef double f64x2 __attribute__((ext_vector_type(2)));
-
-constexpr int kThreads = 512;
-constexpr int kWaves = kThreads / 64;
-constexpr int kColTiles = 6;                            // 16-column tiles per wavefront and pass
-constexpr int kPassTiles = kWaves * kColTiles;          // 48 tiles = 768 columns per pass
-constexpr int kChunkJ = 128;                            // folded columns staged at a time
-constexpr int kAStride = 17;                            // (p, m) pairs per staged column: 16 tile rows + 1 (bank spread)
-constexpr int kMaxLon = 4096;
-constexpr int kStageQ = 16 * kChunkJ / kThreads;        // staged values per thread and chunk (4)
 constexpr int kSteps = 4;                               // K-steps of 4 latitudes per turn of the Legendre loop
 
-inline size_t zonal_lds_bytes(int n_lon) {
-  return (size_t)(n_lon + kChunkJ * kAStride) * sizeof(f64x2) + 2 * 16 * sizeof(int);
-}
+inline size_t zonal_lds_bytes(int n_lon) { return zonal_dft_lds_bytes(n_lon) + 16 * sizeof(int); }
 
 // ---- 1. the zonal stage ---------------------------------------------------------------------------------------------------
 // pole_rows: bit 0 -- row 0 is a pole (|lat| = 90), bit 1 -- row n_lat - 1 is one.
@@ -52,10 +38,9 @@ __global__ __launch_bounds__(kThreads) void sphere_zonal_kernel(const float* con
                                                                 int lmax, int pole_rows, const double* __restrict__ twiddle,
                                                                 f64x2* __restrict__ F, int* __restrict__ flags) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  f64x2* const s_tab = reinterpret_cast<f64x2*>(smem);                 // [N] (cos, sin)
-  f64x2* const s_a = s_tab + N;                                        // [kChunkJ][kAStride] (p, m)
-  int* const s_bad = reinterpret_cast<int*>(s_a + kChunkJ * kAStride);  // [16] a grid row of the tile holds a non-finite value
-  int* const s_zero = s_bad + 16;                                      // [16] the same, as the tile's epilogue reads it
+  const ZonalLds lds = zonal_dft_lds(smem, N);
+  int* const s_bad = lds.bad;
+  int* const s_zero = reinterpret_cast<int*>(lds.tail);                // [16] s_bad, as the tile's epilogue reads it
 
   constexpr int GR = kTruth ? 8 : 16;                                  // grid rows per tile
   constexpr int NI = kTruth ? 2 : 1;
@@ -65,16 +50,12 @@ __global__ __launch_bounds__(kThreads) void sphere_zonal_kernel(const float* con
   const int tid = (int)threadIdx.x, lane = tid & 63;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int lg = lane >> 4, lc = lane & 15;
-  const int J = N / 2 + 1;                                             // folded length
   const int n_coltiles = (lmax + 16) >> 4;                             // the columns m = 0 .. lmax
   const gptr<const float> P = (gptr<const float>)pred_planes[plane];
   const gptr<const float> T = kTruth ? (gptr<const float>)truth_planes[plane] : P;
   const double inv_n = 1.0 / (double)N;
 
-  for (int m = tid; m < N; m += kThreads) s_tab[m] = f64x2{twiddle[2 * m], twiddle[2 * m + 1]};
-
-  // staging role of this thread: folded column jl of the chunk, tile rows sm + 4 q
-  const int jl = tid & (kChunkJ - 1), sm = tid >> 7;
+  zonal_dft_load_table(lds.tab, twiddle, N);
   const int row_begin = chunk * kSphereChunkRows, row_end = min(row_begin + kSphereChunkRows, n_lat);
   int invalid = 0, dropped = 0;                                        // of the chunk: thread 0 keeps them
 
@@ -82,103 +63,37 @@ __global__ __launch_bounds__(kThreads) void sphere_zonal_kernel(const float* con
     if (tid < 16) s_bad[tid] = 0;
     __syncthreads();
 
-    for (int pass = 0; pass < n_coltiles; pass += kPassTiles) {
-      const int nct = min(kColTiles, max(0, (n_coltiles - pass - wave + kWaves - 1) / kWaves));   // wave-uniform
-      f64x4 acc_re[kColTiles], acc_im[kColTiles];
-      int idx[kColTiles], step[kColTiles];
-#pragma unroll
-      for (int c = 0; c < kColTiles; ++c) {
-        acc_re[c] = f64x4{0.0, 0.0, 0.0, 0.0};
-        acc_im[c] = f64x4{0.0, 0.0, 0.0, 0.0};
-        const int k = 16 * (pass + c * kWaves + wave) + lc;
-        idx[c] = (int)(((unsigned)lg * (unsigned)k) % (unsigned)N);
-        step[c] = (int)((4u * (unsigned)k) % (unsigned)N);
-      }
-
-      float ga[kStageQ], gb[kStageQ];
-      auto fetch = [&](int j0) {                                       // the chunk's values of this thread, raw
-        const int j = j0 + jl;
-        const bool has_b = j > 0 && 2 * j != N && j < J;
-#pragma unroll
-        for (int q = 0; q < kStageQ; ++q) {
-          const int m = sm + 4 * q;
-          const int row = row0 + (kTruth ? (m & 7) : m);
-          const gptr<const float> src = (kTruth && m >= 8) ? T : P;
-          const bool in = j < J && row < n_lat;
-          const int64_t base = (int64_t)(in ? row : 0) * N;
-          ga[q] = in ? src[base + j] : 0.f;
-          gb[q] = (in && has_b) ? src[base + (N - j)] : 0.f;
-        }
-      };
-      fetch(0);
-
-      for (int j0 = 0; j0 < J; j0 += kChunkJ) {
-        __syncthreads();                                               // the previous chunk has been multiplied
-        {
-          const int j = j0 + jl;
-          const bool has_b = j > 0 && 2 * j != N && j < J;
-#pragma unroll
-          for (int q = 0; q < kStageQ; ++q) {
-            const int m = sm + 4 * q;
-            const bool ok = __builtin_isfinite(ga[q]) && __builtin_isfinite(gb[q]);
-            if (!ok) s_bad[kTruth ? (m & 7) : m] = 1;
-            const double a = (double)(ok ? ga[q] : 0.f), b = (double)(ok ? gb[q] : 0.f);
-            s_a[jl * kAStride + m] = f64x2{a + b, has_b ? a - b : 0.0};
-          }
-        }
-        __syncthreads();
-        if (j0 + kChunkJ < J) fetch(j0 + kChunkJ);
-
-        const int steps = (min(kChunkJ, J - j0) + 3) >> 2;
-        const f64x2* a_ptr = s_a + lg * kAStride + lc;
-        for (int s = 0; s < steps; ++s) {                              // (a column tile beyond lmax is multiplied like the
-          f64x2 tw[kColTiles];                                         //  others -- its indices stay inside the table -- and
-          const f64x2 av = a_ptr[s * 4 * kAStride];                    //  never written)
-#pragma unroll
-          for (int c = 0; c < kColTiles; ++c) {
-            tw[c] = s_tab[idx[c]];
-            const int t = idx[c] + step[c];
-            idx[c] = t >= N ? t - N : t;
-          }
-#pragma unroll
-          for (int c = 0; c < kColTiles; ++c) {
-            acc_re[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(av.x, tw[c].x, acc_re[c], 0, 0, 0);
-            acc_im[c] = __builtin_amdgcn_mfma_f64_16x16x4f64(av.y, tw[c].y, acc_im[c], 0, 0, 0);
-          }
+    // One pass: n_lat >= 2 lmax + 1 and the table's cap of 1 GiB keep lmax below 512: at most 32 column tiles, under kPassTiles.
+    const int nct = min(kColTiles, max(0, (n_coltiles - wave + kWaves - 1) / kWaves));   // wave-uniform
+    f64x4 acc_re[kColTiles], acc_im[kColTiles];
+    zonal_dft_tile<kTruth>(lds, P, T, n_lat, N, row0, wave, acc_re, acc_im);   // (s_bad is final)
+    if (tid < 16) s_zero[tid] = s_bad[tid];
+    if (tid == 0) {
+      for (int g = 0; g < GR; ++g) {
+        const int row = row0 + g;
+        if (row < n_lat && s_bad[g]) {
+          const bool pole = (row == 0 && (pole_rows & 1)) || (row == n_lat - 1 && (pole_rows & 2));
+          if (pole) ++dropped;
+          else invalid = 1;
         }
       }
-
-      __syncthreads();                                                 // every row of the tile has been seen: s_bad is final
-      if (pass == 0) {
-        if (tid < 16) s_zero[tid] = s_bad[tid];
-        if (tid == 0) {
-          for (int g = 0; g < GR; ++g) {
-            const int row = row0 + g;
-            if (row < n_lat && s_bad[g]) {
-              const bool pole = (row == 0 && (pole_rows & 1)) || (row == n_lat - 1 && (pole_rows & 2));
-              if (pole) ++dropped;
-              else invalid = 1;
-            }
-          }
-        }
-        __syncthreads();
-      }
+    }
+    __syncthreads();
 
 #pragma unroll
-      for (int c = 0; c < kColTiles; ++c) {
-        if (c < nct) {
-          const int m = 16 * (pass + c * kWaves + wave) + lc;
+    for (int c = 0; c < kColTiles; ++c) {
+      if (c < nct) {
+        const int m = 16 * (c * kWaves + wave) + lc;
 #pragma unroll
-          for (int i = 0; i < R; ++i) {
-            const int g = lg + 4 * i, row = row0 + g;                  // (with a truth: registers i and i + 2 of grid row g)
-            if (m <= lmax && row < n_lat) {
-              const bool zero = s_zero[g] != 0;
-              const f64x2 vp = {zero ? 0.0 : acc_re[c][i] * inv_n, zero ? 0.0 : -(acc_im[c][i] * inv_n)};
-              F[sphere_f_offset(lmax, n_lat, NI, plane, 0, m, row)] = vp;
-              if (kTruth) {
-                const f64x2 vt = {zero ? 0.0 : acc_re[c][i + 2] * inv_n, zero ? 0.0 : -(acc_im[c][i + 2] * inv_n)};
-                F[sphere_f_offset(lmax, n_lat, NI, plane, 1, m, row)] = vt;
-              }
+        for (int i = 0; i < R; ++i) {
+          const int g = lg + 4 * i, row = row0 + g;                    // (with a truth: registers i and i + 2 of grid row g)
+          if (m <= lmax && row < n_lat) {
+            const bool zero = s_zero[g] != 0;
+            const f64x2 vp = {zero ? 0.0 : acc_re[c][i] * inv_n, zero ? 0.0 : -(acc_im[c][i] * inv_n)};
+            F[sphere_f_offset(lmax, n_lat, NI, plane, 0, m, row)] = vp;
+            if (kTruth) {
+              const f64x2 vt = {zero ? 0.0 : acc_re[c][i + 2] * inv_n, zero ? 0.0 : -(acc_im[c][i + 2] * inv_n)};
+              F[sphere_f_offset(lmax, n_lat, NI, plane, 1, m, row)] = vt;
             }
           }
         }

@@ -50,7 +50,7 @@ MAX_BANDS = 8
 
 
 @dataclasses.dataclass(frozen=True)
-class Spectra:
+class Spectra(_fields.PowerViews):
     """Result of `spectra`: every property but `wavenumber` is a dict name -> tensor with the leading shape (B,) for a surface
     variable and (B, C) for an atmospheric one, on the device of the prediction."""
 
@@ -58,29 +58,6 @@ class Spectra:
     rows_table: torch.Tensor                             # (n_planes, n_bands) int64
     layout: tuple[tuple[str, int, tuple[int, ...]], ...]   # (name, first plane, shape) per variable
     bands: tuple[tuple[float, float], ...]
-
-    def _field(self, t: torch.Tensor) -> dict[str, torch.Tensor]:
-        return _fields.by_variable(self.layout, t)
-
-    @property
-    def has_truth(self) -> bool:
-        return self.table.shape[1] == 3
-
-    @property
-    def power(self) -> dict[str, torch.Tensor]:
-        return self._field(self.table[:, 0])
-
-    @property
-    def truth_power(self) -> Optional[dict[str, torch.Tensor]]:
-        return self._field(self.table[:, 1]) if self.has_truth else None
-
-    @property
-    def error_power(self) -> Optional[dict[str, torch.Tensor]]:
-        return self._field(self.table[:, 2]) if self.has_truth else None
-
-    @property
-    def ratio(self) -> Optional[dict[str, torch.Tensor]]:
-        return self._field(self.table[:, 0] / self.table[:, 1]) if self.has_truth else None
 
     @property
     def rows(self) -> dict[str, torch.Tensor]:

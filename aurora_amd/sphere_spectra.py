@@ -229,7 +229,7 @@ def coefficients(A: np.ndarray, lmax: int, m: int, Fm: np.ndarray) -> np.ndarray
 
 # ---- the result ----------------------------------------------------------------------------------------------------------------
 @dataclasses.dataclass(frozen=True)
-class SphereSpectra:
+class SphereSpectra(_fields.PowerViews):
     """Result of `sphere_spectra`: every property but `degree` is a dict name -> tensor with the leading shape (B,) for a
     surface variable and (B, C) for an atmospheric one, on the device of the prediction."""
 
@@ -238,29 +238,6 @@ class SphereSpectra:
     dropped_table: torch.Tensor                            # (n_planes,) int32
     layout: tuple[tuple[str, int, tuple[int, ...]], ...]   # (name, first plane, shape) per variable
     lmax: int
-
-    def _field(self, t: torch.Tensor) -> dict[str, torch.Tensor]:
-        return _fields.by_variable(self.layout, t)
-
-    @property
-    def has_truth(self) -> bool:
-        return self.table.shape[1] == 3
-
-    @property
-    def power(self) -> dict[str, torch.Tensor]:
-        return self._field(self.table[:, 0])
-
-    @property
-    def truth_power(self) -> Optional[dict[str, torch.Tensor]]:
-        return self._field(self.table[:, 1]) if self.has_truth else None
-
-    @property
-    def error_power(self) -> Optional[dict[str, torch.Tensor]]:
-        return self._field(self.table[:, 2]) if self.has_truth else None
-
-    @property
-    def ratio(self) -> Optional[dict[str, torch.Tensor]]:
-        return self._field(self.table[:, 0] / self.table[:, 1]) if self.has_truth else None
 
     @property
     def valid(self) -> dict[str, torch.Tensor]:
