@@ -28,8 +28,10 @@ highs -- the points that are the minimum or maximum of all points within R kilom
 path to the rim of a disc, the closed-contour criterion of storm counts (aurora_amd/contours.py), and `link_extrema` links the
 candidates of two steps by an all-pairs nearest search on the sphere, from which `tracks` numbers the storm tracks of a roll-out
 (aurora_amd/links.py), and `sphere_spectra` gives the power spectra by total wavenumber -- the spherical-harmonic analysis of
-every plane -- and the kinetic-energy spectrum from vorticity and divergence (aurora_amd/sphere_spectra.py); the reference has
-no counterpart.
+every plane -- and the kinetic-energy spectrum from vorticity and divergence (aurora_amd/sphere_spectra.py), and
+`sphere_analysis`, `sphere_synthesis` and `sphere_filter` give the coefficients of that analysis, the field of a set of
+coefficients, and a field truncated or weighted by total wavenumber as a `Batch` on its own grid, which every scorer takes
+unchanged (aurora_amd/sphere_transform.py); the reference has no counterpart.
 """
 
 from aurora_amd.batch import Batch, Metadata
@@ -64,6 +66,7 @@ from aurora_amd.scores import Scores, scores
 from aurora_amd.smooth import smooth
 from aurora_amd.spectra import Spectra, spectra
 from aurora_amd.sphere_spectra import SphereSpectra, sphere_spectra
+from aurora_amd.sphere_transform import SphereCoefficients, sphere_analysis, sphere_filter, sphere_synthesis
 from aurora_amd.tracker import Tracker
 
 __all__ = [
@@ -89,6 +92,10 @@ __all__ = [
     "Spectra",
     "sphere_spectra",
     "SphereSpectra",
+    "sphere_analysis",
+    "sphere_synthesis",
+    "sphere_filter",
+    "SphereCoefficients",
     "event_scores",
     "EventScores",
     "probability_scores",

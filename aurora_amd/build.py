@@ -17,7 +17,7 @@ PKG = Path(__file__).resolve().parent
 CSRC = PKG / "csrc"
 LIB = PKG / "_lib" / "libaurora_hip.so"
 SOURCES = ("runtime.hip", "gemm.hip", "gemm_f32.hip", "gemm_ln512.hip", "gemm_a4.hip", "attention.hip", "norm.hip", "embed.hip", "perceiver_attention.hip", "perceiver_out.hip", "band.hip",
-           "model.hip", "model_weights.hip", "model_grid.hip", "step.hip", "regrid.hip", "conservative_regrid.hip", "planes.hip", "scores.hip", "ensemble_scores.hip", "ensemble_quantiles.hip", "spectra.hip", "sphere_spectra.hip", "event_scores.hip",
+           "model.hip", "model_weights.hip", "model_grid.hip", "step.hip", "regrid.hip", "conservative_regrid.hip", "planes.hip", "scores.hip", "ensemble_scores.hip", "ensemble_quantiles.hip", "spectra.hip", "sphere_spectra.hip", "sphere_transform.hip", "event_scores.hip",
            "field_stats.hip", "probability_scores.hip", "diagnostics.hip", "conditional_scores.hip", "region_scores.hip", "objects.hip", "field_quantiles.hip", "object_matches.hip", "nearest_event.hip", "smooth.hip", "extrema.hip", "contours.hip", "links.hip")
 ARCH = "gfx950"
 # -amdgpu-mfma-vgpr-form: keep MFMA accumulators in arch VGPRs (gfx950 has one unified file);

@@ -21,6 +21,7 @@
 //
 // Every load of a plane is a 4-byte load; the planes of a call share nothing but the launch; nothing is read back.
 #include "sphere_spectra_index.h"
+#include "sphere_zonal.h"
 #include "zonal_dft.h"
 
 namespace aurora {
@@ -206,6 +207,27 @@ __global__ __launch_bounds__(256) void sphere_finish_kernel(const double* __rest
 }
 
 }  // namespace
+
+// Launch one, for this call and for aurora_hip_sphere_analysis (sphere_transform.hip), which has no copy of the kernel: the
+// zonal stage of checked arguments on `s`, with a truth where truth_planes is given.  F is the workspace's f64x2 part.
+int sphere_zonal_launch(const float* const* pred_planes, const float* const* truth_planes, int n_planes, int n_lat, int n_lon,
+                        int lmax, int pole_rows, const double* twiddle, void* F, int* flags, hipStream_t s) {
+  once_per_device([] {
+    const int most = (int)zonal_lds_bytes(kMaxLon);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sphere_zonal_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, most);
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sphere_zonal_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, most);
+  });
+  const unsigned zonal_groups = (unsigned)((int64_t)sphere_chunks(n_lat) * n_planes);
+  const size_t lds = zonal_lds_bytes(n_lon);
+  if (truth_planes)
+    hipLaunchKernelGGL(sphere_zonal_kernel<true>, dim3(zonal_groups), dim3(kThreads), lds, s, pred_planes, truth_planes, n_lat,
+                       n_lon, lmax, pole_rows, twiddle, (f64x2*)F, flags);
+  else
+    hipLaunchKernelGGL(sphere_zonal_kernel<false>, dim3(zonal_groups), dim3(kThreads), lds, s, pred_planes, truth_planes, n_lat,
+                       n_lon, lmax, pole_rows, twiddle, (f64x2*)F, flags);
+  return check_launch("sphere_spectra (zonal)");
+}
+
 }  // namespace aurora
 
 using namespace aurora;
@@ -243,23 +265,11 @@ extern "C" int aurora_hip_sphere_spectra(const float* const* pred_planes, const 
   const int64_t values = (int64_t)n_planes * n_out * (lmax + 1);
   AURORA_CHECK_ARG(zonal_groups <= 0x7fffffff && tiles <= 0x7fffffff && plane_groups <= 65535 && (values + 255) / 256 <= 0x7fffffff,
                    "sphere_spectra: too many planes for one launch (%d planes)", n_planes);
-  once_per_device([] {
-    const int most = (int)zonal_lds_bytes(kMaxLon);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sphere_zonal_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, most);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&sphere_zonal_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, most);
-  });
   f64x2* const F = (f64x2*)workspace;
   double* const partial = (double*)((char*)workspace + sphere_f_bytes(lmax, n_lat, n_in, n_planes));
   int* const flags = (int*)((char*)partial + sphere_partial_bytes(lmax, n_out, n_planes));
   const hipStream_t s = as_stream(stream);
-  const size_t lds = zonal_lds_bytes(n_lon);
-  if (has_truth)
-    hipLaunchKernelGGL(sphere_zonal_kernel<true>, dim3((unsigned)zonal_groups), dim3(kThreads), lds, s, pred_planes, truth_planes,
-                       n_lat, n_lon, lmax, pole_rows, twiddle, F, flags);
-  else
-    hipLaunchKernelGGL(sphere_zonal_kernel<false>, dim3((unsigned)zonal_groups), dim3(kThreads), lds, s, pred_planes, truth_planes,
-                       n_lat, n_lon, lmax, pole_rows, twiddle, F, flags);
-  int code = check_launch("sphere_spectra (zonal)");
+  int code = sphere_zonal_launch(pred_planes, truth_planes, n_planes, n_lat, n_lon, lmax, pole_rows, twiddle, F, flags, s);
   if (code != AURORA_OK) return code;
   if (has_truth)
     hipLaunchKernelGGL(sphere_legendre_kernel<true>, dim3((unsigned)tiles, (unsigned)plane_groups), dim3(64), 0, s, table, F, n_lat,

@@ -1,5 +1,5 @@
 // Index arithmetic of aurora_hip_sphere_spectra (sphere_spectra.hip): the triangularly packed analysis table and the
-// workspace.  Plain integer functions that compile for the host alone too: tools/probes/sphere_spectra_index_host.cpp checks
+// workspace; at the end, of aurora_hip_sphere_analysis and aurora_hip_sphere_synthesis (sphere_transform.hip).  Plain integer functions that compile for the host alone too: tools/probes/sphere_spectra_index_host.cpp checks
 // every offset against a triple loop under the address and undefined-behaviour sanitizers.
 //
 // Table (doubles): A[m][l][i] for 0 <= m <= l <= lmax, 0 <= i < H; m outermost, then l from m upwards, then the latitude:
@@ -76,6 +76,24 @@ AURORA_SPHERE_HD inline int64_t sphere_workspace_bytes(int lmax, int H, int has_
   const int64_t b = sphere_f_bytes(lmax, H, has_truth ? 2 : 1, n_planes) + sphere_partial_bytes(lmax, has_truth ? 3 : 1, n_planes) +
                     sphere_flag_bytes(H, n_planes);
   return (b + 15) / 16 * 16;
+}
+
+// ---- aurora_hip_sphere_analysis and aurora_hip_sphere_synthesis (sphere_transform.hip) ------------------------------------
+// tools/probes/sphere_transform_index_host.cpp checks these the same way.
+//
+// Coefficients (pairs (re, im) of doubles), dense: n_planes x (lmax + 1) x (lmax + 1), [plane][m][l]; l < m holds zeros.
+// Synthesis table (doubles): P[m][l][i], packed exactly like the analysis table -- sphere_table_offset is its offset too.
+// Workspace of the analysis: F with n_in = 1, then the flags; of the synthesis: G, in the layout [plane][m][i] of F with
+// n_in = 1 (sphere_f_offset).
+AURORA_SPHERE_HD inline int64_t sphere_coeff_offset(int lmax, int plane, int m, int l) {
+  return ((int64_t)plane * (lmax + 1) + m) * (lmax + 1) + l;
+}
+AURORA_SPHERE_HD inline int64_t sphere_coeff_bytes(int lmax, int n_planes) { return 16 * sphere_coeff_offset(lmax, n_planes, 0, 0); }
+AURORA_SPHERE_HD inline int64_t sphere_analysis_workspace_bytes(int lmax, int H, int n_planes) {
+  return (sphere_f_bytes(lmax, H, 1, n_planes) + sphere_flag_bytes(H, n_planes) + 15) / 16 * 16;
+}
+AURORA_SPHERE_HD inline int64_t sphere_synthesis_workspace_bytes(int lmax, int H, int n_planes) {
+  return sphere_f_bytes(lmax, H, 1, n_planes);
 }
 
 }  // namespace aurora

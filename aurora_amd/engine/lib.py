@@ -145,6 +145,12 @@ _SIGNATURES = {
     "aurora_hip_sphere_spectra_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "aurora_hip_sphere_spectra": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                           c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
+    "aurora_hip_sphere_analysis_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int]),
+    "aurora_hip_sphere_analysis": (c_int, [c_void_p, c_int, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
+    "aurora_hip_sphere_synthesis_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int]),
+    "aurora_hip_sphere_synthesis": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                            ctypes.c_size_t, c_void_p]),
     "aurora_hip_event_scores_workspace_bytes": (ctypes.c_size_t, [c_int, c_int, c_int, c_int, c_int]),
     "aurora_hip_event_scores": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_int,
                                         c_void_p, c_void_p, c_void_p, ctypes.c_size_t, c_void_p]),
@@ -1201,6 +1207,91 @@ def sphere_spectra_power(pred: list[torch.Tensor], truth: Optional[list[torch.Te
     _launch(dev, "sphere_spectra", work, "aurora_hip_sphere_spectra", at["prediction"], at["truth"], n, n_lat, n_lon, lmax,
             int(pole_rows), _ptr(table), _ptr(twiddle), _ptr(power), _ptr(valid), _ptr(dropped), _ptr(workspace), nbytes)
     return power, valid.view(torch.bool), dropped
+
+
+# ---- spherical-harmonic analysis and synthesis (aurora_hip_sphere_analysis, aurora_hip_sphere_synthesis) -------------------
+def sphere_analysis_workspace_bytes(n_planes: int, n_lat: int, n_lon: int, lmax: int) -> int:
+    return int(load().aurora_hip_sphere_analysis_workspace_bytes(n_planes, n_lat, n_lon, lmax))
+
+
+def sphere_synthesis_workspace_bytes(n_planes: int, n_lat: int, n_lon: int, lmax: int) -> int:
+    return int(load().aurora_hip_sphere_synthesis_workspace_bytes(n_planes, n_lat, n_lon, lmax))
+
+
+def _sphere_table(fn: str, table: torch.Tensor, lmax: int) -> tuple:
+    """`table` is a packed ((lmax + 1)(lmax + 2) / 2, n_lat) fp64 table on a device: (the device, n_lat)."""
+    assert lmax >= 0, f"{fn}: lmax must be at least 0, got {lmax}"
+    _operand(fn, "table", table, torch.float64, "((lmax + 1)(lmax + 2) / 2, n_lat) fp64 matrix", dim=2)
+    n_rows, n_lat = table.shape
+    assert n_rows == (lmax + 1) * (lmax + 2) // 2, f"{fn}: the table has {n_rows} rows, lmax = {lmax} needs {(lmax + 1) * (lmax + 2) // 2}"
+    return table.device, n_lat
+
+
+def sphere_analysis(fields: list[torch.Tensor], table: torch.Tensor, lmax: int,
+                    pole_rows: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The spherical-harmonic coefficients (include/aurora_hip.h) of every plane of `fields`, in ONE aurora_hip_sphere_analysis
+    call of two launches: an (n_planes, lmax + 1 [m], lmax + 1 [l]) complex128 tensor, 0 where l < m and NaN for an invalid
+    plane, the (n_planes,) bool validity and the (n_planes,) int32 counts of dropped pole rows, on the device.
+
+    fields: a list of fp32 (..., n_lat, n_lon) tensors on one device with row-major contiguous planes (any leading strides, any
+    4-byte plane alignment); table: the packed ANALYSIS table of `sphere_spectra_power`; pole_rows: as there.  The
+    plane-pointer table is cached by address as in `scores_sums`, the twiddle table per n_lon; the only temporary is the
+    workspace (`sphere_analysis_workspace_bytes`: 16 (lmax + 1) n_lat bytes per plane).  The host does not wait for the device."""
+    lmax = int(lmax)
+    dev, n_lat = _sphere_table("sphere_analysis", table, lmax)
+    n_lon = fields[0].shape[-1] if fields else 2
+    assert 2 <= n_lon <= SPECTRA_MAX_LON, f"sphere_analysis: n_lon must be in 2..{SPECTRA_MAX_LON}, got {n_lon}"
+    assert lmax <= min((n_lat - 1) // 2, (n_lon - 1) // 2), \
+        f"sphere_analysis: lmax = {lmax} is above min((n_lat - 1) // 2, (n_lon - 1) // 2) on a {n_lat} x {n_lon} grid"
+    planes = _planes("sphere_analysis", [("field", fields)], dev, "table", n_lat, n_lon)
+    n = planes.n
+    coeff = torch.empty(n, lmax + 1, lmax + 1, 2, dtype=torch.float64, device=dev)
+    valid = torch.empty(n, dtype=torch.uint8, device=dev)
+    dropped = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return torch.view_as_complex(coeff), valid.view(torch.bool), dropped
+    at = planes.upload()
+    twiddle = spectra_twiddle(n_lon, dev)
+    nbytes = sphere_analysis_workspace_bytes(n, n_lat, n_lon, lmax)
+    workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)   # (from torch's caching allocator: no hipMalloc warm)
+    K = n_lon // 2 + 1
+    work = 2.0 * (n * n_lat) * K * (2 * (lmax + 1)) + 2.0 * (2 * n) * n_lat * table.shape[0]
+    _launch(dev, "sphere_analysis", work, "aurora_hip_sphere_analysis", at["field"], n, n_lat, n_lon, lmax, int(pole_rows),
+            _ptr(table), _ptr(twiddle), _ptr(coeff), _ptr(valid), _ptr(dropped), _ptr(workspace), nbytes)
+    return torch.view_as_complex(coeff), valid.view(torch.bool), dropped
+
+
+def sphere_synthesis(coeff: torch.Tensor, table: torch.Tensor, n_lon: int, valid: Optional[torch.Tensor] = None, *,
+                     out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The fields of the coefficients (include/aurora_hip.h), in ONE aurora_hip_sphere_synthesis call of two launches: an
+    (n_planes, n_lat, n_lon) fp32 tensor on the device.
+
+    coeff: a contiguous (n_planes, lmax + 1 [m], lmax + 1 [l]) complex128 tensor on a device (elements with l < m are not read);
+    table: the packed SYNTHESIS table, ((lmax + 1)(lmax + 2) / 2, n_lat) fp64 on that device; valid: a contiguous (n_planes,)
+    bool tensor there -- a plane whose entry is False comes out as NaN -- or None: every plane is synthesised; out: a
+    contiguous fp32 tensor of the result's shape to write into (any 4-byte alignment), allocated when not given.  The twiddle
+    table is kept per n_lon; the only temporary is the workspace (`sphere_synthesis_workspace_bytes`: 16 (lmax + 1) n_lat bytes
+    per plane).  The host does not wait for the device."""
+    assert coeff.is_cuda and coeff.dtype == torch.complex128 and coeff.dim() == 3 and coeff.shape[1] == coeff.shape[2] and \
+        coeff.is_contiguous(), "sphere_synthesis: coeff must be a contiguous (n_planes, lmax + 1, lmax + 1) complex128 tensor on the device"
+    n, lmax, n_lon = coeff.shape[0], coeff.shape[1] - 1, int(n_lon)
+    dev, n_lat = _sphere_table("sphere_synthesis", table, lmax)
+    assert coeff.device == dev, "sphere_synthesis: every tensor must be on the device of table"
+    assert 2 <= n_lon <= SPECTRA_MAX_LON, f"sphere_synthesis: n_lon must be in 2..{SPECTRA_MAX_LON}, got {n_lon}"
+    assert lmax <= min((n_lat - 1) // 2, (n_lon - 1) // 2), \
+        f"sphere_synthesis: lmax = {lmax} is above min((n_lat - 1) // 2, (n_lon - 1) // 2) on a {n_lat} x {n_lon} grid"
+    if valid is not None:
+        _like("sphere_synthesis", "valid", valid, (n,), torch.bool, dev, "table")
+    (out,) = _outputs("sphere_synthesis", None if out is None else (out,), (((n, n_lat, n_lon), torch.float32, "out"),), dev, "table")
+    if n == 0:
+        return out
+    twiddle = spectra_twiddle(n_lon, dev)
+    nbytes = sphere_synthesis_workspace_bytes(n, n_lat, n_lon, lmax)
+    workspace = torch.empty(nbytes, dtype=torch.uint8, device=dev)   # (from torch's caching allocator: no hipMalloc warm)
+    work = 2.0 * (2 * n) * n_lat * table.shape[0] + 2.0 * (n * n_lat) * (n_lon // 2 + 1) * (2 * (lmax + 1))
+    _launch(dev, "sphere_synthesis", work, "aurora_hip_sphere_synthesis", _ptr(coeff), None if valid is None else _ptr(valid), n,
+            n_lat, n_lon, lmax, _ptr(table), _ptr(twiddle), _ptr(out), _ptr(workspace), nbytes)
+    return out
 
 
 # ---- events: contingency tables and fractions skill score (aurora_hip_event_scores) -----------------------------------

@@ -57,7 +57,8 @@ captured in a graph.  Fields on the CPU take THE RULE in numpy: `np.fft.rfft`, t
 table.
 
 Not offered: degrees above (H - 1) // 2 (a least-squares analysis), synthesis, the coefficients as an output, vector harmonics
-from u and v directly, latitude bands and `BandBatch`.
+from u and v directly, latitude bands and `BandBatch`.  (The coefficients, the synthesis and filters by total wavenumber built
+from them are aurora_amd/sphere_transform.py's: `sphere_analysis`, `sphere_synthesis`, `sphere_filter`.)
 """
 
 from __future__ import annotations

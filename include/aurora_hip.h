@@ -901,6 +901,42 @@ int aurora_hip_sphere_spectra(const float* const* pred_planes, const float* cons
                               int n_lon, int lmax, int pole_rows, const double* table, const double* twiddle, double* power,
                               uint8_t* valid, int32_t* pole_rows_dropped, void* workspace, size_t workspace_bytes, void* stream);
 
+/* ---- spherical-harmonic analysis and synthesis on the device (aurora_amd.sphere_transform; not in the reference) ----------
+ * The grid, `table` (the ANALYSIS table A), LMAX, `twiddle`, `pole_rows` and VALIDITY of aurora_hip_sphere_spectra, without a
+ * truth.  THE RULE of aurora_amd/sphere_transform.py, for the device:
+ *   ANALYSIS   F_m(i) as above; a_lm = sum_i A[m][l][i] F_m(i), rows ascending.  coeff holds n_planes x (lmax + 1) x (lmax + 1)
+ *              pairs (re, im) of doubles, coeff[2 ((plane (lmax + 1) + m) (lmax + 1) + l)]: m first, then l.  The call writes
+ *              EVERY element: 0 where l < m, NaN in both parts for an invalid plane (valid[plane] = 0); a dropped pole row
+ *              enters as zeros and is counted.  The buffer needs no clearing.
+ *   SYNTHESIS TABLE  `table` of aurora_hip_sphere_synthesis holds P[m][l][i] = Pbar_l^m(sin lat_i), the basis WITHOUT the
+ *              quadrature weights, packed exactly like A (same offset formula, same size, same 1 GiB cap).
+ *   INVERSE LEGENDRE  G_m(i) = sum_{l = m .. lmax} b_lm P[m][l][i], l ascending in steps of 4 in the fp64 accumulator of
+ *              v_mfma_f64_16x16x4_f64; a step beyond lmax multiplies zeros.  Elements of coeff with l < m are not read.
+ *   INVERSE ZONAL  y_i[n] = sum_{m = 0 .. lmax} c_m (Re G_m(i) cos(2 pi m n / N) - Im G_m(i) sin(2 pi m n / N)), c_0 = 1 and
+ *              c_m = 2 otherwise, m ascending, FOLDED: for 0 <= n <= N/2, E = sum c_m Re G cos and O = sum c_m Im G sin against
+ *              `twiddle` at (m n) mod N; out[n] = (float)(E - O) and, for 0 < n < N/2, out[N - n] = (float)(E + O): one
+ *              rounding to fp32.  out: n_planes contiguous planes of n_lat x n_lon floats, 4-byte aligned.
+ *   INVALID    valid may be NULL (every plane is synthesised); a plane with valid[plane] = 0 is NaN at every point.  A
+ *              dropped pole row is synthesised like any other row.
+ * Two launches each.  Analysis: the zonal stage of aurora_hip_sphere_spectra, then the Legendre stage with one wavefront per
+ * (16 degrees, 16 consecutive m, 16 planes), every such pair launched, which stores its accumulators.  Synthesis: the inverse
+ * Legendre stage with one wavefront per (16 latitudes, one m, 16 planes), which writes G as (re, im) in the order [plane][m][i],
+ * then the folded inverse tile per 16 grid rows, the columns n = 0 .. N/2 in passes of 768, stored 4 bytes at a time.  No
+ * floating-point atomics; a plane's result is repeatable bit for bit and does not depend on the other planes of the call or
+ * on pointer alignment.  Every table, coefficient and workspace index is clamped into its array.  workspace: 16-byte aligned, no
+ * initialisation needed: n_planes x 16 (lmax + 1) H bytes of F, then n_planes x ceil(H / 32) x 2 int32 flags, rounded up to 16
+ * = aurora_hip_sphere_analysis_workspace_bytes(...); n_planes x 16 (lmax + 1) H bytes of G
+ * = aurora_hip_sphere_synthesis_workspace_bytes(...) (0 for an argument out of range).  n_planes = 0 is a no-op.  The inputs
+ * are not modified.  No host synchronisation, no allocation, no environment variable: capturable in a hipGraph. */
+size_t aurora_hip_sphere_analysis_workspace_bytes(int n_planes, int n_lat, int n_lon, int lmax);
+int aurora_hip_sphere_analysis(const float* const* planes, int n_planes, int n_lat, int n_lon, int lmax, int pole_rows,
+                               const double* table, const double* twiddle, double* coeff, uint8_t* valid,
+                               int32_t* pole_rows_dropped, void* workspace, size_t workspace_bytes, void* stream);
+size_t aurora_hip_sphere_synthesis_workspace_bytes(int n_planes, int n_lat, int n_lon, int lmax);
+int aurora_hip_sphere_synthesis(const double* coeff, const uint8_t* valid, int n_planes, int n_lat, int n_lon, int lmax,
+                                const double* table, const double* twiddle, float* out, void* workspace, size_t workspace_bytes,
+                                void* stream);
+
 /* ---- events: contingency tables and the Fractions Skill Score on the device (aurora_amd.event_scores; not in the reference)
  * Planes as above.  A point (i, j) is VALID where pred and truth are both finite.  For plane k, threshold
  * thr = thresholds[k T + t] (fp32, compared in fp32) and the odd window size n = scales[s] = 2 h + 1:
